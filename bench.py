@@ -9,11 +9,13 @@ SAO statistics / decision / syntax / offsets, CABAC of the CTU row's sub-stream,
 escaping on the host; the access units are delivered inside the timed region (the pipelined call delivers a step's units with the next call: the pipeline is empty when
 the region starts and flushed before it ends).  The source pictures are resident in HBM before the timed region starts.  Warm-up frames are the first frames of the
 sequences (the I frame and the first P frames), the timed frames the P frames that follow - every frame depends on the reconstruction of the one before, nothing is
-replayed or cached.  Every access unit of every sequence is checked against the compiled reference's per-frame digests of its clip (tests/golden/bench_md5.json:
-`stream_matches_reference`, `frames_checked_against_reference`, `clips`) for any --steps / --warmup the fixtures cover (24-40 frames).  Beside the headline:
-`single_sequence` (one sequence alone, frame by frame and with its engines overlapped in one launch: hmr_gpu_enc_encode_chain), `single_thread_order`
-(wfpp_num_threads = 1, the reference's deterministic single-thread stream 2f0c3447...), `at_2160p`, `cfg3_2160p_cbr` (BASELINE configs[2]: rate control in the CTU
-kernel), `cfg5_2160p_intra_rdfull` (configs[4]: all-intra, full RDO, intra TU depth 4).
+replayed or cached.  A plain run does only that: it sets up, warms up, times --steps steps, writes the last step's access units with --dump-outputs DIR (.npy, for
+comparing two builds output for output) and prints the line.  With --full, every access unit of every sequence is checked against the compiled reference's per-frame
+digests of its clip (tests/golden/bench_md5.json: `stream_matches_reference`, `frames_checked_against_reference`, `clips`; null in a plain run) for any --steps /
+--warmup the fixtures cover (24-40 frames), and beside the headline come `single_sequence` (one sequence alone, frame by frame and with its engines overlapped in
+one launch: hmr_gpu_enc_encode_chain), `single_thread_order` (wfpp_num_threads = 1, the reference's deterministic single-thread stream 2f0c3447...),
+`serial_order_batch`, `at_2160p`, `cfg3_2160p_cbr` (BASELINE configs[2]: rate control in the CTU kernel), `cfg5_2160p_intra_rdfull` (configs[4]: all-intra, full RDO,
+intra TU depth 4).
 
 Multi-GPU (--gpus N under torch.distributed.run): one engine per GPU, as BASELINE.json's north_star and configs[3] say - the reference's
 num_enc_engines = N frame pipeline (encoder_engine_thread, hmr_encoder_lib.c:3043) with engine k on rank k.  Every rank keeps one engine object of every
@@ -24,8 +26,8 @@ the reference's num_enc_engines = N stream (oracle/ref_ctudump.c's engine turnst
 
 Extra objects: `roofline` for k_encode_pool (98 % of a step): algorithmic bytes per SURVEY.md 8-d against the 8 TB/s HBM peak, the fabric traffic from the
 calibrated counter passes of this build, and `issue_bound` - what actually binds the kernel (the issue latency of two wavefronts per SIMD and the memory trips of
-their dependent chains), with the ceiling measured live by an issue-rate probe; `roofline.subpel_planes`: the bandwidth-bound phase-plane kernels measured live;
-`cpu_baseline`: the compiled reference (oracle/_ref/ref_lockstep) timed on this host on the same configuration by its own clock - one process per physical core
+their dependent chains), with --full the ceiling measured live by an issue-rate probe; `roofline.subpel_planes` (--full): the bandwidth-bound phase-plane kernels measured
+live; `cpu_baseline` (--full): the compiled reference (oracle/_ref/ref_lockstep) timed on this host on the same configuration by its own clock - one process per physical core
 side by side (the headline of the baseline), one process, and one process with a thread per CTU row.
 """
 import argparse
@@ -159,6 +161,29 @@ def emit(out):
     assert len(text) < 4096, f"headline line grew to {len(text)} bytes"
     sys.stdout.flush()
     print(text, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, units):
+    """--dump-outputs DIR: what the last timed step handed its caller - one access unit per sequence - as float32 / float64 .npy files, so that two builds can be compared
+    output for output.  access_unit_bytes.npy: the length of each sequence's access unit; access_units.npy: their bytes, concatenated in the order of the sequences.  Where
+    that exceeds DUMP_LIMIT_BYTES in all, access_units.npy holds a fixed seeded sample of the bytes and access_units_index.npy their positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sizes = np.array([len(u) for u in units], dtype=np.float64)
+    data = np.frombuffer(b"".join(units), dtype=np.uint8)
+    arrays = {"access_unit_bytes": sizes}
+    room = DUMP_LIMIT_BYTES - sizes.nbytes - (1 << 16)        # (room for the .npy headers)
+    if 4 * data.size <= room:
+        arrays["access_units"] = data.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(data.size, size=room // 12, replace=False))
+        arrays["access_units"] = data[idx].astype(np.float32)
+        arrays["access_units_index"] = idx.astype(np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def load_lib():
@@ -504,6 +529,10 @@ def main():
     ap.add_argument("--device", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--batched", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--batch", type=int, default=0, help="sequences of the multi_stream_batched measurement (one launch for all CTU stages; 0 = skip)")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the check of every access unit against the reference's digests, the secondary sections "
+                    "(single_sequence, single_thread_order, serial_order_batch, at_2160p, cfg3_2160p_cbr, cfg5_2160p_intra_rdfull), the live roofline probes and cpu_baseline; "
+                    "a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned (every sequence's access unit) as .npy files in DIR")
     a = ap.parse_args()
     if a.multi_stream_child:
         width, height, keys = WORKLOADS[a.workload]
@@ -538,25 +567,31 @@ def main():
 
     lib = load_lib()
     if world > 1:
-        out = run_engine_ring(a, world, rank, local, torch)
+        last_units = []
+        out = run_engine_ring(a, world, rank, local, torch, last_units=last_units)
         if rank == 0:
-            if not a.no_cpu_baseline:
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, last_units)
+            if a.full and not a.no_cpu_baseline:
                 width, height, keys = WORKLOADS[a.workload]
                 out["cpu_baseline"] = cpu_baseline(width, height, {k: v for k, v in keys.items() if k != "wpp"}, a.cpu_frames)
             emit(out)
         dist.destroy_process_group()
-        if not out["stream_matches_reference"]:
+        if out["stream_matches_reference"] is False:
             print("bench.py: access units differ from the reference's", file=sys.stderr)
             sys.exit(3)
         return
-    out = run_workload(lib, a, a.workload, world, rank, local, torch, sequences=a.sequences)
+    last_units = []
+    out = run_workload(lib, a, a.workload, world, rank, local, torch, sequences=a.sequences, last_units=last_units)
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, last_units)
         width, height, keys = WORKLOADS[a.workload]
-        if world == 1 and a.sequences > 1:
+        if a.full and world == 1 and a.sequences > 1:
             one = run_workload(lib, a, a.workload, world, rank, local, torch)
             out["single_sequence"] = {k: one[k] for k in ("value", "unit", "ms_per_step", "stream_md5", "stream_matches_reference", "frames_checked_against_reference", "schedule")}
             out["single_sequence"]["note"] = "one sequence alone on the GPU (17 of the 256 CUs busy): the latency of the row-parallel CTU chain"
-        if world == 1 and a.workload == "cfg2-1080p-encode" and not a.no_single_thread_order:
+        if a.full and world == 1 and a.workload == "cfg2-1080p-encode" and not a.no_single_thread_order:
             other = run_workload(lib, a, "cfg2-1080p-encode-single-thread-order", world, rank, local, torch)
             out["single_thread_order"] = {k: other[k] for k in ("value", "unit", "ms_per_step", "stream_md5", "stream_matches_reference", "frames_checked_against_reference", "schedule")}
             out["single_thread_order"]["note"] = "the same encode with wfpp_num_threads = 1: output identical to the reference's single-thread run (md5 2f0c3447...), which costs guesses, verification and re-encode passes"
@@ -572,7 +607,7 @@ def main():
             if a.sequences > 1:
                 big1 = run_workload(lib, b, "cfg2-2160p-encode", world, rank, local, torch)
                 out["at_2160p"]["single_sequence"] = {k: big1[k] for k in ("value", "ms_per_step", "stream_matches_reference")}
-        if world == 1 and a.workload == "cfg2-1080p-encode" and not a.no_single_thread_order and a.sequences > 1:
+        if a.full and world == 1 and a.workload == "cfg2-1080p-encode" and not a.no_single_thread_order and a.sequences > 1:
             # the reference's deterministic single-thread order (wfpp_num_threads = 1: BASELINE.md's parity mode, md5 2f0c3447... for the published clip, no pinned
             # interleaving) as a BATCH: hmr_gpu_enc_create_serial_pool runs a picture CTU by CTU in raster order as tasks of the pool - one decision in flight per
             # picture, so the launch takes the batch call's maximum of 512 pictures
@@ -584,7 +619,7 @@ def main():
             out["serial_order_batch"]["sequences"] = 512
             out["serial_order_batch"]["note"] = ("wfpp_num_threads = 1, the reference's single-thread order, 512 sequences (eight clips) per launch: every stream equal to the plain "
                                                  "reference's (ref_lockstep, no turnstile); one sequence alone in this order: single_thread_order")
-        if world == 1 and a.workload == "cfg2-1080p-encode" and not a.no_single_thread_order:
+        if a.full and world == 1 and a.workload == "cfg2-1080p-encode" and not a.no_single_thread_order:
             # ONE sequence with its engines overlapped on this GPU (hmr_gpu_enc_encode_chain: the frames of a chain in one launch of the CTU kernel, every engine
             # starting its next frame when its last is finished; tools/chain_bench.py): the reference's num_enc_engines pipeline, streams checked against its digests
             import chain_bench
@@ -617,7 +652,7 @@ def main():
                 if a.sequences > 1:
                     r51 = run_workload(lib, c5, "cfg5-2160p-intra-rdfull", world, rank, local, torch)
                     out["cfg5_2160p_intra_rdfull"]["single_sequence"] = {k: r51[k] for k in ("value", "ms_per_step", "stream_matches_reference")}
-        if world == 1:
+        if a.full and world == 1:
             out["roofline"]["subpel_planes"] = subpel_planes_roofline(lib, torch, width, height)
             probe = valu_issue_probe(lib, local)
             if out["roofline"].get("issue_bound") is not None:
@@ -643,7 +678,7 @@ def main():
             out["multi_stream"] = multi_stream_child(local, a.workload, a.streams)
         if world == 1 and a.batch > 1:
             out["multi_stream_batched"] = multi_stream_child(local, a.workload, a.batch, batched=True)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(width, height, {k: v for k, v in keys.items() if k != "wpp"}, a.cpu_frames)
             # the host's figures beside the other sections too: the same three measurements (one process, one thread per CTU row, a process per usable core) of the
             # compiled reference on that section's configuration, on a few frames (2160p: 6; all-intra RD_FULL: 3)
@@ -662,9 +697,10 @@ def main():
         dist.destroy_process_group()
 
 
-def run_engine_ring(a, world, rank, local, torch, adapter=None):
+def run_engine_ring(a, world, rank, local, torch, adapter=None, last_units=None):
     """--gpus N > 1: the engine ring (module docstring).  `adapter`: the encoder behind homerhevc_amd.engines.EngineRing - the product's GpuEngines unless a test brings its
-    own (tests/test_bench_gloo.py runs this function at world 2 over gloo with the one-lane checker build behind it, `adapter.on_cpu`)."""
+    own (tests/test_bench_gloo.py runs this function at world 2 over gloo with the one-lane checker build behind it, `adapter.on_cpu`).  `last_units`, a list: filled with
+    this rank's access units of the last frame, in the order of their sequences."""
     import torch.distributed as dist
     import encoder_cases as ec
     from homerhevc_amd.engines import EngineRing, GpuEngines
@@ -718,6 +754,9 @@ def run_engine_ring(a, world, rank, local, torch, adapter=None):
         kept.extend(ring.flush())
 
     dt = measure(step, a.warmup, nframes, world, (lambda: None) if on_cpu else torch.cuda.synchronize, "cpu" if host_tensors else "cuda", flush if pipelined else None)
+    if last_units is not None and kept:
+        f_last = max(f for f, _ in kept)
+        last_units[:] = [au for f, units in kept if f == f_last for _, au in sorted(units.items())]
     for f, units in kept:
         for s, au in units.items():
             produced[0] += 1
@@ -763,10 +802,11 @@ def run_engine_ring(a, world, rank, local, torch, adapter=None):
     }
 
 
-def run_workload(lib, a, workload, world, rank, local, torch, sequences=1, serial_pool=False):
+def run_workload(lib, a, workload, world, rank, local, torch, sequences=1, serial_pool=False, last_units=None):
     """`sequences` independent sequences of the workload per GPU: 1 = hmr_gpu_enc_encode_source frame by frame; more = one batch call per step (ONE launch for the
     CTU stages of all of them: a pool of CTU tasks on four row workers per CU; the pipelined call by default, whose access units come with the next call), every
-    access unit kept and checked against the reference's digests after the timed region."""
+    access unit kept and, with --full, checked against the reference's digests after the timed region.  `last_units`, a list: filled with the access units of the
+    last timed step, one per sequence."""
     import encoder_cases as ec
     width, height, keys = WORKLOADS[workload]
     keys = dict(keys)
@@ -838,7 +878,9 @@ def run_workload(lib, a, workload, world, rank, local, torch, sequences=1, seria
         step_wall.append(time.perf_counter() - t_step)
 
     dt = measure(step, a.warmup, nframes, world, torch.cuda.synchronize, "cuda", flush if pipelined else None)
-    for units in kept:              # every access unit of every sequence, in the order delivered
+    if last_units is not None:
+        last_units[:] = [C.string_at(buf, nbytes.value)] if S == 1 else kept[-1]
+    for units in kept if a.full else []:        # every access unit of every sequence, in the order delivered
         for i in range(S):
             md5s[i].update(units[i])
         for i in range(nrep):
@@ -855,7 +897,7 @@ def run_workload(lib, a, workload, world, rank, local, torch, sequences=1, seria
         lib.hmr_gpu_destroy(x)          # (a context holds pinned host memory, HBM staging and a stream)
     md5 = md5s[0]
     # every sequence of a clip must have produced the stream of the clip's first sequence, and that one the reference's, access unit by access unit
-    all_same = all(md5s[i].hexdigest() == md5s[i % nrep].hexdigest() for i in range(S))
+    all_same = all(md5s[i].hexdigest() == md5s[i % nrep].hexdigest() for i in range(S)) if a.full else None
 
     if True:
         timed = stats[a.warmup:]
@@ -910,14 +952,15 @@ def run_workload(lib, a, workload, world, rank, local, torch, sequences=1, seria
                          "issue_cycles_over_worker_cycles": round(4 * all_insts / (256 * WORKERS_PER_CU * 2.4e9 / fps_kernel), 3),
                          "build": pm.get("source_digest") or pm.get("build_commit"),
                          "source": f"{os.path.relpath(pm_path, ROOT)} (rocprofv3 --pmc passes of this command), instruction counts per encoded frame x this run's frames/s of the kernel"}
-        digest = md5.hexdigest()
+        digest = md5.hexdigest() if a.full else None
         per_clip = {}
         matches, checked = True, None
-        for i in range(nrep):
+        for i in range(nrep if a.full else 0):
             ok_i, n_i = check_against_reference(seed_workload(workload, seeds[i]), cumulative[i])
             per_clip[str(seeds[i])] = {"stream_md5": md5s[i].hexdigest(), "matches_reference": bool(ok_i), "frames_checked": n_i, "sequences": len(range(i, S, nrep))}
             matches = matches and ok_i
             checked = n_i if checked is None else min(checked, n_i)
+        verdict = bool(matches and all_same) if a.full else None      # (a plain run does not check its output: None)
         out = {
             "metric": "encoded frames/sec, 1080p & 2160p YUV420 fixed-QP IPPP, 1/2/4/8 MI355X", "value": round(world * S * a.steps / dt, 4), "unit": "frames/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -925,13 +968,13 @@ def run_workload(lib, a, workload, world, rank, local, torch, sequences=1, seria
             "config": {"workload": workload, "sequences_per_gpu": S, "frames_per_step": S, "wfpp_num_threads": int(keys.get("wpp", 1)), "width": width, "height": height, "frames_in_sequence": nframes, "gop": "all intra (IMAGE_I forced)" if image_type else "IPPP intra_period=100", "qp": 32,
                        "rd_mode": int(keys.get("rd", 2)), "max_intra_tr_depth": int(keys.get("intra_tr", 2)), "performance_mode": int(keys.get("perf", 2)), "sao": 1, "parallelism": (f"{S} independent sequences per GPU, one launch per step for their CTU stages (a pool of CTU tasks on {WORKERS_PER_CU} row workers per CU)" if S > 1 else "one sequence"),
                        # (the driver keeps `config` verbatim: the run's own verdict on its output sits here too)
-                       "stream_matches_reference": bool(matches and all_same), "frames_checked_against_reference": checked,
+                       "stream_matches_reference": verdict, "frames_checked_against_reference": checked,
                        "timed_region": "per frame: phase planes of the reference, CTU decisions, deblocking, SAO statistics / decision / syntax, CABAC of the CTU rows' sub-streams, SAO offsets and border padding on the device "
                                        "(one launch of k_encode_pool: the decisions and the post-decision tasks of enc_post.h), download of the sub-streams, slice header / entry points / NAL escaping on the host; source in HBM; "
                                        "the first warm-up step is the I frames (warmup_ms_per_step[0])",
                        "call": ("hmr_gpu_enc_encode_batch_pipelined: a step's download and entropy coding run under the next step's CTU launch; the pipeline is empty when the timed "
                                 "region starts and flushed inside it" if pipelined else "hmr_gpu_enc_encode_batch" if S > 1 else "hmr_gpu_enc_encode_source")},
-            "stream_md5": digest, "stream_matches_reference": bool(matches and all_same), "frames_checked_against_reference": checked,
+            "stream_md5": digest, "stream_matches_reference": verdict, "frames_checked_against_reference": checked,
             "evaluations_on_a_stale_prediction_window": stale_total,
             "clips": {"distinct": nrep, "by_seed": per_clip, "sequences_of_a_clip_identical": all_same,
                       "note": "sequence i encodes clip i mod distinct (tools/gen_yuv.py seeds: own texture, pan, pattern, box path); each clip's stream is checked against the compiled reference's digests of that clip"},

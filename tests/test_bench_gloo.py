@@ -117,8 +117,10 @@ class CpuEngines:          # the adapter EngineRing asks for, over the checker b
         lib.henc_cpu_import_reference(hnd, *self._ptrs(row))
 
 a = argparse.Namespace(workload="cfg2-416x240-encode", warmup=1, steps=4, sequences=2, no_pipeline=True, no_cpu_baseline=True, gpus=world)
-out = bench.run_engine_ring(a, world, rank, 0, torch, adapter=CpuEngines())
+units = []
+out = bench.run_engine_ring(a, world, rank, 0, torch, adapter=CpuEngines(), last_units=units)
 if rank == 0:
+    out["last_unit_bytes"] = [len(u) for u in units]
     print(json.dumps(out), flush=True)
 dist.destroy_process_group()
 """
@@ -143,6 +145,8 @@ def test_bench_engine_ring_entry_at_world_2(tmp_path):
     assert line["stream_matches_reference"] is True and line["config"]["stream_matches_reference"] is True
     assert line["access_units_produced"] == 4 * 5 and line["access_units_checked_against_reference"] == 20 and line["access_units_differing"] == 0
     assert line["value"] > 0 and abs(line["value"] - 4 * 4 / (line["ms_per_step"] * 4 / 1e3)) < 1e-2 * line["value"]
+    # what --dump-outputs writes: rank 0's access units of the last frame, one per sequence it encoded
+    assert len(line["last_unit_bytes"]) == 2 and min(line["last_unit_bytes"]) > 0
 
 
 def test_gpus_flag_must_agree_with_the_launcher():

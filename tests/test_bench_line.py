@@ -87,3 +87,24 @@ def test_describe_keys():
     assert bench.describe_keys({}) == "IPPP QP32"
     assert bench.describe_keys(bench.WORKLOADS["cfg3-2160p-cbr"][2]) == "IPPP CBR 20000 kbps perf=1"
     assert bench.describe_keys(bench.WORKLOADS["cfg5-2160p-intra-rdfull"][2]) == "all-intra QP32 rd=1 intra_tr=4 perf=0"
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's access units as float .npy files, every byte while they fit the size limit, past it the same seeded sample every time"""
+    import numpy as np
+    units = [bytes((i * 7 + k) % 256 for k in range(50 + 13 * i)) for i in range(6)]
+    bench.dump_outputs(str(tmp_path / "all"), units)
+    sizes, data = np.load(tmp_path / "all" / "access_unit_bytes.npy"), np.load(tmp_path / "all" / "access_units.npy")
+    assert sizes.dtype == np.float64 and sizes.tolist() == [len(u) for u in units]
+    assert data.dtype == np.float32 and data.astype(np.uint8).tobytes() == b"".join(units)
+    assert not (tmp_path / "all" / "access_units_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", (1 << 16) + 48 + 12 * 100)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), units)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_LIMIT_BYTES
+    idx, data = np.load(tmp_path / "a" / "access_units_index.npy"), np.load(tmp_path / "a" / "access_units.npy")
+    assert len(idx) == len(data) == 100 and np.all(np.diff(idx) > 0)
+    assert data.astype(np.uint8).tobytes() == bytes(b"".join(units)[int(k)] for k in idx)
+    for name in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))

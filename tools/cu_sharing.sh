@@ -6,7 +6,7 @@ V=${1:-q3m}
 cp homerhevc_amd/libhomer_gpu.so /tmp/libhomer_gpu.product.so
 cp build/variants/$V/libhomer_gpu.so homerhevc_amd/libhomer_gpu.so
 run() {
-  python3 bench.py --sequences 128 --steps 4 --warmup 3 --no-cpu-baseline --no-single-thread-order 2>/dev/null | python3 -c "
+  python3 bench.py --full --sequences 128 --steps 4 --warmup 3 --no-cpu-baseline --no-single-thread-order 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', 'fps', d['value'], 'kernel ms', d['roofline']['ms_per_launch'], d['stream_matches_reference'])"
 }

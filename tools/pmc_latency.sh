@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 TAG=${1:-r04lat}
 SEQ=${SEQ:-180}
-ARGS="--steps 2 --warmup 2 --streams 0 --no-cpu-baseline --no-single-thread-order --sequences $SEQ"
+ARGS="--full --steps 2 --warmup 2 --streams 0 --no-cpu-baseline --no-single-thread-order --sequences $SEQ"
 rocprofv3 -L 2>/dev/null | grep -o "\b\(TCP\|TCC\|TA\|TD\|SQ\|SQC\|GRBM\|SPI\)_[A-Za-z_0-9]*" | sort -u > $R/gpurun_out/counters_all.txt
 for set in "SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_WAVE_CYCLES SQ_LEVEL_WAVES SQ_WAVES SQ_BUSY_CYCLES" "SQ_INST_LEVEL_SMEM SQ_INSTS_SMEM SQ_INST_LEVEL_LDS SQ_INSTS_LDS SQ_INSTS_FLAT_LDS_ONLY" "SQ_IFETCH_LEVEL SQ_IFETCH SQC_TC_STALL SQC_ICACHE_BUSY_CYCLES SQC_ICACHE_MISSES SQC_ICACHE_REQ"; do
   tag=$(echo $set | cut -d' ' -f1)

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 3 --no-cpu-baseline"
+ARGS="--full --steps 20 --warmup 3 --no-cpu-baseline"
 # kernel durations: the eager replay (one launch at a time - these are the durations bench.py's roofline uses) and the default graph replay
 # (launches of different graph branches overlap, so individual durations stretch)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o kt -- python3 "$ROOT/bench.py" $ARGS --mode eager > "$OUT/bench_under_rocprof.json" 2> "$OUT/kt.err"

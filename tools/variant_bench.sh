@@ -4,7 +4,7 @@
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $ROOT
 NAMES=$1; shift
-ARGS=${@:---sequences 128 --steps 5 --warmup 3 --no-cpu-baseline --no-single-thread-order}
+ARGS="--full ${*:---sequences 128 --steps 5 --warmup 3 --no-cpu-baseline --no-single-thread-order}"
 mkdir -p gpurun_out/variants
 cp homerhevc_amd/libhomer_gpu.so /tmp/libhomer_gpu.product.so
 for n in $NAMES; do
