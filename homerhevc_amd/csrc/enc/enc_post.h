@@ -123,6 +123,17 @@ struct RowEnt {                // the CABAC coder of a CTU row's sub-stream betw
 	uint8_t ctx[CTX_TOTAL + 5], saved[CTX_TOTAL + 5];
 };
 static_assert(sizeof(RowEnt) % 4 == 0, "word copies");
+// The most bytes one CTU can add to its sub-stream: every row's buffer is CTU_STREAM_BOUND x CTU columns, so that no content the reference encodes (it allocates
+// 32 MB per slice and has no bound check, hmr_bitstream.c) can outgrow it.  A context-coded bin writes at most 6 bits (the smallest rLPS is 6: six renormalisation
+// shifts; an MPS shifts once at most), a bypass bin exactly 1.  Per CTU of 8-bit 4:2:0 (levels are int16, so coeff_abs_level_remaining is at most 32 bins):
+//   6144 coefficients x (sig, greater1, greater2: 3 x 6 + sign and remaining: 33)    39168
+//   384 4x4 sub-blocks x coded_sub_block_flag 6                                         288
+//   384 TUs x (last position: 18 context bins x 6 + 6 suffix bits)                      5472
+//   341 transform-tree nodes x (split, cbf_luma, cbf_cb, cbf_cr: 4 x 6)                 1023
+//   64 CUs x (64 context bins x 6 + 160 bypass: split, skip, modes, merge, MVDs, QP)    4352
+//   SAO, the split flags of the coding tree, the sub-stream's end                        256
+// (iid noise at QP 0 takes about 9 KB per CTU: the budget fixture of tests/golden/make_stream_golden.py)
+constexpr int CTU_STREAM_BOUND = (6144 * 51 + 384 * 6 + 384 * 114 + 341 * 24 + 64 * 544) / 8 + 256;
 struct PostPic {
 	int16_t *dbk[3], *fin[3];  // the deblocked picture and the final one (padded planes, first valid sample; the reconstruction is FrameCtx::rec)
 	int units_stride;

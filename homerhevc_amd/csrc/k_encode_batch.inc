@@ -514,6 +514,9 @@ extern "C" int hmr_gpu_enc_encode_chain(hmr_gpu_enc **encs, int n, hmr_gpu_enc *
 		const int rows = s.wpp ? s.hctu : 1;
 		std::vector<uint32_t> row_bytes(g + pitch - POST_MAX_ROWS, g + pitch - POST_MAX_ROWS + rows);
 		size_t total = 0;
+		for (int r = 0; r < rows; r++) total += row_bytes[r];
+		if (e->h_bs.size() < total) e->h_bs.resize(total);
+		total = 0;
 		for (int r = 0; r < rows; r++) {
 			HIP_TRY(hipMemcpyAsync(e->h_bs.data() + total, e->d_bs + (size_t)r * e->row_cap, row_bytes[r], hipMemcpyDeviceToHost, bst));
 			total += row_bytes[r];

@@ -580,9 +580,9 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 		DEV_ALLOC(e->d_rec[c], e->pic_elems[c]);
 	}
 	{
-		// the post-decision stage: row progress, the rows' CABAC coders and sub-streams (8 KB per CTU: forty times what QP 32 needs; a sub-stream that runs
-		// out of room is an error return, not a truncated stream), the SAO Lagrange multipliers of both slice types by QP
-		e->row_cap = s.wctu * 8192;
+		// the post-decision stage: row progress, the rows' CABAC coders and sub-streams (CTU_STREAM_BOUND per CTU, enc_post.h: the most any content can take;
+		// a sub-stream that runs out of room is still an error return, not a truncated stream), the SAO Lagrange multipliers of both slice types by QP
+		e->row_cap = s.wctu * CTU_STREAM_BOUND;
 		DEV_ALLOC(e->d_rows, s.hctu);
 		DEV_ALLOC(e->d_ent, s.hctu);
 		DEV_ALLOC(e->d_bs, (size_t)e->row_cap * s.hctu);
@@ -594,7 +594,6 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 		sao_lambda_table(s, SLICE_I, tab[1]);
 		HIP_TRY(hipMemcpy(e->d_sao_tab, tab, sizeof tab, hipMemcpyHostToDevice));
 		e->h_ent.resize(s.hctu);
-		e->h_bs.resize((size_t)e->row_cap * s.hctu);
 		DEV_ALLOC(e->d_rc_dyn, 1);
 		if (s.rd_mode == RDM_FULL) {
 			for (auto &sim : e->rdsim) sim.init(e->cfg.wfpp_num_threads > 1 ? e->cfg.wfpp_num_threads : 1, s.wctu, s.hctu, s.sao);
@@ -1084,8 +1083,10 @@ int frame_finish(hmr_gpu_enc *e, int slot, uint8_t *stream, long cap, long *stre
 	const int rows = s.wpp ? s.hctu : 1;
 	std::vector<uint32_t> row_bytes(rows);
 	size_t total = 0;
+	for (int r = 0; r < rows; r++) total += row_bytes[r] = (uint32_t)e->h_ent[r].bytecnt;
+	if (e->h_bs.size() < total) e->h_bs.resize(total);      // (the host copy holds what the picture took, not the rows' whole buffers)
+	total = 0;
 	for (int r = 0; r < rows; r++) {
-		row_bytes[r] = (uint32_t)e->h_ent[r].bytecnt;
 		HIP_TRY(hipMemcpyAsync(e->h_bs.data() + total, e->d_bs + (size_t)r * e->row_cap, row_bytes[r], hipMemcpyDeviceToHost, st));
 		total += row_bytes[r];
 	}

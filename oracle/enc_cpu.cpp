@@ -124,7 +124,7 @@ void post_begin_frame(Cpu &c)
 		c.sao_lambda.assign(52 * 2, 0);
 		c.scratch = (PostScratch *)calloc(1, sizeof(PostScratch));
 	}
-	const int row_cap = s.wctu * 24576;
+	const int row_cap = s.wctu * CTU_STREAM_BOUND;
 	c.bs.assign((size_t)row_cap * s.hctu, 0);
 	memset((void *)c.rows.data(), 0, sizeof(PostRow) * s.hctu);
 	memset((void *)c.ent.data(), 0, sizeof(RowEnt) * s.hctu);

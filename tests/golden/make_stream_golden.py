@@ -99,16 +99,34 @@ CASES = [
     ("416x240_scene_cut_perf3_wpp_rows", 416, 240, 26, {"perf": 3, "cut_at": 23, "wpp": 4}),
     ("832x480_qp26_perf3_rdfull_wpp_rows", 832, 480, 3, {"perf": 3, "qp": 26, "rd": 1, "wpp": 8}),
     ("3840x2160_cbr20000_perf1_wpp32", 3840, 2160, 4, {"bitrate_mode": 1, "bitrate": 20000, "perf": 1, "wpp": 32}),       # BASELINE.json configs[2]: 2160p IPPP, CBR 20000 kbps, performance_mode 1       # BASELINE.json configs[3]: 2160p, n_enc_engines = 8     # the 2160p picture of the metric with the reference's maximum of 32 WPP threads for 34 CTU rows (I + P + P)
+    # the content families of tools/gen_yuv.py (noise, extremes, flat, motion, chroma) under the default settings, a low QP, one WPP thread per row, all-intra RD_FULL,
+    # rate control and two engines: FAMILY_CASES, appended below
+    ("1920x1080_motion_wpp_rows", 1920, 1080, 3, {"content": "motion", "wpp": 17}),
+    # the sub-stream budget: iid noise at QP 0 takes about 8.9 KB per CTU (the device's rows once had 8 KB per CTU and refused the picture), one thread and a thread per row
+    ("384x192_noise_qp0", 384, 192, 2, {"content": "noise", "qp": 0}),
+    ("384x192_noise_qp0_wpp_rows", 384, 192, 2, {"content": "noise", "qp": 0, "wpp": 3}),
 ]
+FAMILY_SETTINGS = [("", 4, {}), ("_qp4", 3, {"qp": 4}), ("_wpp_rows", 4, {"wpp": 4}), ("_force_intra_rdfull_tr4_wpp_rows", 2, {"force_intra": 1, "rd": 1, "intra_tr": 4, "wpp": 4}),
+                   ("_cbr1500_perf1_wpp_rows", 6, {"bitrate_mode": 1, "bitrate": 1500, "perf": 1, "wpp": 4}), ("_eng2_wpp_rows", 6, {"engines": 2, "wpp": 4})]
+# (clip seed 1234 unless listed: motion under rate control with seed 1234 is a stream a decoder does not reconstruct as the reference did - drift R1 of tests/decoder_check.py)
+FAMILY_SEEDS = {"416x240_motion_cbr1500_perf1_wpp_rows": 2}
+FAMILY_CASES = []
+for _content in ("noise", "extremes", "flat", "motion", "chroma"):
+    for _name, _frames, _keys in FAMILY_SETTINGS:
+        _case = f"416x240_{_content}{_name}"
+        _seed = FAMILY_SEEDS.get(_case)
+        FAMILY_CASES.append((_case + (f"_clip{_seed}" if _seed else ""), 416, 240, _frames, dict(_keys, content=_content, **({"clip_seed": _seed} if _seed else {}))))
+CASES += FAMILY_CASES
 
 
 def run(width, height, frames, keys):
     keys = dict(keys)
     cut_at = keys.pop("cut_at", None)
     clip_seed = keys.pop("clip_seed", None)
+    content = keys.pop("content", None)
     with tempfile.TemporaryDirectory() as tmp:
         yuv = os.path.join(tmp, "in.yuv")
-        gen_yuv.write_clip(yuv, width, height, frames, seed=clip_seed or 1234, cut_at=cut_at)
+        gen_yuv.write_clip(yuv, width, height, frames, seed=clip_seed or 1234, cut_at=cut_at, content=content or "default")
         turnstile = int(keys.get("wpp", 1)) > 1 or int(keys.get("engines", 1)) > 1
         cmd = [os.path.join(ROOT, "oracle", "_ref", "ref_ctudump" if turnstile else "ref_lockstep"), yuv, os.path.join(tmp, "out.265"), str(width), str(height), str(frames),
                "recon=" + os.path.join(tmp, "rec.yuv")] + [f"{k}={v}" for k, v in keys.items()]
@@ -120,6 +138,8 @@ def run(width, height, frames, keys):
         keys["cut_at"] = cut_at
     if clip_seed is not None:
         keys["clip_seed"] = clip_seed
+    if content is not None:
+        keys["content"] = content
     return {"width": width, "height": height, "frames": frames, "keys": keys, "stream_md5": hashlib.md5(stream).hexdigest(), "stream_bytes": len(stream),
             "nal_sizes": [len(x) for x in stream_diff.split_nals(stream)],
             "recon_md5": [hashlib.md5(rec[f * fsz:(f + 1) * fsz]).hexdigest() for f in range(frames)]}

@@ -37,6 +37,24 @@ def test_checker_build_on_random_configurations():
     assert sum("IDENTICAL" in ln for ln in lines) >= 15
 
 
+FAMILIES = "noise,extremes,flat,motion,chroma"      # tools/gen_yuv.py's hostile content families
+
+
+@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref not built (the reference's sources are only in the build container)")
+def test_checker_build_on_random_configurations_of_hostile_content():
+    """the same random configurations with the picture content drawn from the content families: large levels, 0/255 edges, flat pictures, fast sub-pel motion,
+    full-range chroma"""
+    lines = run(["--content", FAMILIES, "--cases", "16", "--seed", "105", "--max-ctus", "40"], 1200)
+    assert sum("IDENTICAL" in ln for ln in lines) >= 15
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref not built")
+def test_device_encoder_on_random_configurations_of_hostile_content():
+    lines = run(["--gpu", "--content", FAMILIES, "--cases", "40", "--seed", "106", "--max-ctus", "120"], 900)
+    assert sum("IDENTICAL" in ln for ln in lines) >= 35
+
+
 @pytest.mark.gpu
 @pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref not built")
 def test_device_encoder_on_random_configurations():

@@ -15,6 +15,8 @@ import libs
 
 pytestmark = pytest.mark.gpu
 GOLD = json.load(open(os.path.join(ec.GOLDEN, "streams.json")))
+# the fixtures of tools/gen_yuv.py's content families (noise, extremes, flat, motion, chroma), incl. the sub-stream budget case (noise at QP 0)
+CONTENT_CASES = [case for case, g in GOLD.items() if "content" in g["keys"]]
 
 
 @pytest.fixture(scope="module")
@@ -25,6 +27,7 @@ def gpu():
     lib.hmr_gpu_enc_encode.argtypes = [C.c_void_p] + [C.c_char_p] * 3 + [C.c_int, C.c_char_p, C.c_long, C.POINTER(C.c_long), C.c_char_p]
     lib.hmr_gpu_enc_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.hmr_gpu_enc_destroy.argtypes = [C.c_void_p]
+    lib.hmr_gpu_enc_stale_predictions.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
     lib.hmr_gpu_last_error.restype = C.c_char_p
     ctx = C.c_void_p()
     rc = lib.hmr_gpu_create(C.byref(ctx), 0, None)
@@ -33,12 +36,13 @@ def gpu():
     return lib
 
 
-def encode(lib, case, raw_recon=None):
+def encode(lib, case, raw_recon=None, stale=None):
     g = GOLD[case]
     w, h, frames = g["width"], g["height"], g["frames"]
     keys = dict(g["keys"])
     cut_at = keys.pop("cut_at", None)
     clip_seed = keys.pop("clip_seed", 1234)
+    content = keys.pop("content", "default")
     image_type = 3 if keys.pop("force_intra", 0) else 0          # encoder_in_out_t.image_type: IMAGE_I on every frame
     cfg = ec.default_cfg(w, h, **keys)
     enc = C.c_void_p()
@@ -48,7 +52,7 @@ def encode(lib, case, raw_recon=None):
     rec = C.create_string_buffer(w * h * 3 // 2)
     nbytes = C.c_long()
     stream, recon, log = b"", [], []
-    for f, planes in enumerate(ec.clip_frames(w, h, frames, cut_at, clip_seed)):
+    for f, planes in enumerate(ec.clip_frames(w, h, frames, cut_at, clip_seed, content)):
         st = lib.hmr_gpu_enc_encode(enc, *planes, image_type, buf, len(buf), C.byref(nbytes), rec)
         assert st in (1, 2), lib.hmr_gpu_last_error()
         stream += buf.raw[:nbytes.value]
@@ -58,6 +62,10 @@ def encode(lib, case, raw_recon=None):
         p, n, ms, tot = C.c_int(), C.c_int(), C.c_float(), C.c_float()
         lib.hmr_gpu_enc_last_stats(enc, C.byref(p), C.byref(n), C.byref(ms), C.byref(tot))
         log.append(f"f{f}: {p.value} passes {n.value} encodes {ms.value:.1f}/{tot.value:.1f} ms")
+        if stale is not None:
+            last, total = C.c_long(), C.c_long()
+            assert lib.hmr_gpu_enc_stale_predictions(enc, C.byref(last), C.byref(total)) == 0
+            stale.append(last.value)
     lib.hmr_gpu_enc_destroy(enc)
     print(case, "; ".join(log))
     return stream, recon
@@ -70,10 +78,12 @@ def encode(lib, case, raw_recon=None):
                                   "416x240_cbr400_perf1", "416x240_vbr400", "416x240_force_intra_rdfull_tr4", "416x240_rdfull", "328x264_force_intra_rdfull_tr3_perf0",
                                   "3840x2160_cbr20000_perf1", "3840x2160_force_intra_rdfull_tr4_perf0",
                                   # rate control with several engines
-                                  "416x240_cbr400_perf1_eng2_wpp_rows", "416x240_vbr400_eng3_wpp_rows", "832x480_cbr1500_perf1_eng4_wpp_rows"])
+                                  "416x240_cbr400_perf1_eng2_wpp_rows", "416x240_vbr400_eng3_wpp_rows", "832x480_cbr1500_perf1_eng4_wpp_rows"]
+                         # hostile picture content: noise (and the sub-stream budget at QP 0), hard 0/255 edges, flat pictures, fast sub-pel motion, full-range chroma
+                         + CONTENT_CASES)
 def test_device_stream_is_byte_identical_to_the_reference(gpu, case):
-    raw = []
-    stream, recon = encode(gpu, case, raw_recon=raw)
+    raw, stale = [], []
+    stream, recon = encode(gpu, case, raw_recon=raw, stale=stale)
     g = GOLD[case]
     first_bad = next((f for f in range(g["frames"]) if recon[f] != g["recon_md5"][f]), None)
     assert first_bad is None, f"reconstructed picture {first_bad} differs"
@@ -81,6 +91,8 @@ def test_device_stream_is_byte_identical_to_the_reference(gpu, case):
     assert hashlib.md5(stream).hexdigest() == g["stream_md5"]
     # the decoder-side check: what the device wrote decodes (sub-stream ends, entry points, ranges) to the pictures the device reconstructed (tests/decoder_check.py)
     decoder_check.check(stream, g, case, raw)
+    if case in CONTENT_CASES:
+        assert stale == [0] * g["frames"], stale      # (no evaluation on a stale prediction window, quirk Q12)
 
 
 def test_batch_of_sequences_in_one_launch(gpu):
@@ -128,6 +140,44 @@ def test_batch_of_sequences_in_one_launch(gpu):
     e_arr, slots, ptrs, caps, got = (C.c_void_p * 1)(enc), (C.c_int * 1)(0), (C.c_char_p * 1)(C.cast(bufs[0], C.c_char_p)), (C.c_long * 1)(len(bufs[0])), (C.c_long * 1)()
     assert lib.hmr_gpu_enc_encode_batch(e_arr, 1, slots, None, ptrs, caps, got) == -3
     lib.hmr_gpu_enc_destroy(enc)
+
+
+def test_batch_of_content_families_in_one_launch(gpu):
+    """hmr_gpu_enc_encode_batch with every content family of tools/gen_yuv.py in ONE launch (a thread per CTU row: the batch schedule; noise at QP 0 among them, the
+    largest sub-streams): every sequence's stream and reconstructed pictures must be its fixture's"""
+    lib = gpu
+    lib.hmr_gpu_enc_load_source.argtypes = [C.c_void_p, C.c_int] + [C.c_char_p] * 3
+    lib.hmr_gpu_enc_encode_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    cases = ["416x240_noise_wpp_rows", "416x240_extremes_wpp_rows", "416x240_flat_wpp_rows", "416x240_motion_wpp_rows", "416x240_chroma_wpp_rows", "384x192_noise_qp0_wpp_rows",
+             "416x240_chroma_force_intra_rdfull_tr4_wpp_rows", "416x240_extremes_force_intra_rdfull_tr4_wpp_rows"]
+    encs, ctxs, frames, itype = [], [], [], []
+    for case in cases:
+        g = GOLD[case]
+        keys = dict(g["keys"])
+        content, seed = keys.pop("content"), keys.pop("clip_seed", 1234)
+        itype.append(3 if keys.pop("force_intra", 0) else 0)
+        assert int(keys["wpp"]) == (g["height"] + 63) // 64 and int(keys.get("engines", 1)) == 1
+        ctx, enc = C.c_void_p(), C.c_void_p()
+        assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()
+        cfg = ec.default_cfg(g["width"], g["height"], **keys)
+        assert lib.hmr_gpu_enc_create(ctx, C.byref(cfg), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
+        for f, planes in enumerate(ec.clip_frames(g["width"], g["height"], g["frames"], None, seed, content)):
+            assert lib.hmr_gpu_enc_load_source(enc, f, *planes) == 0, lib.hmr_gpu_last_error()
+        encs.append(enc); ctxs.append(ctx); frames.append(g["frames"])
+    bufs = [C.create_string_buffer(1 << 20) for _ in cases]
+    out = [b"" for _ in cases]
+    for f in range(max(frames)):
+        live = [i for i in range(len(cases)) if f < frames[i]]
+        n = len(live)
+        got = (C.c_long * n)()
+        assert lib.hmr_gpu_enc_encode_batch((C.c_void_p * n)(*[encs[i] for i in live]), n, (C.c_int * n)(*([f] * n)), (C.c_int * n)(*[itype[i] for i in live]),
+                                            (C.c_char_p * n)(*[C.cast(bufs[i], C.c_char_p) for i in live]), (C.c_long * n)(*[len(bufs[i]) for i in live]), got) == 0, lib.hmr_gpu_last_error()
+        for k, i in enumerate(live):
+            out[i] += bufs[i].raw[:got[k]]
+    for i, case in enumerate(cases):
+        assert len(out[i]) == GOLD[case]["stream_bytes"] and hashlib.md5(out[i]).hexdigest() == GOLD[case]["stream_md5"], case
+        decoder_check.check(out[i], GOLD[case], case)      # (the decoded pictures are the reference's reconstruction: recon_md5)
+        lib.hmr_gpu_enc_destroy(encs[i])
 
 
 def test_batch_of_300_sequences_in_one_launch(gpu):

@@ -10,6 +10,7 @@ usage: tools/encoder_fuzz.py [--cases N] [--seed S] [--max-ctus M]        (print
        ... --gpu --batch K                                                  (K cases per hmr_gpu_enc_encode_batch call: one launch for all their CTU stages)
        ... --gpu --engines-only --chain-sets M                              (several engines through hmr_gpu_enc_encode_chain, M objects per engine)
        ... --threads-only / --extra-keys / --max-cols C --max-rows R        (several WPP threads only; also draw me= and cqo=; larger CTU grids)
+       ... --content noise,extremes,flat,motion,chroma (or all)             (the picture content of each case drawn from these tools/gen_yuv.py families)
 A case that differs and had evaluations on a stale prediction window (quirk Q12, include/homer_gpu.h: hmr_gpu_enc_stale_predictions) is marked; --tolerate-q12 keeps it out
 of the exit code.  Runs of the round: profiles/r04_encoder_fuzz.md."""
 import argparse
@@ -33,12 +34,18 @@ LAST_RECON = None
 STALE = 0      # evaluations on a stale prediction window (quirk Q12) in the case just encoded; -1: not counted
 
 
+def clip_frames(width, height, frames, cut_at, clip_seed, content):
+    """the planes of a case's clip as bytes (straight from tools/gen_yuv.py: this tool does not lean on the test helpers' signatures)"""
+    return [tuple(p.tobytes() for p in planes) for planes in gen_yuv.gen_frames(width, height, frames, seed=clip_seed, cut_at=cut_at, content=content)]
+
+
 def reference(width, height, frames, clip_seed, keys):
     keys = dict(keys)
     cut_at = keys.pop("cut_at", None)
+    content = keys.pop("content", "default")
     with tempfile.TemporaryDirectory() as tmp:
         yuv = os.path.join(tmp, "in.yuv")
-        gen_yuv.write_clip(yuv, width, height, frames, clip_seed, cut_at)
+        gen_yuv.write_clip(yuv, width, height, frames, clip_seed, cut_at, content)
         turnstile = int(keys.get("wpp", 1)) > 1 or int(keys.get("engines", 1)) > 1
         cmd = [os.path.join(ROOT, "oracle", "_ref", "ref_ctudump" if turnstile else "ref_lockstep"), yuv, os.path.join(tmp, "out.265"), str(width), str(height), str(frames)]
         cmd += [f"{k}={v}" for k, v in keys.items()]
@@ -79,6 +86,7 @@ def decoder_verdict(stream, recon, width, height, keys, stale):
 def checker(lib, width, height, frames, clip_seed, keys):
     keys = dict(keys)
     cut_at = keys.pop("cut_at", None)
+    content = keys.pop("content", "default")
     image_type = 3 if int(keys.pop("force_intra", 0)) else 0
     cfg = ec.default_cfg(width, height, **keys)
     enc = lib.henc_cpu_create(C.byref(cfg))
@@ -89,7 +97,7 @@ def checker(lib, width, height, frames, clip_seed, keys):
     units = []
     global STALE
     STALE = 0
-    for planes in ec.clip_frames(width, height, frames, cut_at, clip_seed):
+    for planes in clip_frames(width, height, frames, cut_at, clip_seed, content):
         n = lib.henc_cpu_encode_frame(enc, *planes, image_type, buf, len(buf), rec)
         assert n > 0
         units.append(buf.raw[:n])
@@ -101,6 +109,7 @@ def checker(lib, width, height, frames, clip_seed, keys):
 def device(lib, ctx, width, height, frames, clip_seed, keys):
     keys = dict(keys)
     cut_at = keys.pop("cut_at", None)
+    content = keys.pop("content", "default")
     image_type = 3 if int(keys.pop("force_intra", 0)) else 0
     cfg = ec.default_cfg(width, height, **keys)
     enc = C.c_void_p()
@@ -109,7 +118,7 @@ def device(lib, ctx, width, height, frames, clip_seed, keys):
     buf = C.create_string_buffer(8 << 20)
     nbytes = C.c_long()
     units = []
-    for planes in ec.clip_frames(width, height, frames, cut_at, clip_seed):
+    for planes in clip_frames(width, height, frames, cut_at, clip_seed, content):
         st = lib.hmr_gpu_enc_encode(enc, *planes, image_type, buf, len(buf), C.byref(nbytes), None)
         assert st in (1, 2), lib.hmr_gpu_last_error()
         units.append(buf.raw[:nbytes.value])
@@ -133,12 +142,13 @@ def device_batch(lib, group):
     for w, h, frames, clip_seed, keys in group:
         keys = dict(keys)
         cut_at = keys.pop("cut_at", None)
+        content = keys.pop("content", "default")
         types.append(3 if int(keys.pop("force_intra", 0)) else 0)
         cfg = ec.default_cfg(w, h, **keys)
         ctx, enc = C.c_void_p(), C.c_void_p()
         assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()
         assert (lib.hmr_gpu_enc_create_serial_pool if SERIAL_POOL else lib.hmr_gpu_enc_create)(ctx, C.byref(cfg), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
-        for f, planes in enumerate(ec.clip_frames(w, h, frames, cut_at, clip_seed)):
+        for f, planes in enumerate(clip_frames(w, h, frames, cut_at, clip_seed, content)):
             assert lib.hmr_gpu_enc_load_source(enc, f, *planes) == 0, lib.hmr_gpu_last_error()
         encs.append(enc); ctxs.append(ctx); nfr.append(frames)
     bufs = [C.create_string_buffer(8 << 20) for _ in group]
@@ -169,6 +179,7 @@ def device_chain(lib, w, h, frames, clip_seed, keys, sets):
     """a case with several engines through hmr_gpu_enc_encode_chain: the engine objects (and `sets` - 1 twins of each) encode chains of E x sets overlapping frames"""
     keys = dict(keys)
     cut_at = keys.pop("cut_at", None)
+    content = keys.pop("content", "default")
     if int(keys.pop("force_intra", 0)):
         return None
     E = int(keys["engines"])
@@ -194,7 +205,7 @@ def device_chain(lib, w, h, frames, clip_seed, keys, sets):
         k = ((f % chain) // E) * E + f % E
         obj_of[f], slot_of[f] = k, used[k]
         used[k] += 1
-    for f, planes in enumerate(ec.clip_frames(w, h, frames, cut_at, clip_seed)):
+    for f, planes in enumerate(clip_frames(w, h, frames, cut_at, clip_seed, content)):
         assert lib.hmr_gpu_enc_load_source(encs[obj_of[f]], slot_of[f], *planes) == 0, lib.hmr_gpu_last_error()
     bufs = [C.create_string_buffer(8 << 20) for _ in range(chain)]
     units = []
@@ -237,7 +248,7 @@ def load_checker():
     return lib
 
 
-def random_case(rng, max_ctus, gpu=False, max_cols=14, max_rows=9, threads_only=False, engines_only=False, extra_keys=False, combos=False):
+def random_case(rng, max_ctus, gpu=False, max_cols=14, max_rows=9, threads_only=False, engines_only=False, extra_keys=False, combos=False, contents=None):
     while True:
         wc, hc = rng.randint(2, max_cols), rng.randint(1, max_rows)
         if wc * hc > max_ctus:
@@ -315,7 +326,14 @@ def random_case(rng, max_ctus, gpu=False, max_cols=14, max_rows=9, threads_only=
         elif rng.random() < 0.12 and mode != "rc":         # a new scene inside the clip (the in-frame scene-change detection, hmr_motion_inter.c:3791)
             frames += rng.randint(2, 4)
             keys["cut_at"] = rng.randint(2, frames - 2)
-        return width, height, frames, rng.randint(1, 10 ** 6), keys
+        clip_seed = rng.randint(1, 10 ** 6)
+        if contents:        # (drawn last: without --content the cases of a seed are what they always were)
+            keys["content"] = rng.choice(contents)
+            if "bitrate" in keys:
+                # the reference's stream buffer follows the bit rate under rate control (max(intra_period, 50) frames' worth, hmr_encoder_lib.c:965) and is written
+                # without a bound check: a picture of noise that outgrows it makes the reference write past its allocation.  Keep 1.5 x a raw picture inside it.
+                keys["bitrate"] = max(keys["bitrate"], width * height * 9 // 1000 + 1)
+        return width, height, frames, clip_seed, keys
 
 
 def main():
@@ -337,6 +355,7 @@ def main():
     ap.add_argument("--serial-batch", action="store_true", help="with --gpu --batch N: only cases with one WPP thread and one engine, created with hmr_gpu_enc_create_serial_pool and encoded N per batch call "
                                                                 "(the reference's single-thread order as a batch schedule)")
     ap.add_argument("--decode", action="store_true", help="also decode the reference's stream with oracle/hevcdec and compare the pictures with the reference's own reconstruction")
+    ap.add_argument("--content", default=None, help="picture content drawn per case from these tools/gen_yuv.py families (comma-separated, or 'all'; default: the default clip only)")
     ap.add_argument("specs", nargs="*")
     a = ap.parse_args()
     global DECODE, SERIAL_POOL
@@ -365,10 +384,16 @@ def main():
         parts = spec.split(":")
         w, h, frames = (int(v) for v in parts[0].split("x"))
         keys = dict(kv.split("=") for kv in parts[2].split(",")) if len(parts) > 2 and parts[2] else {}
-        cases.append((w, h, frames, int(parts[1]) if len(parts) > 1 and parts[1] else 1234, {k: int(v) for k, v in keys.items()}))
+        cases.append((w, h, frames, int(parts[1]) if len(parts) > 1 and parts[1] else 1234, {k: v if k == "content" else int(v) for k, v in keys.items()}))
+    contents = None
+    if a.content:
+        contents = list(gen_yuv.CONTENTS) if a.content == "all" else a.content.split(",")
+        bad_names = [c for c in contents if c not in gen_yuv.CONTENTS]
+        if bad_names:
+            ap.error(f"--content: unknown {bad_names}, the families are {gen_yuv.CONTENTS}")
     if not cases:
         rng = random.Random(a.seed)
-        cases = [random_case(rng, a.max_ctus, a.gpu, a.max_cols, a.max_rows, a.threads_only, a.engines_only, a.extra_keys, a.combos) for _ in range(a.cases)]
+        cases = [random_case(rng, a.max_ctus, a.gpu, a.max_cols, a.max_rows, a.threads_only, a.engines_only, a.extra_keys, a.combos, contents) for _ in range(a.cases)]
     bad = q12_bad = 0
     batched = {}
     if a.gpu and a.batch > 1:       # groups of cases the batch call takes (one thread per CTU row or the in-between counts, one engine) share their launches
