@@ -20,6 +20,7 @@
 #define HENC_TU_OPERANDS_IN_LDS 1      // (enc_platform.h: the TU primitives' operands are in this kernel's LDS)
 #include <stddef.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <chrono>
 #include <mutex>
 #include <condition_variable>
@@ -33,8 +34,10 @@
 #include "enc/enc_sched.h"
 #include "enc/enc_host.h"
 #include "enc/enc_post.h"
+#include "ingest.h"
 
 using namespace henc;
+constexpr int INGEST_RING = 4;      // job tables of the device ingest in flight (k_encode_ingest.inc)
 
 // k_subpel.hip: the phase planes of a reference picture, queued on `stream` (all of them / one component's)
 int hmr_subpel_plane_on(hipStream_t stream, int comp, const int16_t *pic, int stride, int rows, uint8_t *out);
@@ -964,6 +967,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	}
 }
 
-// the host side: the encoder object and the per-frame entry points, then the calls that put several pictures into one launch
+// the host side: the encoder object and the per-frame entry points, then the calls that put several pictures into one launch, then pictures from device memory
 #include "k_encode_object.inc"
 #include "k_encode_batch.inc"
+#include "k_encode_ingest.inc"

@@ -147,6 +147,11 @@ struct hmr_gpu_enc {
 	int *d_pool_state = nullptr;                         // k_encode_pool: per picture of the launch the open step and the steps' ticket / done counters, then the finished-pictures counter
 	WorkSlow *d_pool_slow = nullptr;                     // the pool workers' transform / decoded windows
 	int pool_workers = 0;
+	// device ingest (k_encode_ingest.inc), on the first encoder of a load call: a ring of job tables in page-locked memory (a table is written again only when the
+	// launch that read it is known to be over: ev_jobs), their copy on the device, the events towards the producer's stream and the encoders' streams
+	IngestJob *h_jobs = nullptr, *d_jobs = nullptr;
+	int jobs_cap = 0, jobs_next = 0;
+	hipEvent_t ev_jobs[INGEST_RING] = {nullptr, nullptr, nullptr, nullptr}, ev_produced = nullptr, ev_ingested = nullptr;
 	EntropyState es;
 	// engines (enc_host.h): the persistent state of each engine this object runs - engine k = frames k, k + E, ... - swapped into d at set_frame
 	CtuInfo *d_ctus_eng[MAX_ENGINES] = {nullptr};
@@ -811,6 +816,11 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	if (e->d_gather) (void)hipFree(e->d_gather);
 	if (e->h_gather) (void)hipHostFree(e->h_gather);
 	if (e->h_offs) (void)hipHostFree(e->h_offs);
+	if (e->h_jobs) (void)hipHostFree(e->h_jobs);
+	if (e->d_jobs) (void)hipFree(e->d_jobs);
+	for (hipEvent_t ev : e->ev_jobs) if (ev) (void)hipEventDestroy(ev);
+	if (e->ev_produced) (void)hipEventDestroy(e->ev_produced);
+	if (e->ev_ingested) (void)hipEventDestroy(e->ev_ingested);
 	if (e->d_batch) (void)hipFree(e->d_batch);
 	if (e->d_pool_state) (void)hipFree(e->d_pool_state);
 	if (e->d_pool_slow) (void)hipFree(e->d_pool_slow);

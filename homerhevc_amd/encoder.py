@@ -1,0 +1,269 @@
+"""The frame encoder on torch tensors: pictures that are already on the GPU in, access units (Annex-B bytes) out.
+
+    cfg = EncoderConfig(1920, 1080, wfpp_num_threads=17)
+    enc = Encoder(cfg)
+    au, slice_type = enc.encode(frame)          # frame: a uint8 CUDA tensor [H * 3 // 2, W] (I420), or a tuple of plane tensors
+
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12 and 12d).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (csrc/k_ingest.hip), ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
+Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
+"""
+import ctypes as C
+
+from .build import LIB_PATH
+
+PIC_I420, PIC_NV12 = 0, 1
+SLICE_P, SLICE_I = 1, 2
+IMAGE_AUTO, IMAGE_I = 0, 3          # encoder_in_out_t.image_type
+
+
+class EncoderConfig(C.Structure):
+    """hmr_gpu_enc_cfg (the reference's HVENC_Cfg): EncoderConfig(width, height, **fields) with the header's field names as keywords.  Fields that are not given have the
+    values of BASELINE.json configs[1]; the VBV buffer follows the bit rate (vbv_size = bitrate, vbv_init = 35 % of it, as the reference's driver sets them) unless given."""
+    _fields_ = [("size", C.c_int32), ("profile", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("frame_rate", C.c_float), ("cu_size", C.c_int32),
+                ("max_pred_partition_depth", C.c_int32), ("max_intra_tr_depth", C.c_int32), ("max_inter_tr_depth", C.c_int32), ("intra_period", C.c_int32),
+                ("gop_size", C.c_int32), ("num_b", C.c_int32), ("num_ref_frames", C.c_int32), ("motion_estimation_precision", C.c_int32), ("qp", C.c_int32),
+                ("chroma_qp_offset", C.c_int32), ("num_enc_engines", C.c_int32), ("wfpp_enable", C.c_int32), ("wfpp_num_threads", C.c_int32),
+                ("sign_hiding", C.c_int32), ("sample_adaptive_offset", C.c_int32), ("bitrate_mode", C.c_int32), ("bitrate", C.c_int32), ("vbv_size", C.c_int32),
+                ("vbv_init", C.c_int32), ("reinit_gop_on_scene_change", C.c_int32), ("rd_mode", C.c_int32), ("performance_mode", C.c_int32)]
+    DEFAULTS = dict(profile=1, frame_rate=25.0, cu_size=64, max_pred_partition_depth=4, max_intra_tr_depth=2, max_inter_tr_depth=1, intra_period=100, gop_size=1, num_b=0,
+                    num_ref_frames=1, motion_estimation_precision=2, qp=32, chroma_qp_offset=2, num_enc_engines=1, wfpp_enable=1, wfpp_num_threads=1, sign_hiding=1,
+                    sample_adaptive_offset=1, bitrate_mode=0, bitrate=20000, reinit_gop_on_scene_change=1, rd_mode=2, performance_mode=2)
+
+    def __init__(self, width, height, **fields):
+        names = {f[0] for f in self._fields_}
+        unknown = sorted(set(fields) - names)
+        if unknown:
+            raise TypeError(f"EncoderConfig: no such field(s) {unknown}")
+        values = dict(self.DEFAULTS, size=C.sizeof(type(self)), width=int(width), height=int(height))
+        values.update(fields)
+        values.setdefault("vbv_size", int(values["bitrate"]))
+        values.setdefault("vbv_init", int(0.35 * int(values["bitrate"])))
+        super().__init__(**{k: (float(v) if k == "frame_rate" else int(v)) for k, v in values.items()})
+
+
+class Picture(C.Structure):
+    """hmr_gpu_picture"""
+    _fields_ = [("format", C.c_int32), ("reserved", C.c_int32), ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3)]
+
+
+_lib = None
+
+
+def load_library():
+    """libhomer_gpu.so with the argument types of the calls this module makes.  torch brings up its HIP runtime first where it finds a GPU."""
+    global _lib
+    if _lib is None:
+        try:
+            import torch
+            if torch.cuda.is_available():
+                torch.cuda.init()
+        except ImportError:
+            pass
+        lib = C.CDLL(LIB_PATH)
+        P, I, L = C.c_void_p, C.c_int, C.c_long
+        lib.hmr_gpu_last_error.restype = C.c_char_p
+        lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
+        lib.hmr_gpu_destroy.argtypes = [P]
+        lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(EncoderConfig), C.POINTER(P)]
+        lib.hmr_gpu_enc_destroy.argtypes = [P]
+        lib.hmr_gpu_picture_check.argtypes = [C.POINTER(Picture), I, I]
+        lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
+        lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
+        lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
+        batch = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
+        lib.hmr_gpu_enc_encode_batch.argtypes = batch
+        lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = batch
+        _lib = lib
+    return _lib
+
+
+def _fail(lib, what):
+    raise RuntimeError(f"{what}: {(lib.hmr_gpu_last_error() or b'').decode(errors='replace')}")
+
+
+def _plane(t, what):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+        raise TypeError(f"picture_of: {what} has to be a uint8 CUDA tensor")
+    return t
+
+
+def picture_of(frame, width, height):
+    """The descriptor (hmr_gpu_picture) of a width x height 4:2:0 picture held by uint8 CUDA tensors; nothing is copied, the tensors' strides become the pitches.
+      one tensor [height * 3 // 2, width], contiguous      I420: the luma rows, then the U plane, then the V plane (each width / 2 x height / 2, tightly packed)
+      (y, u, v): [height, width], 2 x [height / 2, width / 2]  I420 planes; any row stride, unit stride along a row (views into larger tensors are fine)
+      (y, uv): [height, width], [height / 2, width / 2, 2] or [height / 2, width]  NV12: uv holds the U, V pairs of a row next to each other
+    Returns (Picture, tensors): keep the tensors until the load call that takes the descriptor has returned."""
+    w, h = int(width), int(height)
+    pic = Picture(format=PIC_I420, reserved=0)
+    if not isinstance(frame, (tuple, list)):
+        t = _plane(frame, "the frame")
+        if tuple(t.shape) != (h * 3 // 2, w) or not t.is_contiguous():
+            raise ValueError(f"picture_of: a single tensor has to be contiguous [{h * 3 // 2}, {w}] (I420), got {tuple(t.shape)} with strides {t.stride()}")
+        base = t.data_ptr()
+        pic.plane[0], pic.plane[1], pic.plane[2] = base, base + w * h, base + w * h + (w // 2) * (h // 2)
+        pic.pitch[0], pic.pitch[1], pic.pitch[2] = w, w // 2, w // 2
+        return pic, (t,)
+    planes = [_plane(t, f"plane {i}") for i, t in enumerate(frame)]
+    if len(planes) == 2 and planes[1].dim() == 3:
+        uv = planes[1]
+        if tuple(uv.shape) != (h // 2, w // 2, 2) or uv.stride(2) != 1 or uv.stride(1) != 2:
+            raise ValueError(f"picture_of: the UV plane has to be [{h // 2}, {w // 2}, 2] with the pairs next to each other, got {tuple(uv.shape)} with strides {uv.stride()}")
+        planes[1] = uv.as_strided((h // 2, w), (uv.stride(0), 1))
+    if len(planes) not in (2, 3):
+        raise ValueError("picture_of: (y, u, v) for I420 or (y, uv) for NV12")
+    shapes = [(h, w), (h // 2, w)] if len(planes) == 2 else [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
+    pic.format = PIC_NV12 if len(planes) == 2 else PIC_I420
+    for c, (t, shape) in enumerate(zip(planes, shapes)):
+        if tuple(t.shape) != shape or t.stride(1) != 1:
+            raise ValueError(f"picture_of: plane {c} has to be {list(shape)} with unit stride along a row, got {tuple(t.shape)} with strides {t.stride()}")
+        pic.plane[c], pic.pitch[c] = t.data_ptr(), t.stride(0)
+    return pic, tuple(planes)
+
+
+def _stream_of(device):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _au_capacity(cfg):
+    return max(1 << 20, int(cfg.width) * int(cfg.height) * 2)
+
+
+class Encoder:
+    """One sequence: encode(frame) -> (access unit bytes, slice type).  The picture is read on the device, ordered behind what torch's current stream holds when encode is
+    called; work queued on that stream afterwards (writing the tensor again, the allocator reusing it) runs after the picture has been read."""
+
+    def __init__(self, cfg, device=0):
+        self.lib = lib = load_library()
+        self.cfg, self.device = cfg, int(device)
+        self.ctx, self.enc = C.c_void_p(), C.c_void_p()
+        if lib.hmr_gpu_create(C.byref(self.ctx), self.device, None) != 0:
+            self.ctx = C.c_void_p()
+            _fail(lib, "hmr_gpu_create")
+        if lib.hmr_gpu_enc_create(self.ctx, C.byref(cfg), C.byref(self.enc)) != 0:
+            self.enc = C.c_void_p()
+            err = (lib.hmr_gpu_last_error() or b"").decode(errors="replace")
+            self.close()
+            raise RuntimeError(f"hmr_gpu_enc_create: {err}")
+        self.buf = C.create_string_buffer(_au_capacity(cfg))
+        self.slot = 0
+
+    def encode(self, frame, image_type=IMAGE_AUTO):
+        """frame: what picture_of takes.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P / 2 for I)."""
+        lib = self.lib
+        pic, keep = picture_of(frame, self.cfg.width, self.cfg.height)
+        if lib.hmr_gpu_enc_load_source_device(self.enc, self.slot, C.byref(pic), _stream_of(self.device)) != 0:
+            _fail(lib, "hmr_gpu_enc_load_source_device")
+        n = C.c_long()
+        slice_type = lib.hmr_gpu_enc_encode_source(self.enc, self.slot, int(image_type), self.buf, len(self.buf), C.byref(n), None)
+        del keep
+        if slice_type < 0:
+            _fail(lib, "hmr_gpu_enc_encode_source")
+        self.slot ^= 1
+        return self.buf.raw[:n.value], slice_type
+
+    def close(self):
+        if self.enc:
+            self.lib.hmr_gpu_enc_destroy(self.enc)
+            self.enc = C.c_void_p()
+        if self.ctx:
+            self.lib.hmr_gpu_destroy(self.ctx)
+            self.ctx = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class BatchEncoder:
+    """Several sequences (configurations with wfpp_num_threads > 1: the batch schedule), one picture of each per step(): ONE ingest launch for all their pictures and ONE
+    launch for all their CTU stages.  Every sequence has a context - a stream - of its own.
+
+    step(frames): frames[i] is sequence i's next picture (what picture_of takes) or None when it has none this step.  Returns a list with one entry per sequence.
+    Not pipelined: entry i is the access unit of frames[i] (b"" for None).
+    Pipelined (the default): access units are delivered ONE STEP LATE, as by hmr_gpu_enc_encode_batch_pipelined - entry i is the access unit of the picture sequence i was
+    given in the previous step (b"" if it was given none), whose download and entropy coding ran beside this step's launch; flush() returns those of the last step.  When
+    the set of sequences that have a picture changes from one step to the next, the step flushes first; what it returns is the same."""
+
+    def __init__(self, cfgs, device=0, pipelined=True):
+        self.lib = lib = load_library()
+        self.device, self.pipelined = int(device), bool(pipelined)
+        self.cfgs, self.ctxs, self.encs, self.bufs = list(cfgs), [], [], []
+        try:
+            for cfg in self.cfgs:
+                ctx, enc = C.c_void_p(), C.c_void_p()
+                if lib.hmr_gpu_create(C.byref(ctx), self.device, None) != 0:
+                    _fail(lib, "hmr_gpu_create")
+                self.ctxs.append(ctx)
+                if lib.hmr_gpu_enc_create(ctx, C.byref(cfg), C.byref(enc)) != 0:
+                    _fail(lib, "hmr_gpu_enc_create")
+                self.encs.append(enc)
+                self.bufs.append(C.create_string_buffer(_au_capacity(cfg)))
+        except Exception:
+            self.close()
+            raise
+        self.slot = 0
+        self.outstanding = None          # pipelined: the sequences of the step whose access units have not been delivered
+
+    def _call(self, live, slots, image_types):
+        n = len(live)
+        got = (C.c_long * n)()
+        call = self.lib.hmr_gpu_enc_encode_batch_pipelined if self.pipelined else self.lib.hmr_gpu_enc_encode_batch
+        rc = call((C.c_void_p * n)(*[self.encs[i] for i in live]), n, (C.c_int * n)(*slots) if slots is not None else None,
+                  (C.c_int * n)(*image_types) if image_types is not None else None, (C.c_char_p * n)(*[C.cast(self.bufs[i], C.c_char_p) for i in live]),
+                  (C.c_long * n)(*[len(self.bufs[i]) for i in live]), got)
+        if rc != 0:
+            _fail(self.lib, "hmr_gpu_enc_encode_batch_pipelined" if self.pipelined else "hmr_gpu_enc_encode_batch")
+        return {i: C.string_at(self.bufs[i], got[k]) for k, i in enumerate(live)}
+
+    def step(self, frames, image_types=None):
+        if len(frames) != len(self.encs):
+            raise ValueError(f"BatchEncoder.step: {len(self.encs)} sequences, {len(frames)} frames")
+        live = [i for i, f in enumerate(frames) if f is not None]
+        out = {}
+        if self.outstanding is not None and self.outstanding != live:
+            out.update(self.flush_dict())
+        if live:
+            n = len(live)
+            pics, keep = (Picture * n)(), []
+            for k, i in enumerate(live):
+                pics[k], t = picture_of(frames[i], self.cfgs[i].width, self.cfgs[i].height)
+                keep.append(t)
+            slots = [self.slot] * n
+            if self.lib.hmr_gpu_enc_load_sources_device((C.c_void_p * n)(*[self.encs[i] for i in live]), n, (C.c_int * n)(*slots), pics, _stream_of(self.device)) != 0:
+                _fail(self.lib, "hmr_gpu_enc_load_sources_device")
+            for i, au in self._call(live, slots, [int(image_types[i]) for i in live] if image_types is not None else None).items():
+                out[i] = out.get(i, b"") + au      # (behind a flush the call itself delivers nothing)
+            del keep
+            self.slot ^= 1
+            if self.pipelined:
+                self.outstanding = live
+        return [out.get(i, b"") for i in range(len(self.encs))]
+
+    def flush_dict(self):
+        if self.outstanding is None:
+            return {}
+        live, self.outstanding = self.outstanding, None
+        return self._call(live, None, None)
+
+    def flush(self):
+        """pipelined: the access units still outstanding, one entry per sequence (b"" where there is none)"""
+        out = self.flush_dict()
+        return [out.get(i, b"") for i in range(len(self.encs))]
+
+    def close(self):
+        for enc in self.encs:
+            self.lib.hmr_gpu_enc_destroy(enc)
+        for ctx in self.ctxs:
+            self.lib.hmr_gpu_destroy(ctx)
+        self.encs, self.ctxs = [], []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

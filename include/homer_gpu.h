@@ -694,6 +694,40 @@ int hmr_gpu_enc_export_references8(hmr_gpu_enc **encs, int n, uint8_t *dev_rows,
 int hmr_gpu_enc_import_references8(hmr_gpu_enc **encs, int n, const uint8_t *dev_rows, long pitch, const void *states);
 
 /* ------------------------------------------------------------------------------------------------
+ * 12d. Pictures in device memory (no counterpart in the reference, whose pictures arrive in host memory)
+ *     A decoder, a renderer or a tensor library leaves its pictures on the GPU.  hmr_gpu_enc_load_sources_device converts n of them (1 .. 512) into picture slots of
+ *     their encoders with ONE launch of a bandwidth-bound kernel (k_ingest.hip) and no host synchronisation; the slots are what hmr_gpu_enc_load_source makes of the
+ *     same samples, so every encode call of section 12 takes them.  8-bit 4:2:0 as I420 (three planes) or NV12 (luma plane, plane of interleaved U, V pairs); any base
+ *     address, every plane with a byte pitch of its own (at least a row's bytes: width for luma and for NV12's pairs, width / 2 for I420 chroma).  Only the bytes of the
+ *     rows are read - [plane + y * pitch, plane + y * pitch + row bytes) - so the last row may end with the caller's allocation.
+ *     producer_stream is the hipStream_t (NULL: the null stream, treated like any other) on which the caller's work that WRITES the pictures is queued, e.g. torch's
+ *     current stream.  The library records an event on it and the ingest waits for that event; behind the ingest it records an event of its own and lets
+ *     producer_stream wait for it.  So the pictures need not be finished when the call is made, and whatever the caller queues on producer_stream after the call
+ *     returns - overwriting the pictures, an allocator handing their memory on - runs after the library has read them.  The host waits for nothing in either direction
+ *     (a slot that does not exist yet is allocated first, which synchronises the encoder's stream once, as hmr_gpu_enc_load_source does).
+ *     Towards the encode calls: the ingest runs on the first encoder's stream and the streams of all the call's encoders are made to wait for it, so a following
+ *     hmr_gpu_enc_encode_source, _encode_batch, _encode_batch_pipelined or _encode_chain of any of them sees the pictures, again without the host waiting.  Loading a slot
+ *     that an earlier encode call used is ORDERED behind that call, never refused: every encode call of section 12 - the pipelined one too, of which only the download and
+ *     the coding of the access units stay outstanding - returns after its launch has read the source pictures for the last time.  (As everywhere in this interface, calls
+ *     on one encoder are made from one host thread at a time.)
+ *     Refused with HMR_GPU_ERR_ARG before anything is queued: n outside 1 .. 512, a NULL encoder, a slot outside 0 .. 4096, encoders on different devices, the same
+ *     (encoder, slot) twice in a call, a descriptor hmr_gpu_picture_check refuses for the encoder's picture size, a plane pointer that hipPointerGetAttributes does not
+ *     report as device memory of the encoders' device.
+ * ------------------------------------------------------------------------------------------------ */
+enum { HMR_GPU_PIC_I420 = 0, HMR_GPU_PIC_NV12 = 1 };
+typedef struct hmr_gpu_picture {
+	int32_t format, reserved;      /* HMR_GPU_PIC_*; 0 */
+	const uint8_t *plane[3];       /* device pointers; NV12: plane[1] = UV pairs, plane[2] = NULL */
+	int64_t pitch[3];              /* bytes from row to row */
+} hmr_gpu_picture;
+/* pure host check of a descriptor against a picture size: no device, no context.  HMR_GPU_OK, or HMR_GPU_ERR_ARG with the field named by hmr_gpu_last_error: NULL
+ * descriptor, unknown format, non-zero reserved, odd or non-positive width / height, a missing plane pointer, plane[2] given with NV12, a negative pitch, a pitch
+ * smaller than a row's bytes. */
+int hmr_gpu_picture_check(const hmr_gpu_picture *pic, int width, int height);
+int hmr_gpu_enc_load_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_picture *pic, void *producer_stream);
+int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *pics, void *producer_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
  *     Replaces the per-block interpolation calls of the motion search and of motion compensation - the sixteen planes of
  *     hmr_half_pixel_estimation_luma_hm / hmr_quarter_pixel_estimation_luma_hm (hmr_motion_inter.c:395,442) and
