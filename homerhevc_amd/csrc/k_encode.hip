@@ -35,6 +35,7 @@
 #include "enc/enc_host.h"
 #include "enc/enc_post.h"
 #include "ingest.h"
+#include "egress.h"
 
 using namespace henc;
 constexpr int INGEST_RING = 4;      // job tables of the device ingest in flight (k_encode_ingest.inc)
@@ -971,3 +972,4 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 #include "k_encode_object.inc"
 #include "k_encode_batch.inc"
 #include "k_encode_ingest.inc"
+#include "k_encode_egress.inc"

@@ -100,6 +100,7 @@ int batch_launch(hmr_gpu_enc **encs, int n, const int *slots, const int *image_t
 	for (int i = 0; i < n; i++) {
 		hmr_gpu_enc *e = encs[i];
 		if ((rc = set_frame(e, slots[i], image_types ? image_types[i] : 0, -1.0, false))) return rc;
+		e->pic_stream = bst;
 		HIP_TRY(hipEventRecord(e->ev_ready, e->ctx->stream));
 		if (i) HIP_TRY(hipStreamWaitEvent(bst, e->ev_ready, 0));
 		lead->h_frames[i] = e->f;
@@ -375,12 +376,13 @@ extern "C" int hmr_gpu_enc_encode_chain(hmr_gpu_enc **encs, int n, hmr_gpu_enc *
 	const HostState start_state = st;
 	// A call that is refused while the frames are being set up leaves every object as it found it: set_frame moves an object on to its next picture buffer and frame
 	// state before the checks of the LATER frames of the chain run (wrong engine, a P frame without the object before it, an I frame inside the chain).
-	struct Undo { hmr_gpu_enc *e; int cur; HostState st; FrameCtx f; PlaneSet planes, planes2; EncDev d; };
+	struct Undo { hmr_gpu_enc *e; int cur; HostState st; FrameCtx f; PlaneSet planes, planes2; EncDev d; bool has_picture; hipStream_t pic_stream; };
 	std::vector<Undo> undo;
 	auto refuse = [&](int code) {
 		for (size_t k = undo.size(); k-- > 0;) {
 			Undo &u = undo[k];
 			u.e->cur = u.cur; u.e->st = u.st; u.e->f = u.f; u.e->chain_planes = u.planes; u.e->chain_planes2 = u.planes2; u.e->d = u.d;
+			u.e->has_picture = u.has_picture; u.e->pic_stream = u.pic_stream;
 		}
 		return code;
 	};
@@ -401,7 +403,7 @@ extern "C" int hmr_gpu_enc_encode_chain(hmr_gpu_enc **encs, int n, hmr_gpu_enc *
 			HIP_TRY(hipMalloc((void **)&p.c[1], p.bytes_c));
 			ps = p;
 		}
-		undo.push_back(Undo{e, e->cur, e->st, e->f, e->chain_planes, e->chain_planes2, e->d});
+		undo.push_back(Undo{e, e->cur, e->st, e->f, e->chain_planes, e->chain_planes2, e->d, e->has_picture, e->pic_stream});
 		e->st = st;
 		// what the frame predicts from, taken before the object that holds it (prev may be the chain's last object) moves on to its own next frame
 		const hmr_gpu_enc *r = j ? encs[j - 1] : prev;
@@ -414,6 +416,7 @@ extern "C" int hmr_gpu_enc_encode_chain(hmr_gpu_enc **encs, int n, hmr_gpu_enc *
 		std::swap(e->chain_planes, e->chain_planes2);      // (an object writes its two sets in turn: prev - often the chain's last object - keeps the set the chain's first frame reads)
 		if (j == 0 && e == prev) ref_set = e->chain_planes2;       // (a one-engine sequence: the object predicts from its own last picture)
 		if ((rc = set_frame(e, slots[j], image_types ? image_types[j] : 0, -1.0, false, true))) return refuse(rc);
+		e->pic_stream = bst;
 		st = e->st;
 		st.num_encoded_frames++;                       // (what end_frame will do; the distortion average it will store is not read inside the chain)
 		if (e->f.slice_type != SLICE_I) {

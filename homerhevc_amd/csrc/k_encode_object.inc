@@ -152,6 +152,15 @@ struct hmr_gpu_enc {
 	IngestJob *h_jobs = nullptr, *d_jobs = nullptr;
 	int jobs_cap = 0, jobs_next = 0;
 	hipEvent_t ev_jobs[INGEST_RING] = {nullptr, nullptr, nullptr, nullptr}, ev_produced = nullptr, ev_ingested = nullptr;
+	// device egress (k_encode_egress.inc).  Every encoder: whether d_pic[cur] holds an encoded frame's final picture, the stream whose work wrote it (its own, or the
+	// lead's of a batch or chain launch), events for that stream and its own.  The first encoder of an export call: the job tables as for the ingest, the events
+	// towards the consumer's stream
+	bool has_picture = false;
+	hipStream_t pic_stream = nullptr;
+	hipEvent_t ev_pic_done = nullptr, ev_own_done = nullptr;
+	EgressJob *h_ejobs = nullptr, *d_ejobs = nullptr;
+	int ejobs_cap = 0, ejobs_next = 0;
+	hipEvent_t ev_ejobs[INGEST_RING] = {nullptr, nullptr, nullptr, nullptr}, ev_consumer = nullptr, ev_egressed = nullptr;
 	EntropyState es;
 	// engines (enc_host.h): the persistent state of each engine this object runs - engine k = frames k, k + E, ... - swapped into d at set_frame
 	CtuInfo *d_ctus_eng[MAX_ENGINES] = {nullptr};
@@ -380,6 +389,8 @@ int set_frame(hmr_gpu_enc *e, int slot, int image_type, double avg_dist, bool up
 {
 	const Seq &s = e->seq;
 	e->cur ^= 1;
+	e->has_picture = true;
+	e->pic_stream = e->ctx->stream;      // (a batch or chain launch names its lead's stream after this)
 	{
 		const int k = e->local_engines > 1 ? e->st.num_encoded_frames % e->local_engines : 0;
 		e->d.ctus = e->d_ctus_eng[k];
@@ -500,7 +511,7 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 	e->st.engines = clampi(e->cfg.num_enc_engines, 1, MAX_ENGINES);
 	e->engine_index = engine_index;
 	e->local_engines = engine_index >= 0 ? 1 : e->st.engines;
-	if (e->st.engines > 1 && e->cfg.wfpp_num_threads < 2) {
+	if (e->st.engines > 1 && e->cfg.wfpp_num_threads < 2 && engine_index >= 0) {
 		hmr_set_error("hmr_gpu_enc_create: configuration outside the built rows: num_enc_engines > 1 needs the row-per-thread schedule (wfpp_num_threads > 1)");
 		delete e;
 		return HMR_GPU_ERR_ARG;
@@ -516,8 +527,9 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 	e->seq.wide_min_n = 0;
 	// One WPP thread: the single thread's order by guesses, verification and re-encode passes (k_encode_ctus) - except under rate control and RD_FULL, whose decisions
 	// read the entropy coder's progress and states behind FINAL decisions (hmr_rate_control.c:266-282, hmr_arithmetic_encoding.c:2139): there the pool runs the
-	// picture one CTU at a time in raster order (EncDev::raster), the post-decision tasks beside it on the launch's other workers.
-	e->raster = e->cfg.wfpp_num_threads <= 1 && (e->cfg.bitrate_mode != 0 || e->seq.rd_mode == RDM_FULL || g_serial_pool);
+	// picture one CTU at a time in raster order (EncDev::raster), the post-decision tasks beside it on the launch's other workers.  Several engines in one object take that
+	// schedule too (the engines' persistent state is swapped by set_frame, which the pool's launch follows); an object that is ONE engine needs wfpp_num_threads > 1 (above).
+	e->raster = e->cfg.wfpp_num_threads <= 1 && (e->cfg.bitrate_mode != 0 || e->seq.rd_mode == RDM_FULL || g_serial_pool || e->st.engines > 1);
 	e->lockstep = e->cfg.wfpp_num_threads > 1 || e->raster;
 	const Seq &s = e->seq;
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -821,6 +833,10 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	for (hipEvent_t ev : e->ev_jobs) if (ev) (void)hipEventDestroy(ev);
 	if (e->ev_produced) (void)hipEventDestroy(e->ev_produced);
 	if (e->ev_ingested) (void)hipEventDestroy(e->ev_ingested);
+	if (e->h_ejobs) (void)hipHostFree(e->h_ejobs);
+	if (e->d_ejobs) (void)hipFree(e->d_ejobs);
+	for (hipEvent_t ev : {e->ev_ejobs[0], e->ev_ejobs[1], e->ev_ejobs[2], e->ev_ejobs[3], e->ev_consumer, e->ev_egressed, e->ev_pic_done, e->ev_own_done})
+		if (ev) (void)hipEventDestroy(ev);
 	if (e->d_batch) (void)hipFree(e->d_batch);
 	if (e->d_pool_state) (void)hipFree(e->d_pool_state);
 	if (e->d_pool_slow) (void)hipFree(e->d_pool_slow);

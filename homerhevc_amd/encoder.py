@@ -4,8 +4,12 @@
     enc = Encoder(cfg)
     au, slice_type = enc.encode(frame)          # frame: a uint8 CUDA tensor [H * 3 // 2, W] (I420), or a tuple of plane tensors
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12 and 12d).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (csrc/k_ingest.hip), ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
+    rec, ssd = enc.export(ssd=True)             # the reconstructed picture as a uint8 CUDA tensor, the sums of squared differences to `frame` as int64 [3]
+    y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
+
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d and 12e).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (csrc/k_ingest.hip) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (csrc/k_egress.hip), both
+ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
 import ctypes as C
@@ -48,6 +52,25 @@ class Picture(C.Structure):
 
 
 _lib = None
+_host_lib = None
+
+
+def psnr(ssd, width, height):
+    """homer_psnr's three values (Y, U, V, in dB; 99.99 for a zero sum) of three sums of squared differences - Python ints, e.g. export(ssd=True)[1].tolist() - of a
+    width x height 4:2:0 picture, through hmr_gpu_psnr.  Pure host arithmetic: needs neither torch nor a GPU."""
+    global _host_lib
+    if _host_lib is None:
+        lib = _lib or C.CDLL(LIB_PATH)
+        lib.hmr_gpu_last_error.restype = C.c_char_p
+        lib.hmr_gpu_psnr.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+        _host_lib = lib
+    sums = [int(v) for v in ssd]
+    if len(sums) != 3 or min(sums) < 0:
+        raise ValueError(f"psnr: three non-negative sums, got {sums}")
+    out = (C.c_double * 3)()
+    if _host_lib.hmr_gpu_psnr((C.c_uint64 * 3)(*sums), int(width), int(height), out) != 0:
+        raise ValueError((_host_lib.hmr_gpu_last_error() or b"hmr_gpu_psnr").decode(errors="replace"))
+    return tuple(out)
 
 
 def load_library():
@@ -71,6 +94,7 @@ def load_library():
         lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
         lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
+        lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
         batch = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
         lib.hmr_gpu_enc_encode_batch.argtypes = batch
         lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = batch
@@ -127,6 +151,39 @@ def _stream_of(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _output(cfg, out, nv12, device):
+    """the tensor(s) an export writes: `out` (what picture_of takes), or a new I420 tensor / NV12 pair"""
+    import torch
+    if out is not None:
+        return out
+    w, h = int(cfg.width), int(cfg.height)
+    if nv12:
+        return (torch.empty((h, w), dtype=torch.uint8, device=f"cuda:{device}"), torch.empty((h // 2, w // 2, 2), dtype=torch.uint8, device=f"cuda:{device}"))
+    return torch.empty((h * 3 // 2, w), dtype=torch.uint8, device=f"cuda:{device}")
+
+
+def _export(lib, device, encs, cfgs, slot, picture, ssd, outs, nv12):
+    """ONE hmr_gpu_enc_export_pictures_device for the encoders `encs`: (their pictures or None, an int64 tensor [len(encs), 3] or None)"""
+    import torch
+    n = len(encs)
+    if not picture and not ssd:
+        raise ValueError("export: neither the picture nor the sums asked for")
+    pics, results, keep = None, None, []
+    if picture:
+        pics, results = (Picture * n)(), []
+        for k, cfg in enumerate(cfgs):
+            target = _output(cfg, outs[k] if outs is not None else None, nv12, device)
+            pics[k], t = picture_of(target, cfg.width, cfg.height)
+            keep.append(t)
+            results.append(target)
+    sums = torch.empty((n, 3), dtype=torch.int64, device=f"cuda:{device}") if ssd else None
+    if lib.hmr_gpu_enc_export_pictures_device((C.c_void_p * n)(*encs), n, pics, (C.c_int * n)(*([slot] * n)) if ssd else None,
+                                              C.c_void_p(sums.data_ptr()) if ssd else None, _stream_of(device)) != 0:
+        _fail(lib, "hmr_gpu_enc_export_pictures_device")
+    del keep
+    return results, sums
+
+
 def _au_capacity(cfg):
     return max(1 << 20, int(cfg.width) * int(cfg.height) * 2)
 
@@ -149,6 +206,7 @@ class Encoder:
             raise RuntimeError(f"hmr_gpu_enc_create: {err}")
         self.buf = C.create_string_buffer(_au_capacity(cfg))
         self.slot = 0
+        self.slot_used = None            # the slot of the last encoded frame (export)
 
     def encode(self, frame, image_type=IMAGE_AUTO):
         """frame: what picture_of takes.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P / 2 for I)."""
@@ -161,8 +219,20 @@ class Encoder:
         del keep
         if slice_type < 0:
             _fail(lib, "hmr_gpu_enc_encode_source")
+        self.slot_used = self.slot
         self.slot ^= 1
         return self.buf.raw[:n.value], slice_type
+
+    def export(self, picture=True, ssd=False, out=None, nv12=False):
+        """The reconstructed picture of the frame the last encode() encoded (the final picture: after deblocking and SAO, what a decoder makes of the access unit) and / or
+        the three exact sums of squared differences between it and the picture that frame was encoded from.  Returns (picture, ssd); whichever was not asked for is None.
+        picture: `out` written in place (anything picture_of takes: views into larger tensors are fine, only the rows' bytes are written), else a new contiguous uint8
+        tensor [H * 3 // 2, W] (I420), with nv12=True a (y, uv) pair [H, W], [H / 2, W / 2, 2].  ssd: an int64 CUDA tensor [3] (Y, U, V); psnr(ssd.tolist(), W, H) gives dB.
+        One launch of the egress kernel, ordered on torch's current stream: what is queued there afterwards sees the results, nothing waits on the host."""
+        if self.slot_used is None:
+            raise RuntimeError("Encoder.export: nothing has been encoded yet")
+        pics, sums = _export(self.lib, self.device, [self.enc], [self.cfg], self.slot_used, picture, ssd, [out] if out is not None else None, nv12)
+        return (pics[0] if pics else None), (sums[0] if sums is not None else None)
 
     def close(self):
         if self.enc:
@@ -187,7 +257,10 @@ class BatchEncoder:
     Not pipelined: entry i is the access unit of frames[i] (b"" for None).
     Pipelined (the default): access units are delivered ONE STEP LATE, as by hmr_gpu_enc_encode_batch_pipelined - entry i is the access unit of the picture sequence i was
     given in the previous step (b"" if it was given none), whose download and entropy coding ran beside this step's launch; flush() returns those of the last step.  When
-    the set of sequences that have a picture changes from one step to the next, the step flushes first; what it returns is the same."""
+    the set of sequences that have a picture changes from one step to the next, the step flushes first; what it returns is the same.
+
+    export(): the reconstructed pictures and quality sums of the frames given to the LAST step, ONE launch for all of them.  In pipelined mode that step returned the
+    access units of the step BEFORE: the pictures are one step ahead of the access units (a frame's picture exists when its launch has run, its access unit a call later)."""
 
     def __init__(self, cfgs, device=0, pipelined=True):
         self.lib = lib = load_library()
@@ -208,6 +281,7 @@ class BatchEncoder:
             raise
         self.slot = 0
         self.outstanding = None          # pipelined: the sequences of the step whose access units have not been delivered
+        self.last_live, self.slot_used = [], None      # the sequences of the last step that had a picture, and the slot they were encoded from (export)
 
     def _call(self, live, slots, image_types):
         n = len(live)
@@ -239,10 +313,33 @@ class BatchEncoder:
             for i, au in self._call(live, slots, [int(image_types[i]) for i in live] if image_types is not None else None).items():
                 out[i] = out.get(i, b"") + au      # (behind a flush the call itself delivers nothing)
             del keep
+            self.last_live, self.slot_used = live, self.slot
             self.slot ^= 1
             if self.pipelined:
                 self.outstanding = live
         return [out.get(i, b"") for i in range(len(self.encs))]
+
+    def export(self, picture=True, ssd=False, out=None, nv12=False):
+        """As Encoder.export, for every sequence that was given a picture in the last step(), with ONE launch.  Returns (pictures, ssd): a list with one entry per
+        sequence (None for a sequence without a picture in that step; `out`, when given, is such a list too and its entries are written in place) or None, and an int64
+        CUDA tensor [sequences, 3] whose rows of idle sequences are -1, or None."""
+        import torch
+        live = self.last_live
+        if not live:
+            raise RuntimeError("BatchEncoder.export: the last step encoded nothing")
+        if out is not None and len(out) != len(self.encs):
+            raise ValueError(f"BatchEncoder.export: {len(self.encs)} sequences, {len(out)} outputs")
+        pics, sums = _export(self.lib, self.device, [self.encs[i] for i in live], [self.cfgs[i] for i in live], self.slot_used, picture, ssd,
+                             [out[i] for i in live] if out is not None else None, nv12)
+        pictures, table = None, None
+        if pics is not None:
+            pictures = [None] * len(self.encs)
+            for k, i in enumerate(live):
+                pictures[i] = pics[k]
+        if sums is not None:
+            table = torch.full((len(self.encs), 3), -1, dtype=torch.int64, device=sums.device)
+            table[torch.tensor(live, device=sums.device)] = sums
+        return pictures, table
 
     def flush_dict(self):
         if self.outstanding is None:

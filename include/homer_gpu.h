@@ -654,7 +654,8 @@ int hmr_gpu_enc_timeline(hmr_gpu_enc *enc, unsigned long long *out);
 
 /* ------------------------------------------------------------------------------------------------
  * 12b. Engines: hvenc_enc_t.num_encoder_engines / encoder_engine_thread (hmr_encoder_lib.c:3043-3330; hmr_private.h:1232)
- *     hmr_gpu_enc_cfg.num_enc_engines = E > 1 (row-per-thread schedule only) gives the stream of the reference's frame pipeline in the
+ *     hmr_gpu_enc_cfg.num_enc_engines = E > 1 (row-per-thread schedule; with wfpp_num_threads = 1 only as ONE object that holds all engines, hmr_gpu_enc_create,
+ *     which then runs the picture CTU by CTU on the pool's raster schedule) gives the stream of the reference's frame pipeline in the
  *     interleaving oracle/ref_ctudump.c's engine turnstile pins on it: frame n is encoded on the complete reconstruction of frame
  *     n - 1, starts from the avg_dist frame n - E left behind and works on the persistent state of engine n mod E.
  *     hmr_gpu_enc_create keeps all E engines in one object.  hmr_gpu_enc_create_engine makes ONE engine (index k of E): it is given
@@ -726,6 +727,40 @@ typedef struct hmr_gpu_picture {
 int hmr_gpu_picture_check(const hmr_gpu_picture *pic, int width, int height);
 int hmr_gpu_enc_load_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_picture *pic, void *producer_stream);
 int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *pics, void *producer_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 12e. Reconstructed pictures and their quality, left in device memory: homer_psnr (hmr_metics.c:53-105, called for every frame at hmr_encoder_lib.c:3350)
+ *     The mirror image of 12d.  hmr_gpu_enc_export_pictures_device hands the pictures of n encoders (1 .. 512) to the caller as 8-bit 4:2:0 in DEVICE memory and / or
+ *     leaves the exact sums of squared differences between each picture and a picture slot of its encoder in device memory, with ONE launch of a bandwidth-bound
+ *     kernel (k_egress.hip) and no host synchronisation.
+ *     "The picture" of an encoder is the final picture (after deblocking and SAO: what the next frame predicts from, what a decoder reconstructs) of the frame its last
+ *     encode call encoded: hmr_gpu_enc_encode, _encode_source, _encode_batch, _encode_batch_pipelined (the picture of the frames launched by THAT call - the access
+ *     unit arrives a call later, the picture does not; an encoder with an access unit outstanding is accepted here) and _encode_chain (every object of the chain holds
+ *     its own frame's picture, twins included).  An encoder that has not encoded anything yet is refused.
+ *     pics (or NULL: no pictures): n descriptors of OUTPUT pictures - hmr_gpu_picture as in 12d, but the call WRITES through the plane pointers (the const of the type
+ *     describes the ingest).  I420 or NV12, any base address, every plane with a byte pitch of its own, at least a row's bytes.  Only the bytes of the rows are written
+ *     - [plane + y * pitch, plane + y * pitch + row bytes) - so the picture may be a view into something larger and its last row may end with the caller's allocation.
+ *     slots (or NULL: no sums) with dev_ssd (device memory, n x 3 values; NULL exactly when slots is NULL): dev_ssd[3 * i + c] = the sum over the width x height
+ *     (chroma: width / 2 x height / 2) samples of (slot picture - final picture)^2 of plane c, exact, against whatever picture slot slots[i] of encs[i] holds when the
+ *     launch runs.  Normally that is the slot the frame was encoded from, and then the caller must not have loaded another picture into it in between; any loaded slot
+ *     is legal and gives the distance to that picture.  A sum does not fit 32 bits (255^2 x 3840 x 2160 = 5.4e11).  hmr_gpu_psnr turns three sums into homer_psnr's
+ *     three values: 10 * log10(255 * 255 * samples / sum) in double, the chroma planes with (width / 2) * (height / 2) samples, and 99.99 where the sum is 0.  It is pure
+ *     host code: no device, no context.
+ *     consumer_stream is the hipStream_t (NULL: the null stream) on which the caller's work that uses the output memory and dev_ssd is queued, e.g. torch's current
+ *     stream.  The library records an event on it and the egress waits for that event (the consumer may still be using the memory); the egress is also queued behind
+ *     whatever the encoders' streams hold (the launch that writes the picture, a load into the slot).  Behind the egress the library records an event that
+ *     consumer_stream and the streams of all the call's encoders wait for: what the caller queues on consumer_stream after the call sees the pictures and the sums, a
+ *     later encode call (which rewrites the final picture two frames on) and a later load into the slot run after the egress has read them.  The host waits for
+ *     nothing in either direction.
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is queued, every encoder left working: n outside 1 .. 512, a NULL encoder, encoders
+ *     on different devices, both pics and slots NULL, slots without dev_ssd or the reverse, a slot that does not exist, an encoder without an encoded picture, a
+ *     descriptor hmr_gpu_picture_check refuses for the encoder's picture size, an output plane or dev_ssd that hipPointerGetAttributes does not report as device memory
+ *     of the encoders' device.  hmr_gpu_psnr: NULL arguments, an odd or non-positive width or height.
+ * ------------------------------------------------------------------------------------------------ */
+int hmr_gpu_enc_export_pictures_device(hmr_gpu_enc **encs, int n, const hmr_gpu_picture *pics, const int *slots, uint64_t *dev_ssd, void *consumer_stream);
+/* one encoder; slot -1: no sums (dev_ssd NULL) */
+int hmr_gpu_enc_export_picture_device(hmr_gpu_enc *enc, const hmr_gpu_picture *pic, int slot, uint64_t *dev_ssd, void *consumer_stream);
+int hmr_gpu_psnr(const uint64_t ssd[3], int width, int height, double psnr[3]);
 
 /* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
