@@ -34,11 +34,9 @@
 #include "enc/enc_sched.h"
 #include "enc/enc_host.h"
 #include "enc/enc_post.h"
-#include "ingest.h"
-#include "egress.h"
+#include "picture_io.h"
 
 using namespace henc;
-constexpr int INGEST_RING = 4;      // job tables of the device ingest in flight (k_encode_ingest.inc)
 
 // k_subpel.hip: the phase planes of a reference picture, queued on `stream` (all of them / one component's)
 int hmr_subpel_plane_on(hipStream_t stream, int comp, const int16_t *pic, int stride, int rows, uint8_t *out);
@@ -925,18 +923,6 @@ __global__ __launch_bounds__(64) void k_sched_finish(EncDev d)
 	}
 }
 
-// host 8-bit planes -> int16 device planes (sse_copy_8_16 at frame entry, hmr_encoder_lib.c:295-305)
-__global__ void k_widen_plane(const uint8_t *src, int w, int h, int16_t *dst, int stride)
-{
-	const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-	if (x < w && y < h) dst[(size_t)y * stride + x] = src[(size_t)y * w + x];
-}
-__global__ void k_narrow_plane(const int16_t *src, int stride, int w, int h, uint8_t *dst)
-{
-	const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-	if (x < w && y < h) dst[(size_t)y * w + x] = (uint8_t)src[(size_t)y * stride + x];
-}
-
 struct SrcSlot {
 	int16_t *p[3];
 };
@@ -968,8 +954,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	}
 }
 
-// the host side: the encoder object and the per-frame entry points, then the calls that put several pictures into one launch, then pictures from device memory
+// the host side: the encoder object and the per-frame entry points, then the calls that put several pictures into one launch, then pictures from and to device memory
 #include "k_encode_object.inc"
 #include "k_encode_batch.inc"
-#include "k_encode_ingest.inc"
-#include "k_encode_egress.inc"
+#include "k_encode_picture_io.inc"

@@ -147,20 +147,15 @@ struct hmr_gpu_enc {
 	int *d_pool_state = nullptr;                         // k_encode_pool: per picture of the launch the open step and the steps' ticket / done counters, then the finished-pictures counter
 	WorkSlow *d_pool_slow = nullptr;                     // the pool workers' transform / decoded windows
 	int pool_workers = 0;
-	// device ingest (k_encode_ingest.inc), on the first encoder of a load call: a ring of job tables in page-locked memory (a table is written again only when the
-	// launch that read it is known to be over: ev_jobs), their copy on the device, the events towards the producer's stream and the encoders' streams
-	IngestJob *h_jobs = nullptr, *d_jobs = nullptr;
-	int jobs_cap = 0, jobs_next = 0;
-	hipEvent_t ev_jobs[INGEST_RING] = {nullptr, nullptr, nullptr, nullptr}, ev_produced = nullptr, ev_ingested = nullptr;
-	// device egress (k_encode_egress.inc).  Every encoder: whether d_pic[cur] holds an encoded frame's final picture, the stream whose work wrote it (its own, or the
-	// lead's of a batch or chain launch), events for that stream and its own.  The first encoder of an export call: the job tables as for the ingest, the events
-	// towards the consumer's stream
+	// picture conversion (picture_io.h, k_encode_picture_io.inc): the job tables and events of the k_ingest / k_egress launches this encoder leads - as the first
+	// encoder of a load / export call, and alone in the host-memory entries (widen_packed, narrow_packed)
+	JobRing<IngestJob> ingest;
+	JobRing<EgressJob> egress;
+	// every encoder: whether d_pic[cur] holds an encoded frame's final picture, the stream whose work wrote it (its own, or the lead's of a batch or chain launch),
+	// events for that stream and its own (an export call waits behind both)
 	bool has_picture = false;
 	hipStream_t pic_stream = nullptr;
 	hipEvent_t ev_pic_done = nullptr, ev_own_done = nullptr;
-	EgressJob *h_ejobs = nullptr, *d_ejobs = nullptr;
-	int ejobs_cap = 0, ejobs_next = 0;
-	hipEvent_t ev_ejobs[INGEST_RING] = {nullptr, nullptr, nullptr, nullptr}, ev_consumer = nullptr, ev_egressed = nullptr;
 	EntropyState es;
 	// engines (enc_host.h): the persistent state of each engine this object runs - engine k = frames k, k + E, ... - swapped into d at set_frame
 	CtuInfo *d_ctus_eng[MAX_ENGINES] = {nullptr};
@@ -201,18 +196,68 @@ int dev_alloc(T **p, size_t n, hipStream_t st)
 		if (rc_) return rc_;              \
 	} while (0)
 
-int load_planes(hmr_gpu_enc *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int16_t *const dst[3], int stride_y, int stride_c)
+// Jobs of k_ingest / k_egress (picture_io.h).  Ingest: the 8-bit picture `pic` of e's size into the int16 planes `dst` (at sample (0, 0)) with the given strides.
+// Egress: e's final picture into `pic` (NULL: no picture), the sums of its squared differences against the int16 planes `src` of a picture slot (NULL: none) into ssd.
+IngestJob ingest_job(const hmr_gpu_enc *e, const hmr_gpu_picture &pic, int16_t *const dst[3], int stride_y, int stride_c)
+{
+	IngestJob j;
+	for (int c = 0; c < 3; c++) {
+		j.src[c] = pic.plane[c];
+		j.pitch[c] = pic.pitch[c];
+		j.dst[c] = dst[c];
+	}
+	j.stride_y = stride_y; j.stride_c = stride_c;
+	j.width = e->seq.width; j.height = e->seq.height;
+	j.format = pic.format; j.reserved = 0;
+	return j;
+}
+EgressJob egress_job(hmr_gpu_enc *e, const hmr_gpu_picture *pic, int16_t *const src[3], uint64_t *ssd)
 {
 	const Seq &s = e->seq;
-	hipStream_t st = e->ctx->stream;
-	const uint8_t *in[3] = {y, u, v};
+	EgressJob j;
 	for (int c = 0; c < 3; c++) {
-		const int w = c ? s.width / 2 : s.width, h = c ? s.height / 2 : s.height;
-		HIP_TRY(hipMemcpyAsync(e->d_bytes, in[c], (size_t)w * h, hipMemcpyHostToDevice, st));
-		hipLaunchKernelGGL(k_widen_plane, dim3((w + 255) / 256, h), dim3(256), 0, st, e->d_bytes, w, h, dst[c], c ? stride_c : stride_y);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(st));   // d_bytes is reused by the next plane
+		j.rec[c] = plane0(e, e->cur, c);
+		j.src[c] = src ? src[c] : nullptr;
+		j.dst[c] = pic ? const_cast<uint8_t *>(pic->plane[c]) : nullptr;      // (as the output descriptor: the call writes through the plane pointers)
+		j.pitch[c] = pic ? pic->pitch[c] : 0;
 	}
+	j.ssd = ssd;
+	j.stride_y = s.stride_y; j.stride_c = s.stride_c;
+	j.src_stride_y = s.src_stride_y; j.src_stride_c = s.src_stride_c;
+	j.width = s.width; j.height = s.height;
+	j.format = pic ? pic->format : HMR_GPU_PIC_I420; j.reserved = 0;
+	return j;
+}
+// a tightly packed I420 picture of e's size at `bytes` (luma pitch width, chroma pitch width / 2): the staging buffer d_bytes, a picture as it travels between GPUs
+hmr_gpu_picture packed_picture(const hmr_gpu_enc *e, const uint8_t *bytes)
+{
+	const int64_t w = e->seq.width, h = e->seq.height;
+	return hmr_gpu_picture{HMR_GPU_PIC_I420, 0, {bytes, bytes + w * h, bytes + w * h + (w / 2) * (h / 2)}, {w, w / 2, w / 2}};
+}
+// Queued on the encoder's own stream, nothing waited for: the packed picture at `bytes` (device memory) into the planes `dst` / e's final picture into one at `bytes`.
+int widen_packed(hmr_gpu_enc *e, const uint8_t *bytes, int16_t *const dst[3], int stride_y, int stride_c)
+{
+	const IngestJob j = ingest_job(e, packed_picture(e, bytes), dst, stride_y, stride_c);
+	return run_jobs(e->ingest, hmr_ingest_launch, e->ctx->stream, &j, 1, e->ctx->stream);
+}
+int narrow_packed(hmr_gpu_enc *e, uint8_t *bytes)
+{
+	const hmr_gpu_picture pic = packed_picture(e, bytes);
+	const EgressJob j = egress_job(e, &pic, nullptr, nullptr);
+	return run_jobs(e->egress, hmr_egress_launch, e->ctx->stream, &j, 1, e->ctx->stream);
+}
+
+// a picture in host memory into the planes `dst`: the device path (k_ingest) plus the copy into the staging buffer and a synchronise
+int load_planes(hmr_gpu_enc *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int16_t *const dst[3], int stride_y, int stride_c)
+{
+	hipStream_t st = e->ctx->stream;
+	const hmr_gpu_picture staged = packed_picture(e, e->d_bytes);
+	const uint8_t *in[3] = {y, u, v};
+	for (int c = 0; c < 3; c++)
+		HIP_TRY(hipMemcpyAsync(const_cast<uint8_t *>(staged.plane[c]), in[c], (size_t)staged.pitch[c] * (c ? e->seq.height / 2 : e->seq.height), hipMemcpyHostToDevice, st));
+	const int rc = widen_packed(e, e->d_bytes, dst, stride_y, stride_c);
+	if (rc) return rc;
+	HIP_TRY(hipStreamSynchronize(st));
 	return HMR_GPU_OK;
 }
 
@@ -752,16 +797,9 @@ extern "C" int hmr_gpu_enc_export_references8(hmr_gpu_enc **encs, int n, uint8_t
 	for (int i = 0; i < n; i++) {
 		hmr_gpu_enc *e = encs[i];
 		if (!e || pitch < hmr_gpu_enc_reference_bytes(e)) return HMR_GPU_ERR_ARG;
-		const Seq &s = e->seq;
-		hipStream_t st = e->ctx->stream;
 		HIP_TRY(hipSetDevice(e->ctx->device));
-		uint8_t *o = dev_rows + (size_t)i * pitch;
-		for (int c = 0; c < 3; c++) {
-			const int w = c ? s.width / 2 : s.width, h = c ? s.height / 2 : s.height;
-			hipLaunchKernelGGL(k_narrow_plane, dim3((w + 255) / 256, h), dim3(256), 0, st, plane0(e, e->cur, c), c ? s.stride_c : s.stride_y, w, h, o);
-			o += (size_t)w * h;
-		}
-		HIP_TRY(hipGetLastError());
+		const int rc = narrow_packed(e, dev_rows + (size_t)i * pitch);
+		if (rc) return rc;
 		memcpy((uint8_t *)states + (size_t)i * sizeof(HostState), &e->st, sizeof(HostState));
 	}
 	for (int i = 0; i < n; i++) HIP_TRY(hipStreamSynchronize(encs[i]->ctx->stream));
@@ -780,17 +818,12 @@ extern "C" int hmr_gpu_enc_import_references8(hmr_gpu_enc **encs, int n, const u
 			return HMR_GPU_ERR_ARG;
 		}
 		const Seq &s = e->seq;
-		hipStream_t st = e->ctx->stream;
 		HIP_TRY(hipSetDevice(e->ctx->device));
-		const uint8_t *o = dev_rows + (size_t)i * pitch;
-		for (int c = 0; c < 3; c++) {
-			const int w = c ? s.width / 2 : s.width, h = c ? s.height / 2 : s.height;
-			hipLaunchKernelGGL(k_widen_plane, dim3((w + 255) / 256, h), dim3(256), 0, st, o, w, h, plane0(e, e->cur, c), c ? s.stride_c : s.stride_y);
-			o += (size_t)w * h;
-		}
-		HIP_TRY(hipGetLastError());
-		hmr_gpu_frame fr = {s.width, s.height, plane0(e, e->cur, 0), plane0(e, e->cur, 1), plane0(e, e->cur, 2), s.stride_y, s.stride_c};
-		const int rc = hmr_gpu_pad_frame(e->ctx, &fr, s.margin_y, s.margin_y);
+		int16_t *dst[3] = {plane0(e, e->cur, 0), plane0(e, e->cur, 1), plane0(e, e->cur, 2)};
+		int rc = widen_packed(e, dev_rows + (size_t)i * pitch, dst, s.stride_y, s.stride_c);
+		if (rc) return rc;
+		hmr_gpu_frame fr = {s.width, s.height, dst[0], dst[1], dst[2], s.stride_y, s.stride_c};
+		rc = hmr_gpu_pad_frame(e->ctx, &fr, s.margin_y, s.margin_y);
 		if (rc) return rc;
 		e->st = in;
 	}
@@ -828,15 +861,10 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	if (e->d_gather) (void)hipFree(e->d_gather);
 	if (e->h_gather) (void)hipHostFree(e->h_gather);
 	if (e->h_offs) (void)hipHostFree(e->h_offs);
-	if (e->h_jobs) (void)hipHostFree(e->h_jobs);
-	if (e->d_jobs) (void)hipFree(e->d_jobs);
-	for (hipEvent_t ev : e->ev_jobs) if (ev) (void)hipEventDestroy(ev);
-	if (e->ev_produced) (void)hipEventDestroy(e->ev_produced);
-	if (e->ev_ingested) (void)hipEventDestroy(e->ev_ingested);
-	if (e->h_ejobs) (void)hipHostFree(e->h_ejobs);
-	if (e->d_ejobs) (void)hipFree(e->d_ejobs);
-	for (hipEvent_t ev : {e->ev_ejobs[0], e->ev_ejobs[1], e->ev_ejobs[2], e->ev_ejobs[3], e->ev_consumer, e->ev_egressed, e->ev_pic_done, e->ev_own_done})
-		if (ev) (void)hipEventDestroy(ev);
+	e->ingest.release();
+	e->egress.release();
+	if (e->ev_pic_done) (void)hipEventDestroy(e->ev_pic_done);
+	if (e->ev_own_done) (void)hipEventDestroy(e->ev_own_done);
 	if (e->d_batch) (void)hipFree(e->d_batch);
 	if (e->d_pool_state) (void)hipFree(e->d_pool_state);
 	if (e->d_pool_slow) (void)hipFree(e->d_pool_slow);
@@ -1116,15 +1144,9 @@ int frame_finish(hmr_gpu_enc *e, int slot, uint8_t *stream, long cap, long *stre
 		HIP_TRY(hipMemcpyAsync(e->h_bs.data() + total, e->d_bs + (size_t)r * e->row_cap, row_bytes[r], hipMemcpyDeviceToHost, st));
 		total += row_bytes[r];
 	}
-	if (recon) {
-		uint8_t *o = recon;
-		for (int c = 0; c < 3; c++) {
-			const int w = c ? s.width / 2 : s.width, h = c ? s.height / 2 : s.height;
-			hipLaunchKernelGGL(k_narrow_plane, dim3((w + 255) / 256, h), dim3(256), 0, st, plane0(e, e->cur, c), c ? s.stride_c : s.stride_y, w, h, e->d_bytes);
-			HIP_TRY(hipMemcpyAsync(o, e->d_bytes, (size_t)w * h, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipStreamSynchronize(st));
-			o += (size_t)w * h;
-		}
+	if (recon) {      // (the device path - k_egress into the staging buffer - plus one copy)
+		if ((rc = narrow_packed(e, e->d_bytes))) return rc;
+		HIP_TRY(hipMemcpyAsync(recon, e->d_bytes, (size_t)s.width * s.height * 3 / 2, hipMemcpyDeviceToHost, st));
 	}
 	HIP_TRY(hipStreamSynchronize(st));
 	const uint32_t *gr = e->h_gather;

@@ -1,0 +1,165 @@
+// Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
+// (include/homer_gpu.h sections 12d and 12e).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_egress (picture_io.hip)
+// on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
+//   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
+//   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
+//           streams (which may still load the slots); the consumer's stream and all of those streams go on behind it.
+// Each entry checks the caller's arguments and builds the jobs; the host-memory entries of k_encode_object.inc (widen_packed, narrow_packed) build theirs for a
+// packed picture - the staging buffer, a picture between GPUs - and run the same kernels.
+#include <unordered_set>
+namespace {
+int picture_refuse(const char *fn, int i, const char *what)
+{
+	hmr_set_error("%s: picture %d: %s", fn, i, what);
+	return HMR_GPU_ERR_ARG;
+}
+bool on_device(const void *p, int device)
+{
+	hipPointerAttribute_t attr;
+	memset(&attr, 0, sizeof attr);
+	if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == device) return true;
+	(void)hipGetLastError();
+	return false;
+}
+int not_device(const char *fn, int i, const char *what, int device)
+{
+	hmr_set_error("%s: picture %d: %s is not device memory of device %d", fn, i, what, device);
+	return HMR_GPU_ERR_ARG;
+}
+// a descriptor against the encoder's picture size
+int check_descriptor(const char *fn, int i, const hmr_gpu_picture *pic, const hmr_gpu_enc *e)
+{
+	if (hmr_gpu_picture_check(pic, e->seq.width, e->seq.height) == HMR_GPU_OK) return HMR_GPU_OK;
+	const std::string why = hmr_gpu_last_error();
+	return picture_refuse(fn, i, why.c_str());
+}
+// every plane of every picture is device memory of `device`
+int check_planes(const char *fn, const hmr_gpu_picture *pics, int n, int device)
+{
+	static const char *const names[3] = {"plane[0]", "plane[1]", "plane[2]"};
+	for (int i = 0; i < n; i++)
+		for (int c = 0; c < (pics[i].format == HMR_GPU_PIC_NV12 ? 2 : 3); c++)
+			if (!on_device(pics[i].plane[c], device)) return not_device(fn, i, names[c], device);
+	return HMR_GPU_OK;
+}
+}  // namespace
+
+extern "C" int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *pics, void *producer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_load_sources_device";
+	static_assert(PICTURE_MAX_JOBS == BATCH_MAX, "a load call feeds a batch call, an export call follows one");
+	if (!encs || !slots || !pics || n < 1 || n > PICTURE_MAX_JOBS) {
+		hmr_set_error("%s: needs 1 .. %d encoders with their slots and pictures (n = %d)", fn, PICTURE_MAX_JOBS, n);
+		return HMR_GPU_ERR_ARG;
+	}
+	for (int i = 0; i < n; i++) {
+		if (!encs[i]) return picture_refuse(fn, i, "the encoder is NULL");
+		if (slots[i] < 0 || slots[i] > 4096) return picture_refuse(fn, i, "the slot is outside 0 .. 4096");
+		if (encs[i]->ctx->device != encs[0]->ctx->device) return picture_refuse(fn, i, "the encoder is on another device than the call's first");
+	}
+	{
+		// the same (encoder, slot) twice: two pictures into one slot in one launch would leave a mix of them
+		std::vector<std::pair<hmr_gpu_enc *, int>> seen(n);
+		for (int i = 0; i < n; i++) seen[i] = {encs[i], slots[i]};
+		std::sort(seen.begin(), seen.end());
+		if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) {
+			hmr_set_error("%s: the same encoder and slot twice in one call", fn);
+			return HMR_GPU_ERR_ARG;
+		}
+	}
+	const int device = encs[0]->ctx->device;
+	int rc;
+	for (int i = 0; i < n; i++)
+		if ((rc = check_descriptor(fn, i, &pics[i], encs[i]))) return rc;
+	HIP_TRY(hipSetDevice(device));
+	if ((rc = check_planes(fn, pics, n, device))) return rc;
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		while ((int)e->src.size() <= slots[i]) {
+			SrcSlot sl;
+			for (int c = 0; c < 3; c++) DEV_ALLOC(sl.p[c], e->src_elems[c]);
+			e->src.push_back(sl);
+		}
+	}
+	std::vector<IngestJob> jobs(n);
+	for (int i = 0; i < n; i++) jobs[i] = ingest_job(encs[i], pics[i], encs[i]->src[slots[i]].p, encs[i]->seq.src_stride_y, encs[i]->seq.src_stride_c);
+	// the pictures are complete when what the producer's stream holds now has run; every other encoder's stream (an encode call starts there: set-up copies, ev_ready)
+	// and the producer's (it may write the pictures again) go on behind the ingest
+	hipStream_t producer = (hipStream_t)producer_stream;
+	std::vector<hipStream_t> behind(1, producer);
+	for (int i = 1; i < n; i++) behind.push_back(encs[i]->ctx->stream);
+	return run_jobs(encs[0]->ingest, hmr_ingest_launch, encs[0]->ctx->stream, jobs.data(), n, producer, behind);
+}
+
+extern "C" int hmr_gpu_enc_load_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_picture *pic, void *producer_stream)
+{
+	return hmr_gpu_enc_load_sources_device(&enc, 1, &slot, pic, producer_stream);
+}
+
+extern "C" int hmr_gpu_enc_export_pictures_device(hmr_gpu_enc **encs, int n, const hmr_gpu_picture *pics, const int *slots, uint64_t *dev_ssd, void *consumer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_export_pictures_device";
+	if (!encs || n < 1 || n > PICTURE_MAX_JOBS) {
+		hmr_set_error("%s: needs 1 .. %d encoders (n = %d)", fn, PICTURE_MAX_JOBS, n);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!pics && !slots) {
+		hmr_set_error("%s: neither pictures nor slots: nothing to do", fn);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!slots != !dev_ssd) {
+		hmr_set_error("%s: slots and dev_ssd go together (the sums of squared differences against the slots' pictures)", fn);
+		return HMR_GPU_ERR_ARG;
+	}
+	int rc;
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		if (!e) return picture_refuse(fn, i, "the encoder is NULL");
+		if (e->ctx->device != encs[0]->ctx->device) return picture_refuse(fn, i, "the encoder is on another device than the call's first");
+		if (!e->has_picture) return picture_refuse(fn, i, "the encoder has not encoded a picture yet");
+		if (slots && (slots[i] < 0 || slots[i] >= (int)e->src.size())) return picture_refuse(fn, i, "the slot does not exist");
+		if (slots && e->seq.width > EGRESS_MAX_WIDTH) return picture_refuse(fn, i, "sums are made for pictures up to 8192 samples wide");
+		if (pics && (rc = check_descriptor(fn, i, &pics[i], e))) return rc;
+	}
+	const int device = encs[0]->ctx->device;
+	HIP_TRY(hipSetDevice(device));
+	if (pics && (rc = check_planes(fn, pics, n, device))) return rc;
+	if (dev_ssd && (!on_device(dev_ssd, device) || !on_device(dev_ssd + 3 * (size_t)n - 1, device))) return not_device(fn, 0, "dev_ssd", device);
+	std::vector<EgressJob> jobs(n);
+	for (int i = 0; i < n; i++)
+		jobs[i] = egress_job(encs[i], pics ? &pics[i] : nullptr, slots ? encs[i]->src[slots[i]].p : nullptr, dev_ssd ? dev_ssd + 3 * (size_t)i : nullptr);
+	hipStream_t st = encs[0]->ctx->stream, consumer = (hipStream_t)consumer_stream;
+	// Behind the consumer (its work on the output memory and on dev_ssd: run_jobs), and here behind the launches that wrote the final pictures and behind what the
+	// encoders' own streams hold (loads into the slots), every distinct stream once.  The consumer reads the output behind the egress; a later encode call rewrites the
+	// final picture, a later load the slot: those streams go on behind it too.
+	auto behind_the_writers = [&](std::vector<hipStream_t> &behind) -> int {
+		std::unordered_set<hipStream_t> seen = {consumer, st};
+		for (int i = 0; i < n; i++) {
+			hmr_gpu_enc *e = encs[i];
+			if (!e->ev_pic_done) {
+				HIP_TRY(hipEventCreateWithFlags(&e->ev_pic_done, hipEventDisableTiming));
+				HIP_TRY(hipEventCreateWithFlags(&e->ev_own_done, hipEventDisableTiming));
+			}
+			const hipStream_t wrote[2] = {e->pic_stream, e->ctx->stream};
+			hipEvent_t const ev[2] = {e->ev_pic_done, e->ev_own_done};
+			for (int k = 0; k < 2; k++) {
+				if (!seen.insert(wrote[k]).second) continue;
+				behind.push_back(wrote[k]);
+				// a stream with nothing in flight has nothing to queue behind (calls on one encoder come from one host thread at a time: nobody is adding to it now);
+				// the query is far cheaper than an event and a wait, and after an encode call most of a batch's streams are idle
+				if (hipStreamQuery(wrote[k]) == hipSuccess) continue;
+				(void)hipGetLastError();
+				HIP_TRY(hipEventRecord(ev[k], wrote[k]));
+				HIP_TRY(hipStreamWaitEvent(st, ev[k], 0));
+			}
+		}
+		if (dev_ssd) HIP_TRY(hipMemsetAsync(dev_ssd, 0, 3 * (size_t)n * sizeof(uint64_t), st));
+		return HMR_GPU_OK;
+	};
+	return run_jobs(encs[0]->egress, hmr_egress_launch, st, jobs.data(), n, consumer, std::vector<hipStream_t>(1, consumer), behind_the_writers);
+}
+
+extern "C" int hmr_gpu_enc_export_picture_device(hmr_gpu_enc *enc, const hmr_gpu_picture *pic, int slot, uint64_t *dev_ssd, void *consumer_stream)
+{
+	return hmr_gpu_enc_export_pictures_device(&enc, 1, pic, slot >= 0 ? &slot : nullptr, dev_ssd, consumer_stream);
+}

@@ -1,0 +1,122 @@
+// Picture conversion on the device (picture_io.hip): 8-bit 4:2:0 pictures in device memory <-> the int16 planes of the frame encoder, a batch of pictures per launch.
+// Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture).  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
+// squared differences against the int16 source planes of a picture slot.  A launch reads its pictures from a job table; JobRing holds the tables of one encoder and
+// run_jobs queues one launch, ordered against the caller's stream by events (k_encode_picture_io.inc and the host-memory entries of k_encode_object.inc use it).
+#pragma once
+#include <algorithm>
+#include <functional>
+#include <vector>
+#include "common.h"
+
+#define PICTURE_MAX_JOBS 512         // pictures per launch (the batch calls' limit)
+#define PICTURE_RING 4               // job tables of one direction in flight
+#define EGRESS_MAX_WIDTH 8192        // a workgroup's partial sum stays inside 32 bits up to this width (picture_io.hip)
+
+// one picture of an ingest launch
+struct IngestJob {
+	const uint8_t *src[3];       // I420: Y, U, V; NV12: Y, interleaved UV, unused
+	int64_t pitch[3];            // bytes from row to row
+	int16_t *dst[3];             // the planes at sample (0, 0); 16-byte aligned
+	int32_t stride_y, stride_c;  // elements, multiples of 8
+	int32_t width, height, format, reserved;
+};
+
+// one picture of an egress launch
+struct EgressJob {
+	const int16_t *rec[3];       // the final picture's planes at sample (0, 0); 16-byte aligned, read-only
+	const int16_t *src[3];       // the slot's planes, or all NULL: no sums
+	uint8_t *dst[3];             // I420: Y, U, V; NV12: Y, interleaved UV, unused; or all NULL: no picture
+	int64_t pitch[3];            // bytes from row to row of dst
+	uint64_t *ssd;               // three sums (zeroed in front of the launch), or NULL
+	int32_t stride_y, stride_c;  // of rec, elements, multiples of 8
+	int32_t src_stride_y, src_stride_c;
+	int32_t width, height, format, reserved;
+};
+
+// Algorithmic bytes of one width x height picture through k_egress (tools/egress_bench.py restates it): the final picture is read, the slot's picture is read
+// when sums are asked for, the 8-bit picture is written when one is asked for.
+static inline double hmr_egress_bytes(int width, int height, int picture, int sums)
+{
+	const double wh = (double)width * height;
+	return 3.0 * wh + (sums ? 3.0 * wh : 0.0) + (picture ? 1.5 * wh : 0.0);
+}
+
+// The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of k_ingest /
+// k_egress handles all n pictures; both on `stream`, nothing is waited for.
+int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n);
+int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n);
+
+// The job tables of the calls one encoder leads, in one direction: a ring of tables in page-locked memory (a table is written again only when the launch that read it
+// is known to be over: ev_turn), their copy on the device, the events towards the outside stream (producer or consumer) and towards the streams that go on behind a launch.
+template <class Job>
+struct JobRing {
+	Job *h = nullptr, *d = nullptr;
+	int cap = 0, next = 0;
+	hipEvent_t ev_turn[PICTURE_RING] = {nullptr, nullptr, nullptr, nullptr}, ev_outside = nullptr, ev_done = nullptr;
+
+	// made at the first call (or a larger one: the work `st` holds, which reads the old tables, is waited for)
+	int prepare(int n, hipStream_t st)
+	{
+		if (!ev_done) {
+			for (hipEvent_t &ev : ev_turn) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+			HIP_TRY(hipEventCreateWithFlags(&ev_outside, hipEventDisableTiming));
+			HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+		}
+		if (n <= cap) return HMR_GPU_OK;
+		HIP_TRY(hipStreamSynchronize(st));
+		if (h) (void)hipHostFree(h);
+		if (d) (void)hipFree(d);
+		h = d = nullptr;
+		cap = 0;
+		const int want = n == 1 ? 1 : PICTURE_MAX_JOBS;
+		HIP_TRY(hipHostMalloc((void **)&h, (size_t)PICTURE_RING * want * sizeof(Job), hipHostMallocDefault));
+		HIP_TRY(hipMalloc((void **)&d, (size_t)want * sizeof(Job)));
+		cap = want;
+		next = 0;
+		return HMR_GPU_OK;
+	}
+	// the next table of the ring and the event to record behind the launch that reads it
+	int next_table(Job **table, hipEvent_t *turn)
+	{
+		*turn = ev_turn[next];
+		*table = h + (size_t)next * cap;
+		next = (next + 1) % PICTURE_RING;
+		HIP_TRY(hipEventSynchronize(*turn));      // (the launch of PICTURE_RING calls ago: over long since; an event never recorded counts as complete)
+		return HMR_GPU_OK;
+	}
+	void release()
+	{
+		if (h) (void)hipHostFree(h);
+		if (d) (void)hipFree(d);
+		for (hipEvent_t ev : {ev_turn[0], ev_turn[1], ev_turn[2], ev_turn[3], ev_outside, ev_done})
+			if (ev) (void)hipEventDestroy(ev);
+	}
+};
+
+// One launch (hmr_ingest_launch / hmr_egress_launch) over n jobs on `st`, behind what the `outside` stream holds now and behind whatever `before` queues (it may add to
+// `behind`); every distinct stream of `behind` goes on behind the launch.  The host waits for nothing but the ring's turn.
+template <class Job>
+int run_jobs(JobRing<Job> &ring, int (*launch)(hipStream_t, const Job *, Job *, int), hipStream_t st, const Job *jobs, int n, hipStream_t outside,
+	     std::vector<hipStream_t> behind = {}, const std::function<int(std::vector<hipStream_t> &)> &before = nullptr)
+{
+	int rc = ring.prepare(n, st);
+	if (rc) return rc;
+	Job *table;
+	hipEvent_t turn;
+	if ((rc = ring.next_table(&table, &turn))) return rc;
+	std::copy(jobs, jobs + n, table);
+	if (outside != st) {
+		HIP_TRY(hipEventRecord(ring.ev_outside, outside));
+		HIP_TRY(hipStreamWaitEvent(st, ring.ev_outside, 0));
+	}
+	if (before && (rc = before(behind))) return rc;
+	if ((rc = launch(st, table, ring.d, n))) return rc;
+	HIP_TRY(hipEventRecord(turn, st));
+	std::sort(behind.begin(), behind.end());
+	behind.erase(std::unique(behind.begin(), behind.end()), behind.end());
+	behind.erase(std::remove(behind.begin(), behind.end(), st), behind.end());
+	if (behind.empty()) return HMR_GPU_OK;
+	HIP_TRY(hipEventRecord(ring.ev_done, st));
+	for (hipStream_t w : behind) HIP_TRY(hipStreamWaitEvent(w, ring.ev_done, 0));
+	return HMR_GPU_OK;
+}

@@ -1,0 +1,330 @@
+// Picture conversion on the device (include/homer_gpu.h sections 12d and 12e): 8-bit 4:2:0 pictures in device memory - I420 planes or NV12, any base address, any
+// pitch - to and from the int16 planes of the frame encoder (sample (x, y) at y * stride + x).  ONE launch for a batch of pictures in either direction; neither has
+// arithmetic to speak of, both are bound by HBM.
+//
+// k_ingest: 8-bit pictures into int16 planes - the source planes of a picture slot, or a reference picture: sample (x, y) at y * stride + x, nothing outside
+// width x height touched.  1.5 W H bytes read, 3 W H written per picture.
+// k_egress: the frame encoder's final pictures (int16 planes with margins) into 8-bit pictures, and / or the exact sums of squared differences of each plane against the
+// int16 source planes of a picture slot.  Per picture 3 W H bytes read (final picture), 3 W H read (slot, when sums are asked for), 1.5 W H written (when a picture is
+// asked for) - hmr_egress_bytes in picture_io.h.
+//
+// Mapping (struct Chunk): blockIdx.y = picture (a record of the job table), blockIdx.x = a chunk of CHUNK_ROWS rows of it - first the luma rows, then the chroma rows (a
+// chroma row is its U and its V part: as many 8-bit bytes as a luma row) - so that one grid covers the three planes of every picture; pictures smaller than the largest
+// of the launch leave their last chunks empty.  A lane takes a span of 16 samples.  Ingest: one 16-byte load, two 16-byte stores of int16; NV12 chroma: one 16-byte load
+// of eight U, V pairs, one 16-byte store to each plane.  Egress: two 16-byte loads of the final picture (four with the slot's samples), the low bytes packed by
+// v_perm_b32 into ONE 16-byte store; NV12 chroma: a 16-byte load of eight U and one of eight V samples, interleaved into one 16-byte store.  The int16 side is always
+// 16-byte aligned (strides and margins are multiples of 8 elements, the planes come from hipMalloc, a lane starts at a multiple of 8 elements).  The 8-bit side is
+// whatever the caller made: its 16-byte load or store is issued at whatever address the row gives it (load16 / store16 below); a row's tail of fewer than 16 samples
+// goes sample by sample.  No lane reads or writes a byte of an 8-bit plane outside [plane + y * pitch, plane + y * pitch + row bytes).
+//
+// Sums: a lane adds the squares of its differences into 32-bit accumulators (one for luma or U, one for V), the wavefront's lanes are summed by the DPP butterfly of
+// common.h, the workgroup's four wavefronts through LDS in 64 bits, and one lane adds the workgroup's sum to the picture's 64-bit sum of that plane with one vector atomic
+// (global_atomic_add_x2).  Integer sums: exact whatever the order.  A chunk holds at most CHUNK_ROWS x EGRESS_MAX_WIDTH samples of one plane, each difference at most 255:
+// 8 x 8192 x 255^2 = 4 261 478 400 < 2^32, so neither a lane's nor a wavefront's accumulator wraps; a picture's sum does not fit 32 bits (255^2 x 3840 x 2160 = 5.4e11).
+#include <math.h>
+#include "picture_io.h"
+
+namespace {
+constexpr int CHUNK_ROWS = 8;
+static_assert((uint64_t)CHUNK_ROWS * EGRESS_MAX_WIDTH * 255 * 255 < (1ull << 32), "a workgroup's partial sum of one plane fits 32 bits");
+
+// The job tables hold plain pointers; the kernels address them as global memory (global_load / global_store instead of the flat forms).
+#define GLOBAL_AS __attribute__((address_space(1)))
+typedef GLOBAL_AS const uint8_t *bytes_in;
+typedef GLOBAL_AS uint8_t *bytes_out;
+typedef GLOBAL_AS const int16_t *samples_in;
+typedef GLOBAL_AS int16_t *samples_out;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_unaligned __attribute__((aligned(1)));
+
+// Exactly the 16 bytes at s / d, whatever the alignment: ONE global_load_dwordx4 / global_store_dwordx4 (the memory pipeline takes vector accesses at any byte address;
+// one that straddles a cache line costs a second line access, no more bytes).  Spelling the unaligned case as dword or byte accesses gives the same instruction: the
+// backend merges them.
+__device__ __forceinline__ u32x4 load16(bytes_in s) { return *(GLOBAL_AS const u32x4_unaligned *)s; }
+__device__ __forceinline__ void store16(bytes_out d, u32x4 v) { *(GLOBAL_AS u32x4_unaligned *)d = v; }
+
+// What workgroup b of a W x H picture does.  Its class: luma(), chroma, or nothing (empty()); its rows of that class: [rows().y0, rows().y0 + rows().n); the spans of one row:
+// luma_spans() of 16 samples; chroma as pairs (NV12): pair_spans() of 8 U, V pairs; chroma as planes (I420): plane_spans() of 16 samples of the row's U part, then as
+// many of its V part.  (Accessors, not fields: each is evaluated where a kernel has already branched on the class, so nothing is computed for another class.)
+struct Rows {
+	int y0, n;
+};
+struct Chunk {
+	int b, W, H;
+	__host__ __device__ __forceinline__ int luma_chunks() const { return (H + CHUNK_ROWS - 1) / CHUNK_ROWS; }
+	__host__ __device__ __forceinline__ int chroma_chunks() const { return ((H >> 1) + CHUNK_ROWS - 1) / CHUNK_ROWS; }
+	__host__ __device__ __forceinline__ int chunks() const { return luma_chunks() + chroma_chunks(); }      // (the grid's x size for this picture)
+	__host__ __device__ __forceinline__ bool luma() const { return b < luma_chunks(); }
+	__host__ __device__ __forceinline__ bool empty() const { return b >= chunks(); }
+	__host__ __device__ __forceinline__ Rows rows() const
+	{
+		const int y0 = (luma() ? b : b - luma_chunks()) * CHUNK_ROWS, left = (luma() ? H : H >> 1) - y0;
+		return Rows{y0, left < CHUNK_ROWS ? left : CHUNK_ROWS};
+	}
+	__host__ __device__ __forceinline__ int luma_spans() const { return (W + 15) >> 4; }
+	__host__ __device__ __forceinline__ int pair_spans() const { return ((W >> 1) + 7) >> 3; }
+	__host__ __device__ __forceinline__ int plane_spans() const { return ((W >> 1) + 15) >> 4; }
+};
+
+// ---- ingest ----
+__device__ __forceinline__ uint32_t even_bytes(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0c020c00u); }      // bytes 0 and 2 of w as two 16-bit values
+__device__ __forceinline__ uint32_t odd_bytes(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0c030c01u); }       // bytes 1 and 3
+__device__ __forceinline__ uint32_t low_bytes(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0c010c00u); }       // bytes 0 and 1
+__device__ __forceinline__ uint32_t high_bytes(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0c030c02u); }      // bytes 2 and 3
+
+// n <= 16 samples of a plane row, widened; d is 16-byte aligned
+__device__ __forceinline__ void widen_span(bytes_in s, samples_out d, int n)
+{
+	if (n == 16) {
+		const u32x4 v = load16(s);
+		GLOBAL_AS u32x4 *o = (GLOBAL_AS u32x4 *)d;
+		o[0] = u32x4{low_bytes(v.x), high_bytes(v.x), low_bytes(v.y), high_bytes(v.y)};
+		o[1] = u32x4{low_bytes(v.z), high_bytes(v.z), low_bytes(v.w), high_bytes(v.w)};
+		return;
+	}
+	for (int i = 0; i < n; i++) d[i] = s[i];      // (a row's tail)
+}
+// n <= 8 pairs of an NV12 chroma row into the U and the V plane; du / dv are 16-byte aligned
+__device__ __forceinline__ void split_span(bytes_in s, samples_out du, samples_out dv, int n)
+{
+	if (n == 8) {
+		const u32x4 v = load16(s);
+		*(GLOBAL_AS u32x4 *)du = u32x4{even_bytes(v.x), even_bytes(v.y), even_bytes(v.z), even_bytes(v.w)};
+		*(GLOBAL_AS u32x4 *)dv = u32x4{odd_bytes(v.x), odd_bytes(v.y), odd_bytes(v.z), odd_bytes(v.w)};
+		return;
+	}
+	for (int i = 0; i < n; i++) { du[i] = s[2 * i]; dv[i] = s[2 * i + 1]; }
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_ingest(const IngestJob *jobs)
+{
+	const IngestJob j = jobs[blockIdx.y];
+	const int W = j.width, cw = W >> 1, t = (int)threadIdx.x;
+	const Chunk k{(int)blockIdx.x, W, j.height};
+	if (k.luma()) {
+		const Rows rw = k.rows();
+		const int y0 = rw.y0, rows = rw.n, per_row = k.luma_spans();
+		const bytes_in src = (bytes_in)j.src[0];
+		const samples_out dst = (samples_out)j.dst[0];
+		const int64_t pitch = j.pitch[0];
+		const int stride = j.stride_y;
+		for (int i = t; i < rows * per_row; i += HMR_BLOCK) {
+			const int r = i / per_row, x = (i - r * per_row) << 4, y = y0 + r;
+			widen_span(src + (int64_t)y * pitch + x, dst + (size_t)y * stride + x, W - x < 16 ? W - x : 16);
+		}
+		return;
+	}
+	if (k.empty()) return;
+	const Rows rw = k.rows();
+	const int y0 = rw.y0, rows = rw.n;
+	const int stride = j.stride_c;
+	if (j.format == HMR_GPU_PIC_NV12) {
+		const int per_row = k.pair_spans();
+		const bytes_in src = (bytes_in)j.src[1];
+		const samples_out du = (samples_out)j.dst[1], dv = (samples_out)j.dst[2];
+		const int64_t pitch = j.pitch[1];
+		for (int i = t; i < rows * per_row; i += HMR_BLOCK) {
+			const int r = i / per_row, x = (i - r * per_row) << 3, y = y0 + r;
+			const size_t o = (size_t)y * stride + x;
+			split_span(src + (int64_t)y * pitch + 2 * x, du + o, dv + o, cw - x < 8 ? cw - x : 8);
+		}
+		return;
+	}
+	const int per_plane = k.plane_spans(), per_row = 2 * per_plane;      // (a row's U part, then its V part)
+	const bytes_in su = (bytes_in)j.src[1], sv = (bytes_in)j.src[2];
+	const samples_out du = (samples_out)j.dst[1], dv = (samples_out)j.dst[2];
+	const int64_t pu = j.pitch[1], pv = j.pitch[2];
+	for (int i = t; i < rows * per_row; i += HMR_BLOCK) {
+		const int r = i / per_row, g = i - r * per_row, y = y0 + r;
+		const bool is_v = g >= per_plane;
+		const int x = (is_v ? g - per_plane : g) << 4;
+		widen_span((is_v ? sv : su) + (int64_t)y * (is_v ? pv : pu) + x, (is_v ? dv : du) + (size_t)y * stride + x, cw - x < 16 ? cw - x : 16);
+	}
+}
+
+// ---- egress ----
+// two dwords of two int16 samples each -> their four low bytes
+__device__ __forceinline__ uint32_t pack4(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x06040200u); }
+// a dword of two U samples, a dword of two V samples -> U0 V0 U1 V1
+__device__ __forceinline__ uint32_t weave4(uint32_t u, uint32_t v) { return __builtin_amdgcn_perm(v, u, 0x06020400u); }
+__device__ __forceinline__ u32x4 pack16(u32x4 a, u32x4 b) { return u32x4{pack4(a.x, a.y), pack4(a.z, a.w), pack4(b.x, b.y), pack4(b.z, b.w)}; }
+
+// squared differences of two int16 pairs
+__device__ __forceinline__ uint32_t sq2(uint32_t a, uint32_t b)
+{
+	const int d0 = (int)(int16_t)a - (int)(int16_t)b, d1 = ((int)a >> 16) - ((int)b >> 16);
+	return (uint32_t)(d0 * d0) + (uint32_t)(d1 * d1);
+}
+__device__ __forceinline__ uint32_t sq8(u32x4 a, u32x4 b) { return sq2(a.x, b.x) + sq2(a.y, b.y) + sq2(a.z, b.z) + sq2(a.w, b.w); }
+
+// n <= 16 samples of a plane row: r / s 16-byte aligned (s NULL: no sum), d anywhere (NULL: no picture); returns the sum of squared differences
+__device__ __forceinline__ uint32_t narrow_span(samples_in r, samples_in s, bytes_out d, int n)
+{
+	uint32_t acc = 0;
+	if (n == 16) {
+		const GLOBAL_AS u32x4 *rv = (const GLOBAL_AS u32x4 *)r;
+		const u32x4 a = rv[0], b = rv[1];
+		if (s) {
+			const GLOBAL_AS u32x4 *sv = (const GLOBAL_AS u32x4 *)s;
+			acc = sq8(sv[0], a) + sq8(sv[1], b);
+		}
+		if (d) store16(d, pack16(a, b));
+		return acc;
+	}
+	for (int i = 0; i < n; i++) {      // (a row's tail)
+		const int v = r[i];
+		if (s) { const int e = s[i] - v; acc += (uint32_t)(e * e); }
+		if (d) d[i] = (uint8_t)v;
+	}
+	return acc;
+}
+// n <= 8 samples of a U and of a V row into n pairs of an NV12 chroma row; the sums of both planes
+__device__ __forceinline__ void weave_span(samples_in ru, samples_in rv, samples_in su, samples_in sv, bytes_out d, int n, uint32_t &acc_u, uint32_t &acc_v)
+{
+	if (n == 8) {
+		const u32x4 u = *(const GLOBAL_AS u32x4 *)ru, v = *(const GLOBAL_AS u32x4 *)rv;
+		if (su) {
+			acc_u += sq8(*(const GLOBAL_AS u32x4 *)su, u);
+			acc_v += sq8(*(const GLOBAL_AS u32x4 *)sv, v);
+		}
+		if (d) store16(d, u32x4{weave4(u.x, v.x), weave4(u.y, v.y), weave4(u.z, v.z), weave4(u.w, v.w)});
+		return;
+	}
+	for (int i = 0; i < n; i++) {
+		const int u = ru[i], v = rv[i];
+		if (su) { const int eu = su[i] - u, ev = sv[i] - v; acc_u += (uint32_t)(eu * eu); acc_v += (uint32_t)(ev * ev); }
+		if (d) { d[2 * i] = (uint8_t)u; d[2 * i + 1] = (uint8_t)v; }
+	}
+}
+
+// the workgroup's sum of `acc` to sum[0] and, when `two`, of `acc2` to sum[1]; every lane of the workgroup comes here
+__device__ __forceinline__ void add_sums(GLOBAL_AS uint64_t *sum, uint32_t acc, uint32_t acc2, bool two)
+{
+	__shared__ uint32_t part[2][HMR_WAVES_PER_BLOCK];
+	const uint32_t w0 = wave_sum(acc), w1 = two ? wave_sum(acc2) : 0u;
+	if (lane_id() == 0) { part[0][wave_in_block()] = w0; part[1][wave_in_block()] = w1; }
+	__syncthreads();
+	if (threadIdx.x < (two ? 2u : 1u)) {
+		uint64_t total = 0;
+		for (int k = 0; k < HMR_WAVES_PER_BLOCK; k++) total += part[threadIdx.x][k];
+		if (total) __hip_atomic_fetch_add(sum + threadIdx.x, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_egress(const EgressJob *jobs)
+{
+	const EgressJob j = jobs[blockIdx.y];
+	const int W = j.width, cw = W >> 1, t = (int)threadIdx.x;
+	const Chunk k{(int)blockIdx.x, W, j.height};
+	const bool luma = k.luma(), sums = j.src[0] != nullptr, picture = j.dst[0] != nullptr;
+	GLOBAL_AS uint64_t *ssd = (GLOBAL_AS uint64_t *)j.ssd;
+	if (luma) {
+		const Rows rw = k.rows();
+		const int y0 = rw.y0, rows = rw.n, per_row = k.luma_spans();
+		const samples_in rec = (samples_in)j.rec[0], src = (samples_in)j.src[0];
+		const bytes_out dst = (bytes_out)j.dst[0];
+		const int64_t pitch = j.pitch[0];
+		uint32_t acc = 0;
+		for (int i = t; i < rows * per_row; i += HMR_BLOCK) {
+			const int r = i / per_row, x = (i - r * per_row) << 4, y = y0 + r;
+			acc += narrow_span(rec + (size_t)y * j.stride_y + x, sums ? src + (size_t)y * j.src_stride_y + x : nullptr, picture ? dst + (int64_t)y * pitch + x : nullptr,
+					   W - x < 16 ? W - x : 16);
+		}
+		if (sums) add_sums(ssd, acc, 0, false);
+		return;
+	}
+	if (k.empty()) return;
+	const Rows rw = k.rows();
+	const int y0 = rw.y0, rows = rw.n;
+	const samples_in ru = (samples_in)j.rec[1], rv = (samples_in)j.rec[2], su = (samples_in)j.src[1], sv = (samples_in)j.src[2];
+	uint32_t acc_u = 0, acc_v = 0;
+	if (j.format == HMR_GPU_PIC_NV12 && picture) {      // (sums alone: plane by plane)
+		const int per_row = k.pair_spans();
+		const bytes_out dst = (bytes_out)j.dst[1];
+		const int64_t pitch = j.pitch[1];
+		for (int i = t; i < rows * per_row; i += HMR_BLOCK) {
+			const int r = i / per_row, x = (i - r * per_row) << 3, y = y0 + r;
+			const size_t o = (size_t)y * j.stride_c + x, so = (size_t)y * j.src_stride_c + x;
+			weave_span(ru + o, rv + o, sums ? su + so : nullptr, sums ? sv + so : nullptr, dst + (int64_t)y * pitch + 2 * x, cw - x < 8 ? cw - x : 8, acc_u, acc_v);
+		}
+	} else {
+		const int per_plane = k.plane_spans(), per_row = 2 * per_plane;      // (a row's U part, then its V part)
+		const bytes_out du = (bytes_out)j.dst[1], dv = (bytes_out)j.dst[2];
+		const int64_t pu = j.pitch[1], pv = j.pitch[2];
+		for (int i = t; i < rows * per_row; i += HMR_BLOCK) {
+			const int r = i / per_row, g = i - r * per_row, y = y0 + r;
+			const bool is_v = g >= per_plane;
+			const int x = (is_v ? g - per_plane : g) << 4;
+			const uint32_t a = narrow_span((is_v ? rv : ru) + (size_t)y * j.stride_c + x, sums ? (is_v ? sv : su) + (size_t)y * j.src_stride_c + x : nullptr,
+						       picture ? (is_v ? dv : du) + (int64_t)y * (is_v ? pv : pu) + x : nullptr, cw - x < 16 ? cw - x : 16);
+			if (is_v) acc_v += a; else acc_u += a;
+		}
+	}
+	if (sums) add_sums(ssd + 1, acc_u, acc_v, true);
+}
+
+// ---- launches ----
+// a job table from page-locked host memory to the device by a kernel, `words` 32-bit words per job: a host-to-device copy would queue on the copy engines behind a
+// batch's multi-megabyte download (k_encode_batch.inc, k_batch_stage)
+__global__ __launch_bounds__(64) void k_picture_jobs(const uint32_t *h_jobs, uint32_t *d_jobs, int words)
+{
+	for (int k = threadIdx.x; k < words; k += blockDim.x) d_jobs[blockIdx.x * words + k] = h_jobs[blockIdx.x * words + k];
+}
+
+template <class Job>
+int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n)
+{
+	static_assert(sizeof(Job) % 4 == 0, "word copies");
+	if (!h_jobs || !d_jobs || n < 1 || n > PICTURE_MAX_JOBS) return HMR_GPU_ERR_ARG;
+	int chunks = 0;      // of the tallest picture
+	for (int i = 0; i < n; i++) chunks = std::max(chunks, Chunk{0, h_jobs[i].width, h_jobs[i].height}.chunks());
+	hipLaunchKernelGGL(k_picture_jobs, dim3(n), dim3(64), 0, stream, (const uint32_t *)h_jobs, (uint32_t *)d_jobs, (int)(sizeof(Job) / 4));
+	hipLaunchKernelGGL(kernel, dim3(chunks, n), dim3(HMR_BLOCK), 0, stream, (const Job *)d_jobs);
+	HIP_TRY(hipGetLastError());
+	return HMR_GPU_OK;
+}
+}  // namespace
+
+int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n) { return launch(k_ingest, stream, h_jobs, d_jobs, n); }
+int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n) { return launch(k_egress, stream, h_jobs, d_jobs, n); }
+
+static int refuse(const char *what)
+{
+	hmr_set_error("hmr_gpu_picture: %s", what);
+	return HMR_GPU_ERR_ARG;
+}
+// a descriptor against a picture size, on the host alone
+extern "C" int hmr_gpu_picture_check(const hmr_gpu_picture *pic, int width, int height)
+{
+	if (!pic) return refuse("the descriptor is NULL");
+	if (pic->format != HMR_GPU_PIC_I420 && pic->format != HMR_GPU_PIC_NV12) return refuse("format: neither HMR_GPU_PIC_I420 nor HMR_GPU_PIC_NV12");
+	if (pic->reserved != 0) return refuse("reserved: must be 0");
+	if (width <= 0 || (width & 1)) return refuse("width: must be positive and even");
+	if (height <= 0 || (height & 1)) return refuse("height: must be positive and even");
+	const int planes = pic->format == HMR_GPU_PIC_NV12 ? 2 : 3;
+	static const char *const missing[3] = {"plane[0]: NULL", "plane[1]: NULL", "plane[2]: NULL"};
+	static const char *const negative[3] = {"pitch[0]: negative", "pitch[1]: negative", "pitch[2]: negative"};
+	static const char *const narrow[3] = {"pitch[0]: less than a row's bytes (width)", "pitch[1]: less than a row's bytes (I420: width / 2, NV12: width)", "pitch[2]: less than a row's bytes (width / 2)"};
+	for (int c = 0; c < planes; c++) {
+		if (!pic->plane[c]) return refuse(missing[c]);
+		if (pic->pitch[c] < 0) return refuse(negative[c]);
+		const int row_bytes = c == 0 || pic->format == HMR_GPU_PIC_NV12 ? width : width / 2;
+		if (pic->pitch[c] < row_bytes) return refuse(narrow[c]);
+	}
+	if (planes == 2 && pic->plane[2]) return refuse("plane[2]: must be NULL for NV12 (plane[1] holds the U, V pairs)");
+	return HMR_GPU_OK;
+}
+
+// homer_psnr's arithmetic (hmr_metics.c:66-104) on sums of squared differences: pure host
+extern "C" int hmr_gpu_psnr(const uint64_t ssd[3], int width, int height, double psnr[3])
+{
+	if (!ssd || !psnr || width <= 0 || height <= 0 || (width & 1) || (height & 1)) {
+		hmr_set_error("hmr_gpu_psnr: needs three sums, three results and a positive even width and height (%d x %d)", width, height);
+		return HMR_GPU_ERR_ARG;
+	}
+	for (int c = 0; c < 3; c++) {
+		const double samples = c ? (double)(width / 2) * (height / 2) : (double)width * height;
+		psnr[c] = ssd[c] ? 10.0 * log10(255.0 * 255.0 * samples / (double)ssd[c]) : 99.99;
+	}
+	return HMR_GPU_OK;
+}

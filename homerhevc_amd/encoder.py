@@ -8,7 +8,7 @@
     y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
 
 ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d and 12e).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (csrc/k_ingest.hip) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (csrc/k_egress.hip), both
+the ingest kernel (k_ingest, csrc/picture_io.hip) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), both
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """

@@ -697,7 +697,7 @@ int hmr_gpu_enc_import_references8(hmr_gpu_enc **encs, int n, const uint8_t *dev
 /* ------------------------------------------------------------------------------------------------
  * 12d. Pictures in device memory (no counterpart in the reference, whose pictures arrive in host memory)
  *     A decoder, a renderer or a tensor library leaves its pictures on the GPU.  hmr_gpu_enc_load_sources_device converts n of them (1 .. 512) into picture slots of
- *     their encoders with ONE launch of a bandwidth-bound kernel (k_ingest.hip) and no host synchronisation; the slots are what hmr_gpu_enc_load_source makes of the
+ *     their encoders with ONE launch of a bandwidth-bound kernel (k_ingest, picture_io.hip) and no host synchronisation; the slots are what hmr_gpu_enc_load_source makes of the
  *     same samples, so every encode call of section 12 takes them.  8-bit 4:2:0 as I420 (three planes) or NV12 (luma plane, plane of interleaved U, V pairs); any base
  *     address, every plane with a byte pitch of its own (at least a row's bytes: width for luma and for NV12's pairs, width / 2 for I420 chroma).  Only the bytes of the
  *     rows are read - [plane + y * pitch, plane + y * pitch + row bytes) - so the last row may end with the caller's allocation.
@@ -732,7 +732,7 @@ int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const int *slots,
  * 12e. Reconstructed pictures and their quality, left in device memory: homer_psnr (hmr_metics.c:53-105, called for every frame at hmr_encoder_lib.c:3350)
  *     The mirror image of 12d.  hmr_gpu_enc_export_pictures_device hands the pictures of n encoders (1 .. 512) to the caller as 8-bit 4:2:0 in DEVICE memory and / or
  *     leaves the exact sums of squared differences between each picture and a picture slot of its encoder in device memory, with ONE launch of a bandwidth-bound
- *     kernel (k_egress.hip) and no host synchronisation.
+ *     kernel (k_egress, picture_io.hip) and no host synchronisation.
  *     "The picture" of an encoder is the final picture (after deblocking and SAO: what the next frame predicts from, what a decoder reconstructs) of the frame its last
  *     encode call encoded: hmr_gpu_enc_encode, _encode_source, _encode_batch, _encode_batch_pipelined (the picture of the frames launched by THAT call - the access
  *     unit arrives a call later, the picture does not; an encoder with an access unit outstanding is accepted here) and _encode_chain (every object of the chain holds

@@ -1,4 +1,4 @@
-"""-m gpu: reconstructed pictures and quality sums left in device memory (include/homer_gpu.h section 12e, csrc/k_egress.hip, homerhevc_amd/encoder.py).  Every
+"""-m gpu: reconstructed pictures and quality sums left in device memory (include/homer_gpu.h section 12e, csrc/picture_io.hip, homerhevc_amd/encoder.py).  Every
 expectation is the compiled reference's: tests/golden/streams.json `recon_md5` for the pictures, tests/golden/quality.json (the sums of squared differences between the
 clip and the reference's own reconstruction, and homer_psnr's values of them) for the sums.  The pictures are exported tightly packed, as I420 planes at odd addresses
 inside larger buffers and as NV12; every byte of the output buffers outside the pictures' rows has to stay what it was."""

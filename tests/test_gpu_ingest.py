@@ -1,4 +1,4 @@
-"""-m gpu: pictures that are already in device memory (include/homer_gpu.h section 12d, csrc/k_ingest.hip, homerhevc_amd/encoder.py).  The clips of the reference's
+"""-m gpu: pictures that are already in device memory (include/homer_gpu.h section 12d, csrc/picture_io.hip, homerhevc_amd/encoder.py).  The clips of the reference's
 fixtures are uploaded with torch - tightly packed I420, I420 planes at odd addresses inside larger tensors, NV12 - and go into the encoders' picture slots by the ingest
 kernel; every stream and every reconstructed picture must be what the compiled reference produced (tests/golden/streams.json)."""
 import ctypes as C
@@ -258,7 +258,7 @@ def test_batch_encoder_class(gpu, pipelined):
 
 def test_refusals_leave_the_encoder_working(gpu):
     """every argument error the host can see without following a pointer is HMR_GPU_ERR_ARG with a text, nothing is launched, and the encoder still produces its fixture's
-    stream.  (Host pointers and freed tensors are deliberately not tried: see the pointer-attribute check in csrc/k_encode_ingest.inc.)"""
+    stream.  (Host pointers and freed tensors are deliberately not tried: see the pointer-attribute check in csrc/k_encode_picture_io.inc.)"""
     import torch
     lib, case = gpu, "416x240_wpp_rows"
     g = GOLD[case]

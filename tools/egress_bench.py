@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU box tool: what the device egress (include/homer_gpu.h section 12e, csrc/k_egress.hip) costs and what it replaces, on bench.py's flagship workload
+"""GPU box tool: what the device egress (include/homer_gpu.h section 12e, k_egress in csrc/picture_io.hip) costs and what it replaces, on bench.py's flagship workload
 (256 sequences of 1920x1080, bench.py's configuration and clips).  Writes profiles/egress_bench.json.
 
     python tools/egress_bench.py [--sequences 256] [--steps 20] [--bench-this FILE ... --bench-parent FILE ...]
@@ -8,7 +8,8 @@
                    in a run of its own (this program starts it as a child, the traced program behind `--`, no counters); bytes from egress_bytes() below.  Yardsticks in
                    the same file: k_ingest re-measured in the same visit by tools/ingest_bench.py's own trace, and the 6.29 TB/s float4 copy.
   replaces         wall time between device synchronisations to leave one 8-bit picture of every sequence in device memory through hmr_gpu_enc_export_references8
-                   (per sequence three launches and a host synchronisation) and through ONE hmr_gpu_enc_export_pictures_device, alternating, five repetitions each
+                   and through ONE hmr_gpu_enc_export_pictures_device, alternating, five repetitions each.  The former runs the same kernel (one picture per launch on the
+                   sequence's own stream): what is left between the two figures is a launch per picture and the host synchronisations
   streaming_step   ms per step of hmr_gpu_enc_encode_batch_pipelined plain and with an export (picture and sums) of every sequence after every step, alternating,
                    three windows each; the condition: median with export <= median plain + egress kernel time + spread of plain
   bench            bench.py's lines of this build and of the parent commit's, when the files are given (all from the same GPU visit, alternating)
@@ -36,7 +37,7 @@ VARIANTS = [("picture", True, False), ("sums", False, True), ("both", True, True
 
 
 def egress_bytes(width, height, picture, sums):
-    """algorithmic bytes of one picture through k_egress (csrc/egress.h hmr_egress_bytes): the final picture is read (int16: 3 W H), the slot's picture is read when
+    """algorithmic bytes of one picture through k_egress (csrc/picture_io.h hmr_egress_bytes): the final picture is read (int16: 3 W H), the slot's picture is read when
     sums are asked for (3 W H), the 8-bit picture is written when one is asked for (1.5 W H)"""
     wh = float(width) * height
     return 3.0 * wh + (3.0 * wh if sums else 0.0) + (1.5 * wh if picture else 0.0)
@@ -111,7 +112,7 @@ def kernel_rate(S):
         traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
         if not traces:
             return {"error": "no kernel trace written", "files": sorted(os.listdir(out))}
-        rows = [r for r in csv.DictReader(open(traces[0])) if "k_egress" in r["Kernel_Name"] and "k_egress_jobs" not in r["Kernel_Name"]]
+        rows = [r for r in csv.DictReader(open(traces[0])) if "k_egress" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows]
     if len(us) != 36:

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""GPU box tool: what the device ingest (include/homer_gpu.h section 12d, csrc/k_ingest.hip) costs and what it replaces, on bench.py's flagship workload
+"""GPU box tool: what the device ingest (include/homer_gpu.h section 12d, k_ingest in csrc/picture_io.hip) costs and what it replaces, on bench.py's flagship workload
 (256 sequences of 1920x1080, bench.py's configuration and clips).  Writes profiles/ingest_bench.json.
 
     python tools/ingest_bench.py [--sequences 256] [--steps 20] [--bench-this FILE --bench-parent FILE]
 
   kernel_rate      k_ingest's time for one launch over all sequences' pictures, I420 and NV12, from `rocprofv3 --kernel-trace --stats` in a run of its own (this
                    program starts it as a child, the traced program behind `--`, no counters); bytes from the formula 1.5 W H read + 3 W H written per picture
-  replaces         wall time to bring one picture of every sequence into a slot through hmr_gpu_enc_load_source (host planes: per plane a copy, a launch and a
-                   synchronise) and through ONE hmr_gpu_enc_load_sources_device, alternating, five repetitions each
+  replaces         wall time to bring one picture of every sequence into a slot through hmr_gpu_enc_load_source (host planes) and through ONE
+                   hmr_gpu_enc_load_sources_device, alternating, five repetitions each.  The host entry runs the same kernel (one picture per launch): what is left
+                   between the two figures is its copies from host memory, a launch and a synchronisation per picture
   streaming_step   ms per step of hmr_gpu_enc_encode_batch_pipelined with the slots preloaded (what bench.py times) and with a fresh device picture ingested for every
                    sequence before every step, alternating, three repetitions each; the condition streaming <= preloaded + kernel time + spread of preloaded
   bench            bench.py's line of this build and of the parent commit's, when the two files are given (both from the same GPU visit)
@@ -119,7 +120,7 @@ def kernel_rate_in(S, out):
     traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
     if not traces:
         return {"error": "no kernel trace written", "files": sorted(os.listdir(out))}
-    rows = [r for r in csv.DictReader(open(traces[0])) if "k_ingest" in r["Kernel_Name"] and "k_ingest_jobs" not in r["Kernel_Name"]]
+    rows = [r for r in csv.DictReader(open(traces[0])) if "k_ingest" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows]
     if len(us) != 12:
