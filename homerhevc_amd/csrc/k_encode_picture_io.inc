@@ -1,5 +1,5 @@
 // Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
-// (include/homer_gpu.h sections 12d and 12e).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_egress (picture_io.hip)
+// (include/homer_gpu.h sections 12d, 12e and 12f).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_egress (picture_io.hip)
 // on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
 //   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
 //   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
@@ -44,9 +44,10 @@ int check_planes(const char *fn, const hmr_gpu_picture *pics, int n, int device)
 }
 }  // namespace
 
-extern "C" int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *pics, void *producer_stream)
+namespace {
+// what the load calls of sections 12d and 12f refuse before they look at a picture
+int check_load(const char *fn, hmr_gpu_enc **encs, int n, const int *slots, const void *pics)
 {
-	static const char *const fn = "hmr_gpu_enc_load_sources_device";
 	static_assert(PICTURE_MAX_JOBS == BATCH_MAX, "a load call feeds a batch call, an export call follows one");
 	if (!encs || !slots || !pics || n < 1 || n > PICTURE_MAX_JOBS) {
 		hmr_set_error("%s: needs 1 .. %d encoders with their slots and pictures (n = %d)", fn, PICTURE_MAX_JOBS, n);
@@ -57,22 +58,19 @@ extern "C" int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const 
 		if (slots[i] < 0 || slots[i] > 4096) return picture_refuse(fn, i, "the slot is outside 0 .. 4096");
 		if (encs[i]->ctx->device != encs[0]->ctx->device) return picture_refuse(fn, i, "the encoder is on another device than the call's first");
 	}
-	{
-		// the same (encoder, slot) twice: two pictures into one slot in one launch would leave a mix of them
-		std::vector<std::pair<hmr_gpu_enc *, int>> seen(n);
-		for (int i = 0; i < n; i++) seen[i] = {encs[i], slots[i]};
-		std::sort(seen.begin(), seen.end());
-		if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) {
-			hmr_set_error("%s: the same encoder and slot twice in one call", fn);
-			return HMR_GPU_ERR_ARG;
-		}
+	// the same (encoder, slot) twice: two pictures into one slot in one launch would leave a mix of them
+	std::vector<std::pair<hmr_gpu_enc *, int>> seen(n);
+	for (int i = 0; i < n; i++) seen[i] = {encs[i], slots[i]};
+	std::sort(seen.begin(), seen.end());
+	if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) {
+		hmr_set_error("%s: the same encoder and slot twice in one call", fn);
+		return HMR_GPU_ERR_ARG;
 	}
-	const int device = encs[0]->ctx->device;
-	int rc;
-	for (int i = 0; i < n; i++)
-		if ((rc = check_descriptor(fn, i, &pics[i], encs[i]))) return rc;
-	HIP_TRY(hipSetDevice(device));
-	if ((rc = check_planes(fn, pics, n, device))) return rc;
+	return HMR_GPU_OK;
+}
+// the slots of a load call exist
+int make_slots(hmr_gpu_enc **encs, int n, const int *slots)
+{
 	for (int i = 0; i < n; i++) {
 		hmr_gpu_enc *e = encs[i];
 		while ((int)e->src.size() <= slots[i]) {
@@ -81,14 +79,34 @@ extern "C" int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const 
 			e->src.push_back(sl);
 		}
 	}
-	std::vector<IngestJob> jobs(n);
-	for (int i = 0; i < n; i++) jobs[i] = ingest_job(encs[i], pics[i], encs[i]->src[slots[i]].p, encs[i]->seq.src_stride_y, encs[i]->seq.src_stride_c);
-	// the pictures are complete when what the producer's stream holds now has run; every other encoder's stream (an encode call starts there: set-up copies, ev_ready)
-	// and the producer's (it may write the pictures again) go on behind the ingest
+	return HMR_GPU_OK;
+}
+// One launch over the jobs of a load call on the first encoder's stream.  The pictures are complete when what the producer's stream holds now has run; every other
+// encoder's stream (an encode call starts there: set-up copies, ev_ready) and the producer's (it may write the pictures again) go on behind the ingest.
+template <class Job>
+int run_load(JobRing<Job> &ring, int (*launch)(hipStream_t, const Job *, Job *, int), hmr_gpu_enc **encs, int n, const Job *jobs, void *producer_stream)
+{
 	hipStream_t producer = (hipStream_t)producer_stream;
 	std::vector<hipStream_t> behind(1, producer);
 	for (int i = 1; i < n; i++) behind.push_back(encs[i]->ctx->stream);
-	return run_jobs(encs[0]->ingest, hmr_ingest_launch, encs[0]->ctx->stream, jobs.data(), n, producer, behind);
+	return run_jobs(ring, launch, encs[0]->ctx->stream, jobs, n, producer, behind);
+}
+}  // namespace
+
+extern "C" int hmr_gpu_enc_load_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *pics, void *producer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_load_sources_device";
+	int rc;
+	if ((rc = check_load(fn, encs, n, slots, pics))) return rc;
+	const int device = encs[0]->ctx->device;
+	for (int i = 0; i < n; i++)
+		if ((rc = check_descriptor(fn, i, &pics[i], encs[i]))) return rc;
+	HIP_TRY(hipSetDevice(device));
+	if ((rc = check_planes(fn, pics, n, device))) return rc;
+	if ((rc = make_slots(encs, n, slots))) return rc;
+	std::vector<IngestJob> jobs(n);
+	for (int i = 0; i < n; i++) jobs[i] = ingest_job(encs[i], pics[i], encs[i]->src[slots[i]].p, encs[i]->seq.src_stride_y, encs[i]->seq.src_stride_c);
+	return run_load(encs[0]->ingest, hmr_ingest_launch, encs, n, jobs.data(), producer_stream);
 }
 
 extern "C" int hmr_gpu_enc_load_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_picture *pic, void *producer_stream)
@@ -162,4 +180,102 @@ extern "C" int hmr_gpu_enc_export_pictures_device(hmr_gpu_enc **encs, int n, con
 extern "C" int hmr_gpu_enc_export_picture_device(hmr_gpu_enc *enc, const hmr_gpu_picture *pic, int slot, uint64_t *dev_ssd, void *consumer_stream)
 {
 	return hmr_gpu_enc_export_pictures_device(&enc, 1, pic, slot >= 0 ? &slot : nullptr, dev_ssd, consumer_stream);
+}
+
+// ---- section 12f: RGB pictures in, the slots' pictures out ----
+extern "C" int hmr_gpu_enc_load_sources_rgb_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_rgb_picture *pics, void *producer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_load_sources_rgb_device";
+	int rc;
+	if ((rc = check_load(fn, encs, n, slots, pics))) return rc;
+	const int device = encs[0]->ctx->device;
+	for (int i = 0; i < n; i++)
+		if (hmr_gpu_rgb_picture_check(&pics[i], encs[i]->seq.width, encs[i]->seq.height) != HMR_GPU_OK) {
+			const std::string why = hmr_gpu_last_error();
+			return picture_refuse(fn, i, why.c_str());
+		}
+	HIP_TRY(hipSetDevice(device));
+	static const char *const names[3] = {"plane[0]", "plane[1]", "plane[2]"};
+	for (int i = 0; i < n; i++)
+		for (int c = 0; c < (pics[i].format == HMR_GPU_RGB_PACKED8 ? 1 : 3); c++)
+			if (!on_device(pics[i].plane[c], device)) return not_device(fn, i, names[c], device);
+	if ((rc = make_slots(encs, n, slots))) return rc;
+	std::vector<RgbIngestJob> jobs(n);
+	for (int i = 0; i < n; i++) {
+		const hmr_gpu_enc *e = encs[i];
+		const hmr_gpu_rgb_picture &pic = pics[i];
+		RgbIngestJob &j = jobs[i];
+		memset(&j, 0, sizeof j);
+		for (int c = 0; c < 3; c++) {
+			j.src[c] = (const uint8_t *)pic.plane[c];
+			j.pitch[c] = pic.pitch[c];
+			j.dst[c] = e->src[slots[i]].p[c];
+			j.offset[c] = pic.offset[c];
+		}
+		j.stride_y = e->seq.src_stride_y; j.stride_c = e->seq.src_stride_c;
+		j.width = e->seq.width; j.height = e->seq.height;
+		j.format = pic.format; j.pixel_bytes = pic.pixel_bytes;
+		j.m = hmr_rgb_matrix(pic.matrix, pic.full_range);
+	}
+	return run_load(encs[0]->ingest_rgb, hmr_ingest_rgb_launch, encs, n, jobs.data(), producer_stream);
+}
+
+extern "C" int hmr_gpu_enc_load_source_rgb_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_rgb_picture *pic, void *producer_stream)
+{
+	return hmr_gpu_enc_load_sources_rgb_device(&enc, 1, &slot, pic, producer_stream);
+}
+
+extern "C" int hmr_gpu_enc_export_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *outs, void *consumer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_export_sources_device";
+	if (!encs || !slots || !outs || n < 1 || n > PICTURE_MAX_JOBS) {
+		hmr_set_error("%s: needs 1 .. %d encoders with their slots and output pictures (n = %d)", fn, PICTURE_MAX_JOBS, n);
+		return HMR_GPU_ERR_ARG;
+	}
+	int rc;
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		if (!e) return picture_refuse(fn, i, "the encoder is NULL");
+		if (e->ctx->device != encs[0]->ctx->device) return picture_refuse(fn, i, "the encoder is on another device than the call's first");
+		if (slots[i] < 0 || slots[i] >= (int)e->src.size()) return picture_refuse(fn, i, "the slot does not exist");
+		if ((rc = check_descriptor(fn, i, &outs[i], e))) return rc;
+	}
+	const int device = encs[0]->ctx->device;
+	HIP_TRY(hipSetDevice(device));
+	if ((rc = check_planes(fn, outs, n, device))) return rc;
+	// k_egress with the slot's planes and strides in place of the final picture's, and no sums
+	std::vector<EgressJob> jobs(n);
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		EgressJob &j = jobs[i];
+		j = egress_job(e, &outs[i], nullptr, nullptr);
+		for (int c = 0; c < 3; c++) j.rec[c] = e->src[slots[i]].p[c];
+		j.stride_y = e->seq.src_stride_y; j.stride_c = e->seq.src_stride_c;
+	}
+	hipStream_t st = encs[0]->ctx->stream, consumer = (hipStream_t)consumer_stream;
+	// behind the consumer (its work on the output memory: run_jobs) and behind what the encoders' own streams hold (a load into the slot waits there); the consumer
+	// reads the output behind the egress, a later load rewrites the slot: those streams go on behind it
+	auto behind_the_loads = [&](std::vector<hipStream_t> &behind) -> int {
+		std::unordered_set<hipStream_t> seen = {consumer, st};
+		for (int i = 0; i < n; i++) {
+			hmr_gpu_enc *e = encs[i];
+			if (!seen.insert(e->ctx->stream).second) continue;
+			behind.push_back(e->ctx->stream);
+			if (hipStreamQuery(e->ctx->stream) == hipSuccess) continue;      // (nothing in flight: nothing to queue behind, as in the export of the final pictures)
+			(void)hipGetLastError();
+			if (!e->ev_pic_done) {
+				HIP_TRY(hipEventCreateWithFlags(&e->ev_pic_done, hipEventDisableTiming));
+				HIP_TRY(hipEventCreateWithFlags(&e->ev_own_done, hipEventDisableTiming));
+			}
+			HIP_TRY(hipEventRecord(e->ev_own_done, e->ctx->stream));
+			HIP_TRY(hipStreamWaitEvent(st, e->ev_own_done, 0));
+		}
+		return HMR_GPU_OK;
+	};
+	return run_jobs(encs[0]->egress, hmr_egress_launch, st, jobs.data(), n, consumer, std::vector<hipStream_t>(1, consumer), behind_the_loads);
+}
+
+extern "C" int hmr_gpu_enc_export_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_picture *out, void *consumer_stream)
+{
+	return hmr_gpu_enc_export_sources_device(&enc, 1, &slot, out, consumer_stream);
 }

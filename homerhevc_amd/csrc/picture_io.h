@@ -1,5 +1,6 @@
 // Picture conversion on the device (picture_io.hip): 8-bit 4:2:0 pictures in device memory <-> the int16 planes of the frame encoder, a batch of pictures per launch.
-// Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture).  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
+// Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture); RGB pictures (8-bit packed or planar, binary16, binary32) -> the same planes, colour
+// converted in the same pass (rgb_yuv.h).  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
 // squared differences against the int16 source planes of a picture slot.  A launch reads its pictures from a job table; JobRing holds the tables of one encoder and
 // run_jobs queues one launch, ordered against the caller's stream by events (k_encode_picture_io.inc and the host-memory entries of k_encode_object.inc use it).
 #pragma once
@@ -7,6 +8,7 @@
 #include <functional>
 #include <vector>
 #include "common.h"
+#include "rgb_yuv.h"
 
 #define PICTURE_MAX_JOBS 512         // pictures per launch (the batch calls' limit)
 #define PICTURE_RING 4               // job tables of one direction in flight
@@ -33,6 +35,28 @@ struct EgressJob {
 	int32_t width, height, format, reserved;
 };
 
+// one picture of an RGB ingest launch (k_ingest_rgb): the caller's RGB picture into the int16 planes, colour-converted by rgb_yuv.h's arithmetic
+struct RgbIngestJob {
+	const uint8_t *src[3];       // HMR_GPU_RGB_PACKED8: src[0] alone; planar: R, G, B
+	int64_t pitch[3];            // bytes from row to row
+	int16_t *dst[3];             // the planes at sample (0, 0); 16-byte aligned
+	int32_t stride_y, stride_c;  // elements, multiples of 8
+	int32_t width, height, format, pixel_bytes;
+	int32_t offset[3];           // PACKED8: byte of R, G, B inside a pixel
+	RgbMatrix m;                 // the nine coefficients and yoff: a launch mixes matrices and ranges
+	int32_t reserved[3];
+};
+static_assert(sizeof(RgbIngestJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
+
+// Algorithmic bytes of one width x height picture through k_ingest_rgb (tools/rgb_ingest_bench.py restates it): every sample of the source is read once -
+// 3 or 4 bytes per pixel packed, 3 planar 8-bit, 6 planar binary16, 12 planar binary32 - and the int16 Y, U, V planes are written: 4 W H in every case.
+static inline double hmr_ingest_rgb_bytes(int width, int height, int format, int pixel_bytes)
+{
+	const double wh = (double)width * height;
+	const double read = format == HMR_GPU_RGB_PACKED8 ? pixel_bytes : format == HMR_GPU_RGB_PLANAR8 ? 3 : format == HMR_GPU_RGB_PLANAR_F16 ? 6 : 12;
+	return (read + 4.0) * wh;
+}
+
 // Algorithmic bytes of one width x height picture through k_egress (tools/egress_bench.py restates it): the final picture is read, the slot's picture is read
 // when sums are asked for, the 8-bit picture is written when one is asked for.
 static inline double hmr_egress_bytes(int width, int height, int picture, int sums)
@@ -42,9 +66,10 @@ static inline double hmr_egress_bytes(int width, int height, int picture, int su
 }
 
 // The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of k_ingest /
-// k_egress handles all n pictures; both on `stream`, nothing is waited for.
+// k_ingest_rgb / k_egress handles all n pictures; both on `stream`, nothing is waited for.
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n);
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n);
+int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n);
 
 // The job tables of the calls one encoder leads, in one direction: a ring of tables in page-locked memory (a table is written again only when the launch that read it
 // is known to be over: ev_turn), their copy on the device, the events towards the outside stream (producer or consumer) and towards the streams that go on behind a launch.

@@ -8,6 +8,13 @@
 // int16 source planes of a picture slot.  Per picture 3 W H bytes read (final picture), 3 W H read (slot, when sums are asked for), 1.5 W H written (when a picture is
 // asked for) - hmr_egress_bytes in picture_io.h.
 //
+// k_ingest_rgb (section 12f): RGB pictures - packed 8-bit with 3 or 4 bytes per pixel and any channel order, planar 8-bit, planar binary16, planar binary32 - into the same
+// int16 planes, converted to 4:2:0 Y'CbCr by the integer arithmetic of rgb_yuv.h in the same pass.  3, 4, 3, 6 or 12 W H bytes read, 4 W H written per picture
+// (hmr_ingest_rgb_bytes in picture_io.h).  blockIdx.y = picture, blockIdx.x = a chunk of CHUNK_ROWS luma rows = CHUNK_ROWS / 2 chroma rows; a lane takes a span of 16
+// pixels of TWO adjacent rows, so the 2 x 2 sums of the chroma samples never leave the lane: 16-byte loads at whatever address the pitch gives (per row: three for
+// 3-byte pixels, four for 4-byte pixels, one per plane for planar 8-bit, two / four per plane for binary16 / binary32), channels picked by v_alignbyte_b32 / v_bfe_u32 with
+// the job's byte offsets, four 16-byte stores of int16 luma and one each of eight U and eight V samples.  A row's tail of fewer than 16 pixels goes sample by sample, a lane per 2 x 2 block.
+//
 // Mapping (struct Chunk): blockIdx.y = picture (a record of the job table), blockIdx.x = a chunk of CHUNK_ROWS rows of it - first the luma rows, then the chroma rows (a
 // chroma row is its U and its V part: as many 8-bit bytes as a luma row) - so that one grid covers the three planes of every picture; pictures smaller than the largest
 // of the launch leave their last chunks empty.  A lane takes a span of 16 samples.  Ingest: one 16-byte load, two 16-byte stores of int16; NV12 chroma: one 16-byte load
@@ -142,6 +149,196 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ingest(const IngestJob *jobs)
 	}
 }
 
+// ---- RGB ingest ----
+// a sample of an RGB picture as 8 bits: `plane` is the packed plane or the channel's own; host and device pointers alike (hmr_gpu_rgb_convert_host, a row's tail)
+template <class Bytes, class Halves, class Floats>
+__host__ __device__ __forceinline__ int rgb_sample(Bytes plane, int64_t pitch, int format, int pixel_bytes, int offset, int x, int y)
+{
+	const Bytes row = plane + (int64_t)y * pitch;
+	switch (format) {
+	case HMR_GPU_RGB_PACKED8: return row[x * pixel_bytes + offset];
+	case HMR_GPU_RGB_PLANAR8: return row[x];
+	case HMR_GPU_RGB_PLANAR_F16: return hmr_rgb_quantize((float)((Halves)row)[x]);
+	default: return hmr_rgb_quantize(((Floats)row)[x]);
+	}
+}
+
+// The forms a span is read in (a launch mixes them: one per picture).  PX pixels of a row are held as raw dwords: packed - the row's bytes as they lie; planar - PX
+// samples of R, then of G, then of B.
+enum { RGB_PACKED3, RGB_PACKED4, RGB_PLANAR8, RGB_F16, RGB_F32 };
+template <int V> struct RgbForm {
+	static constexpr int PX = V == RGB_F32 ? 8 : 16;      // pixels read at a time (binary32: half a span, 96 bytes a row)
+	static constexpr int PLANE = V == RGB_PLANAR8 ? PX / 4 : V == RGB_F16 ? PX / 2 : PX;      // dwords per channel (planar)
+	static constexpr int WORDS = V == RGB_PACKED3 ? 3 * PX / 4 : V == RGB_PACKED4 ? PX : 3 * PLANE;
+};
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+template <int V>
+__device__ __forceinline__ void rgb_load_row(const RgbIngestJob &j, int x, int y, uint32_t *raw)
+{
+	typedef RgbForm<V> F;
+	if (V == RGB_PACKED3 || V == RGB_PACKED4) {
+		const bytes_in s = (bytes_in)j.src[0] + (int64_t)y * j.pitch[0] + (int64_t)x * (V == RGB_PACKED3 ? 3 : 4);
+#pragma unroll
+		for (int k = 0; k < F::WORDS / 4; k++) {
+			const u32x4 v = load16(s + 16 * k);
+			raw[4 * k] = v.x; raw[4 * k + 1] = v.y; raw[4 * k + 2] = v.z; raw[4 * k + 3] = v.w;
+		}
+		return;
+	}
+	constexpr int elem = V == RGB_PLANAR8 ? 1 : V == RGB_F16 ? 2 : 4;
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		const bytes_in s = (bytes_in)j.src[c] + (int64_t)y * j.pitch[c] + (int64_t)x * elem;
+#pragma unroll
+		for (int k = 0; k < F::PLANE / 4; k++) {
+			const u32x4 v = load16(s + 16 * k);
+			uint32_t *o = raw + c * F::PLANE + 4 * k;
+			o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+		}
+	}
+}
+
+// R, G, B of pixel i of a row's raw dwords; sh[c] = 8 * offset[c] (packed)
+template <int V>
+__device__ __forceinline__ void rgb_pixel(const uint32_t *raw, int i, const int sh[3], int &r, int &g, int &b)
+{
+	typedef RgbForm<V> F;
+	if (V == RGB_PACKED3 || V == RGB_PACKED4) {
+		uint32_t w;
+		if (V == RGB_PACKED4) w = raw[i];
+		else {
+			const int d = (3 * i) >> 2, s = (3 * i) & 3;      // the pixel's three bytes start at byte s of dword d
+			w = s ? __builtin_amdgcn_alignbyte(d + 1 < F::WORDS ? raw[d + 1] : 0u, raw[d], (uint32_t)s) : raw[d];
+		}
+		r = (int)((w >> sh[0]) & 255u); g = (int)((w >> sh[1]) & 255u); b = (int)((w >> sh[2]) & 255u);
+		return;
+	}
+	const uint32_t *pr = raw, *pg = raw + F::PLANE, *pb = raw + 2 * F::PLANE;
+	if (V == RGB_PLANAR8) {
+		const int d = i >> 2, s = 8 * (i & 3);
+		r = (int)((pr[d] >> s) & 255u); g = (int)((pg[d] >> s) & 255u); b = (int)((pb[d] >> s) & 255u);
+	} else if (V == RGB_F16) {
+		const int d = i >> 1;
+		const f16x2 hr = __builtin_bit_cast(f16x2, pr[d]), hg = __builtin_bit_cast(f16x2, pg[d]), hb = __builtin_bit_cast(f16x2, pb[d]);
+		r = hmr_rgb_quantize((float)((i & 1) ? hr.y : hr.x)); g = hmr_rgb_quantize((float)((i & 1) ? hg.y : hg.x)); b = hmr_rgb_quantize((float)((i & 1) ? hb.y : hb.x));
+	} else {
+		r = hmr_rgb_quantize(__builtin_bit_cast(float, pr[i])); g = hmr_rgb_quantize(__builtin_bit_cast(float, pg[i])); b = hmr_rgb_quantize(__builtin_bit_cast(float, pb[i]));
+	}
+}
+
+// pixels i0 .. i0 + 7 of two adjacent rows a, b: eight luma samples of each row and four U and four V samples, as int16 pairs
+template <int V>
+__device__ __forceinline__ void rgb_convert8(const uint32_t *a, const uint32_t *b, int i0, const RgbMatrix &m, const int sh[3], u32x4 &ya, u32x4 &yb, uint32_t *u, uint32_t *v)
+{
+	uint32_t la[4], lb[4], cu[4], cv[4];
+#pragma unroll
+	for (int p = 0; p < 4; p++) {
+		int r0, g0, b0, r1, g1, b1, r2, g2, b2, r3, g3, b3;
+		rgb_pixel<V>(a, i0 + 2 * p, sh, r0, g0, b0);
+		rgb_pixel<V>(a, i0 + 2 * p + 1, sh, r1, g1, b1);
+		rgb_pixel<V>(b, i0 + 2 * p, sh, r2, g2, b2);
+		rgb_pixel<V>(b, i0 + 2 * p + 1, sh, r3, g3, b3);
+		la[p] = (uint32_t)hmr_rgb_luma(m, r0, g0, b0) | (uint32_t)hmr_rgb_luma(m, r1, g1, b1) << 16;
+		lb[p] = (uint32_t)hmr_rgb_luma(m, r2, g2, b2) | (uint32_t)hmr_rgb_luma(m, r3, g3, b3) << 16;
+		const int sr = r0 + r1 + r2 + r3, sg = g0 + g1 + g2 + g3, sb = b0 + b1 + b2 + b3;
+		cu[p] = (uint32_t)hmr_rgb_chroma(m.u, sr, sg, sb);
+		cv[p] = (uint32_t)hmr_rgb_chroma(m.v, sr, sg, sb);
+	}
+	ya = u32x4{la[0], la[1], la[2], la[3]};
+	yb = u32x4{lb[0], lb[1], lb[2], lb[3]};
+	u[0] = cu[0] | cu[1] << 16; u[1] = cu[2] | cu[3] << 16;
+	v[0] = cv[0] | cv[1] << 16; v[1] = cv[2] | cv[3] << 16;
+}
+
+// 16 pixels at (x, y) of rows y and y + 1 (x a multiple of 16, y even): 32 luma samples, 8 U and 8 V samples
+template <int V>
+__device__ __forceinline__ void rgb_span(const RgbIngestJob &j, int x, int y, const int sh[3])
+{
+	typedef RgbForm<V> F;
+	u32x4 ya[2], yb[2];
+	uint32_t u[4], v[4];
+	if (F::PX == 8) {
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			uint32_t a[F::WORDS], b[F::WORDS];
+			rgb_load_row<V>(j, x + 8 * h, y, a);
+			rgb_load_row<V>(j, x + 8 * h, y + 1, b);
+			rgb_convert8<V>(a, b, 0, j.m, sh, ya[h], yb[h], u + 2 * h, v + 2 * h);
+		}
+	} else {
+		uint32_t a[F::WORDS], b[F::WORDS];
+		rgb_load_row<V>(j, x, y, a);
+		rgb_load_row<V>(j, x, y + 1, b);
+#pragma unroll
+		for (int h = 0; h < 2; h++) rgb_convert8<V>(a, b, 8 * h, j.m, sh, ya[h], yb[h], u + 2 * h, v + 2 * h);
+	}
+	GLOBAL_AS u32x4 *oa = (GLOBAL_AS u32x4 *)((samples_out)j.dst[0] + (size_t)y * j.stride_y + x), *ob = (GLOBAL_AS u32x4 *)((samples_out)j.dst[0] + (size_t)(y + 1) * j.stride_y + x);
+	oa[0] = ya[0]; oa[1] = ya[1];
+	ob[0] = yb[0]; ob[1] = yb[1];
+	const size_t oc = (size_t)(y >> 1) * j.stride_c + (x >> 1);
+	*(GLOBAL_AS u32x4 *)((samples_out)j.dst[1] + oc) = u32x4{u[0], u[1], u[2], u[3]};
+	*(GLOBAL_AS u32x4 *)((samples_out)j.dst[2] + oc) = u32x4{v[0], v[1], v[2], v[3]};
+}
+
+// the 2 x 2 block at (bx, y) of a picture of format FMT, sample by sample (a row's tail)
+template <int FMT>
+__device__ __forceinline__ void rgb_block(const RgbIngestJob &j, int bx, int y)
+{
+	const samples_out dy = (samples_out)j.dst[0];
+	constexpr bool packed = FMT == HMR_GPU_RGB_PACKED8;
+	int s[3] = {0, 0, 0};
+#pragma unroll
+	for (int k = 0; k < 4; k++) {
+		const int px = bx + (k & 1), py = y + (k >> 1);
+		int c3[3];
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			c3[c] = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[packed ? 0 : c], j.pitch[packed ? 0 : c], FMT, j.pixel_bytes, j.offset[c], px, py);
+			s[c] += c3[c];
+		}
+		dy[(size_t)py * j.stride_y + px] = (int16_t)hmr_rgb_luma(j.m, c3[0], c3[1], c3[2]);
+	}
+	const size_t oc = (size_t)(y >> 1) * j.stride_c + (bx >> 1);
+	((samples_out)j.dst[1])[oc] = (int16_t)hmr_rgb_chroma(j.m.u, s[0], s[1], s[2]);
+	((samples_out)j.dst[2])[oc] = (int16_t)hmr_rgb_chroma(j.m.v, s[0], s[1], s[2]);
+}
+
+// the rows y0 .. of a picture read in form V (format FMT): whole spans, then the row's tail of fewer than 16 pixels, a lane per 2 x 2 block
+template <int V, int FMT>
+__device__ __forceinline__ void rgb_chunk(const RgbIngestJob &j, int y0)
+{
+	const int left = j.height - y0, pairs = (left < CHUNK_ROWS ? left : CHUNK_ROWS) >> 1, per_row = j.width >> 4;      // (whole spans)
+	const int sh[3] = {8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]};
+	for (int i = (int)threadIdx.x; i < pairs * per_row; i += HMR_BLOCK) {
+		const int r = i / per_row, x = (i - r * per_row) << 4, y = y0 + 2 * r;
+		rgb_span<V>(j, x, y, sh);
+	}
+	const int tail = (j.width & 15) >> 1;
+	for (int i = (int)threadIdx.x; i < pairs * tail; i += HMR_BLOCK) {
+		const int r = i / tail;
+		rgb_block<FMT>(j, (j.width & ~15) + 2 * (i - r * tail), y0 + 2 * r);
+	}
+}
+
+__host__ __device__ __forceinline__ int rgb_chunks(int height) { return (height + CHUNK_ROWS - 1) / CHUNK_ROWS; }
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_ingest_rgb(const RgbIngestJob *jobs)
+{
+	const RgbIngestJob j = jobs[blockIdx.y];
+	const int y0 = (int)blockIdx.x * CHUNK_ROWS;
+	if (y0 >= j.height) return;
+	switch (j.format) {
+	case HMR_GPU_RGB_PACKED8:
+		if (j.pixel_bytes == 3) rgb_chunk<RGB_PACKED3, HMR_GPU_RGB_PACKED8>(j, y0);
+		else rgb_chunk<RGB_PACKED4, HMR_GPU_RGB_PACKED8>(j, y0);
+		break;
+	case HMR_GPU_RGB_PLANAR8: rgb_chunk<RGB_PLANAR8, HMR_GPU_RGB_PLANAR8>(j, y0); break;
+	case HMR_GPU_RGB_PLANAR_F16: rgb_chunk<RGB_F16, HMR_GPU_RGB_PLANAR_F16>(j, y0); break;
+	default: rgb_chunk<RGB_F32, HMR_GPU_RGB_PLANAR_F32>(j, y0); break;
+	}
+}
+
 // ---- egress ----
 // two dwords of two int16 samples each -> their four low bytes
 __device__ __forceinline__ uint32_t pack4(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x06040200u); }
@@ -271,13 +468,17 @@ __global__ __launch_bounds__(64) void k_picture_jobs(const uint32_t *h_jobs, uin
 	for (int k = threadIdx.x; k < words; k += blockDim.x) d_jobs[blockIdx.x * words + k] = h_jobs[blockIdx.x * words + k];
 }
 
+inline int chunks_of(const IngestJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
+inline int chunks_of(const EgressJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
+inline int chunks_of(const RgbIngestJob &j) { return rgb_chunks(j.height); }
+
 template <class Job>
 int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n)
 {
 	static_assert(sizeof(Job) % 4 == 0, "word copies");
 	if (!h_jobs || !d_jobs || n < 1 || n > PICTURE_MAX_JOBS) return HMR_GPU_ERR_ARG;
 	int chunks = 0;      // of the tallest picture
-	for (int i = 0; i < n; i++) chunks = std::max(chunks, Chunk{0, h_jobs[i].width, h_jobs[i].height}.chunks());
+	for (int i = 0; i < n; i++) chunks = std::max(chunks, chunks_of(h_jobs[i]));
 	hipLaunchKernelGGL(k_picture_jobs, dim3(n), dim3(64), 0, stream, (const uint32_t *)h_jobs, (uint32_t *)d_jobs, (int)(sizeof(Job) / 4));
 	hipLaunchKernelGGL(kernel, dim3(chunks, n), dim3(HMR_BLOCK), 0, stream, (const Job *)d_jobs);
 	HIP_TRY(hipGetLastError());
@@ -287,6 +488,7 @@ int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, J
 
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n) { return launch(k_ingest, stream, h_jobs, d_jobs, n); }
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n) { return launch(k_egress, stream, h_jobs, d_jobs, n); }
+int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n) { return launch(k_ingest_rgb, stream, h_jobs, d_jobs, n); }
 
 static int refuse(const char *what)
 {
@@ -312,6 +514,89 @@ extern "C" int hmr_gpu_picture_check(const hmr_gpu_picture *pic, int width, int 
 		if (pic->pitch[c] < row_bytes) return refuse(narrow[c]);
 	}
 	if (planes == 2 && pic->plane[2]) return refuse("plane[2]: must be NULL for NV12 (plane[1] holds the U, V pairs)");
+	return HMR_GPU_OK;
+}
+
+static int refuse_rgb(const char *what)
+{
+	hmr_set_error("hmr_gpu_rgb_picture: %s", what);
+	return HMR_GPU_ERR_ARG;
+}
+// an RGB descriptor against a picture size, on the host alone
+extern "C" int hmr_gpu_rgb_picture_check(const hmr_gpu_rgb_picture *pic, int width, int height)
+{
+	if (!pic) return refuse_rgb("the descriptor is NULL");
+	if (pic->format < HMR_GPU_RGB_PACKED8 || pic->format > HMR_GPU_RGB_PLANAR_F32) return refuse_rgb("format: not one of HMR_GPU_RGB_PACKED8, _PLANAR8, _PLANAR_F16, _PLANAR_F32");
+	if (pic->matrix != HMR_GPU_MATRIX_BT601 && pic->matrix != HMR_GPU_MATRIX_BT709) return refuse_rgb("matrix: neither HMR_GPU_MATRIX_BT601 nor HMR_GPU_MATRIX_BT709");
+	if (pic->full_range != 0 && pic->full_range != 1) return refuse_rgb("full_range: must be 0 or 1");
+	if (pic->reserved != 0) return refuse_rgb("reserved: must be 0");
+	if (width <= 0 || (width & 1)) return refuse_rgb("width: must be positive and even");
+	if (height <= 0 || (height & 1)) return refuse_rgb("height: must be positive and even");
+	const bool packed = pic->format == HMR_GPU_RGB_PACKED8;
+	static const char *const offset_range[3] = {"offset[0]: outside 0 .. pixel_bytes - 1", "offset[1]: outside 0 .. pixel_bytes - 1", "offset[2]: outside 0 .. pixel_bytes - 1"};
+	static const char *const offset_zero[3] = {"offset[0]: must be 0 for a planar format", "offset[1]: must be 0 for a planar format", "offset[2]: must be 0 for a planar format"};
+	if (packed) {
+		if (pic->pixel_bytes != 3 && pic->pixel_bytes != 4) return refuse_rgb("pixel_bytes: must be 3 or 4 for HMR_GPU_RGB_PACKED8");
+		for (int c = 0; c < 3; c++)
+			if (pic->offset[c] < 0 || pic->offset[c] >= pic->pixel_bytes) return refuse_rgb(offset_range[c]);
+		if (pic->offset[1] == pic->offset[0]) return refuse_rgb("offset[1]: the same byte as offset[0]");
+		if (pic->offset[2] == pic->offset[0] || pic->offset[2] == pic->offset[1]) return refuse_rgb("offset[2]: the same byte as another channel's");
+	} else {
+		if (pic->pixel_bytes != 0) return refuse_rgb("pixel_bytes: must be 0 for a planar format");
+		for (int c = 0; c < 3; c++)
+			if (pic->offset[c] != 0) return refuse_rgb(offset_zero[c]);
+	}
+	const int elem = packed ? pic->pixel_bytes : pic->format == HMR_GPU_RGB_PLANAR8 ? 1 : pic->format == HMR_GPU_RGB_PLANAR_F16 ? 2 : 4;
+	const int align = packed ? 1 : elem;
+	static const char *const missing[3] = {"plane[0]: NULL", "plane[1]: NULL", "plane[2]: NULL"};
+	static const char *const extra[3] = {"", "plane[1]: must be NULL for HMR_GPU_RGB_PACKED8 (plane[0] holds the pixels)", "plane[2]: must be NULL for HMR_GPU_RGB_PACKED8 (plane[0] holds the pixels)"};
+	static const char *const negative[3] = {"pitch[0]: negative", "pitch[1]: negative", "pitch[2]: negative"};
+	static const char *const narrow[3] = {"pitch[0]: less than a row's bytes (width x pixel_bytes, or width x the element size)", "pitch[1]: less than a row's bytes (width x the element size)",
+					      "pitch[2]: less than a row's bytes (width x the element size)"};
+	static const char *const plane_align[3] = {"plane[0]: not a multiple of the element size", "plane[1]: not a multiple of the element size", "plane[2]: not a multiple of the element size"};
+	static const char *const pitch_align[3] = {"pitch[0]: not a multiple of the element size", "pitch[1]: not a multiple of the element size", "pitch[2]: not a multiple of the element size"};
+	for (int c = 0; c < 3; c++) {
+		if (packed && c) {
+			if (pic->plane[c]) return refuse_rgb(extra[c]);
+			continue;
+		}
+		if (!pic->plane[c]) return refuse_rgb(missing[c]);
+		if (pic->pitch[c] < 0) return refuse_rgb(negative[c]);
+		if (pic->pitch[c] < (int64_t)width * elem) return refuse_rgb(narrow[c]);
+		if ((uintptr_t)pic->plane[c] % align) return refuse_rgb(plane_align[c]);
+		if (pic->pitch[c] % align) return refuse_rgb(pitch_align[c]);
+	}
+	return HMR_GPU_OK;
+}
+
+// rgb_yuv.h's arithmetic over host memory: the loop a caller would write from the header's formulas
+extern "C" int hmr_gpu_rgb_convert_host(const hmr_gpu_rgb_picture *pic, int width, int height, uint8_t *y, uint8_t *u, uint8_t *v)
+{
+	const int rc = hmr_gpu_rgb_picture_check(pic, width, height);
+	if (rc) return rc;
+	if (!y || !u || !v) {
+		hmr_set_error("hmr_gpu_rgb_convert_host: needs the three output planes");
+		return HMR_GPU_ERR_ARG;
+	}
+	const RgbMatrix m = hmr_rgb_matrix(pic->matrix, pic->full_range);
+	const bool packed = pic->format == HMR_GPU_RGB_PACKED8;
+	for (int by = 0; by < height; by += 2)
+		for (int bx = 0; bx < width; bx += 2) {
+			int s[3] = {0, 0, 0};
+			for (int k = 0; k < 4; k++) {
+				const int px = bx + (k & 1), py = by + (k >> 1);
+				int c3[3];
+				for (int c = 0; c < 3; c++) {
+					c3[c] = rgb_sample<const uint8_t *, const _Float16 *, const float *>((const uint8_t *)pic->plane[packed ? 0 : c], pic->pitch[packed ? 0 : c], pic->format, pic->pixel_bytes,
+													      pic->offset[c], px, py);
+					s[c] += c3[c];
+				}
+				y[(size_t)py * width + px] = (uint8_t)hmr_rgb_luma(m, c3[0], c3[1], c3[2]);
+			}
+			const size_t oc = (size_t)(by >> 1) * (width >> 1) + (bx >> 1);
+			u[oc] = (uint8_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
+			v[oc] = (uint8_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
+		}
 	return HMR_GPU_OK;
 }
 

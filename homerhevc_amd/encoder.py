@@ -4,11 +4,14 @@
     enc = Encoder(cfg)
     au, slice_type = enc.encode(frame)          # frame: a uint8 CUDA tensor [H * 3 // 2, W] (I420), or a tuple of plane tensors
 
+    au, slice_type = enc.encode(RGBFrame(rgb))  # rgb: a [3, H, W] tensor (uint8, or float16 / float32 in 0 .. 1) or packed uint8 [H, W, 3 or 4]; BT.709 limited range
+    yuv = enc.source()                          # the 4:2:0 picture that frame was encoded from, as a uint8 CUDA tensor
+
     rec, ssd = enc.export(ssd=True)             # the reconstructed picture as a uint8 CUDA tensor, the sums of squared differences to `frame` as int64 [3]
     y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d and 12e).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), both
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e and 12f).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), both
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
@@ -17,6 +20,9 @@ import ctypes as C
 from .build import LIB_PATH
 
 PIC_I420, PIC_NV12 = 0, 1
+RGB_PACKED8, RGB_PLANAR8, RGB_PLANAR_F16, RGB_PLANAR_F32 = 0, 1, 2, 3
+MATRICES = {"bt601": 0, "bt709": 1}
+ORDERS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0)), "argb": (4, (1, 2, 3)), "abgr": (4, (3, 2, 1))}      # pixel bytes, byte of R, G, B
 SLICE_P, SLICE_I = 1, 2
 IMAGE_AUTO, IMAGE_I = 0, 3          # encoder_in_out_t.image_type
 
@@ -49,6 +55,59 @@ class EncoderConfig(C.Structure):
 class Picture(C.Structure):
     """hmr_gpu_picture"""
     _fields_ = [("format", C.c_int32), ("reserved", C.c_int32), ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3)]
+
+
+class RgbPicture(C.Structure):
+    """hmr_gpu_rgb_picture"""
+    _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32), ("reserved", C.c_int32), ("pixel_bytes", C.c_int32), ("offset", C.c_int32 * 3),
+                ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3)]
+
+
+class RGBFrame:
+    """An RGB picture for Encoder.encode / BatchEncoder.step: converted to 8-bit 4:2:0 by the ingest kernel itself, in the integer arithmetic of include/homer_gpu.h section
+    12f (every sample can be reproduced from the table there; hmr_gpu_rgb_convert_host is the same arithmetic on the host).
+      tensor: a uint8 CUDA tensor [H, W, 3] or [H, W, 4], packed: unit stride over the channels, a pixel every 3 / 4 bytes, any row stride - `order` names the bytes of a
+              pixel: "rgb", "bgr" (3 bytes), "rgba", "bgra", "argb", "abgr" (4 bytes; the alpha byte is ignored);
+              or a [3, H, W] tensor of uint8, float16 or float32 (R, G, B planes; floats are clamped to 0 .. 1 and scaled by 255, NaN counts as 0) with unit stride along
+              a row - views and channel slices of larger tensors are fine, `order` is ignored.
+      matrix: "bt709" or "bt601"; full_range: False for 16 .. 235 / 16 .. 240, True for 0 .. 255.
+    The stream does NOT say which matrix or range was used (the parameter sets carry no colour description, as the reference's): tell the decoder's side by other means."""
+
+    def __init__(self, tensor, order="rgb", matrix="bt709", full_range=False):
+        if matrix not in MATRICES:
+            raise ValueError(f"RGBFrame: matrix has to be one of {sorted(MATRICES)}, got {matrix!r}")
+        if order not in ORDERS:
+            raise ValueError(f"RGBFrame: order has to be one of {sorted(ORDERS)}, got {order!r}")
+        self.tensor, self.order, self.matrix, self.full_range = tensor, order, matrix, bool(full_range)
+
+
+def rgb_picture_of(frame, width, height):
+    """The descriptor (hmr_gpu_rgb_picture) of a width x height RGBFrame; nothing is copied, the tensor's strides become the pitches.  Returns (RgbPicture, tensors): keep
+    the tensors until the load call that takes the descriptor has returned."""
+    import torch
+    w, h, t = int(width), int(height), frame.tensor
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 3:
+        raise TypeError("rgb_picture_of: the frame has to be a three-dimensional CUDA tensor")
+    pic = RgbPicture(matrix=MATRICES[frame.matrix], full_range=int(frame.full_range), reserved=0)
+    if tuple(t.shape[:2]) == (h, w) and t.shape[2] in (3, 4) and t.dtype == torch.uint8 and tuple(t.shape) != (3, h, w):
+        pixel_bytes, offsets = ORDERS[frame.order]
+        if pixel_bytes != t.shape[2]:
+            raise ValueError(f"rgb_picture_of: order {frame.order!r} names {pixel_bytes} bytes a pixel, the tensor has {t.shape[2]}")
+        if t.stride(2) != 1 or t.stride(1) != pixel_bytes:
+            raise ValueError(f"rgb_picture_of: a packed frame has to have unit stride over the channels and a pixel every {pixel_bytes} bytes, got strides {t.stride()}")
+        pic.format, pic.pixel_bytes = RGB_PACKED8, pixel_bytes
+        pic.offset[0], pic.offset[1], pic.offset[2] = offsets
+        pic.plane[0], pic.pitch[0] = t.data_ptr(), t.stride(0)
+        return pic, (t,)
+    formats = {torch.uint8: RGB_PLANAR8, torch.float16: RGB_PLANAR_F16, torch.float32: RGB_PLANAR_F32}
+    if tuple(t.shape) != (3, h, w) or t.dtype not in formats:
+        raise ValueError(f"rgb_picture_of: a uint8 tensor [{h}, {w}, 3 or 4] or a uint8 / float16 / float32 tensor [3, {h}, {w}], got {t.dtype} {tuple(t.shape)}")
+    if t.stride(2) != 1:
+        raise ValueError(f"rgb_picture_of: a planar frame has to have unit stride along a row, got strides {t.stride()}")
+    pic.format, pic.pixel_bytes = formats[t.dtype], 0
+    for c in range(3):
+        pic.plane[c], pic.pitch[c] = t.data_ptr() + c * t.stride(0) * t.element_size(), t.stride(1) * t.element_size()
+    return pic, (t,)
 
 
 _lib = None
@@ -93,6 +152,9 @@ def load_library():
         lib.hmr_gpu_picture_check.argtypes = [C.POINTER(Picture), I, I]
         lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
         lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
+        lib.hmr_gpu_enc_load_source_rgb_device.argtypes = [P, I, C.POINTER(RgbPicture), P]
+        lib.hmr_gpu_enc_load_sources_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), P]
+        lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
         lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
         batch = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
@@ -184,6 +246,41 @@ def _export(lib, device, encs, cfgs, slot, picture, ssd, outs, nv12):
     return results, sums
 
 
+def _load(lib, device, encs, cfgs, slot, frames):
+    """the frames (what picture_of takes, or RGBFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
+    kinds = {False: [], True: []}
+    for k, f in enumerate(frames):
+        kinds[isinstance(f, RGBFrame)].append(k)
+    keep = []
+    for rgb, members in kinds.items():
+        n = len(members)
+        if not n:
+            continue
+        pics = ((RgbPicture if rgb else Picture) * n)()
+        for j, k in enumerate(members):
+            pics[j], t = (rgb_picture_of if rgb else picture_of)(frames[k], cfgs[k].width, cfgs[k].height)
+            keep.append(t)
+        name = "hmr_gpu_enc_load_sources_rgb_device" if rgb else "hmr_gpu_enc_load_sources_device"
+        if getattr(lib, name)((C.c_void_p * n)(*[encs[k] for k in members]), n, (C.c_int * n)(*([slot] * n)), pics, _stream_of(device)) != 0:
+            _fail(lib, name)
+    return keep
+
+
+def _export_sources(lib, device, encs, cfgs, slot, outs, nv12):
+    """ONE hmr_gpu_enc_export_sources_device: what slot `slot` of the encoders holds, as 8-bit 4:2:0"""
+    n = len(encs)
+    pics, results, keep = (Picture * n)(), [], []
+    for k, cfg in enumerate(cfgs):
+        target = _output(cfg, outs[k] if outs is not None else None, nv12, device)
+        pics[k], t = picture_of(target, cfg.width, cfg.height)
+        keep.append(t)
+        results.append(target)
+    if lib.hmr_gpu_enc_export_sources_device((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([slot] * n)), pics, _stream_of(device)) != 0:
+        _fail(lib, "hmr_gpu_enc_export_sources_device")
+    del keep
+    return results
+
+
 def _au_capacity(cfg):
     return max(1 << 20, int(cfg.width) * int(cfg.height) * 2)
 
@@ -209,11 +306,10 @@ class Encoder:
         self.slot_used = None            # the slot of the last encoded frame (export)
 
     def encode(self, frame, image_type=IMAGE_AUTO):
-        """frame: what picture_of takes.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P / 2 for I)."""
+        """frame: what picture_of takes, or an RGBFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
+        2 for I)."""
         lib = self.lib
-        pic, keep = picture_of(frame, self.cfg.width, self.cfg.height)
-        if lib.hmr_gpu_enc_load_source_device(self.enc, self.slot, C.byref(pic), _stream_of(self.device)) != 0:
-            _fail(lib, "hmr_gpu_enc_load_source_device")
+        keep = _load(lib, self.device, [self.enc], [self.cfg], self.slot, [frame])
         n = C.c_long()
         slice_type = lib.hmr_gpu_enc_encode_source(self.enc, self.slot, int(image_type), self.buf, len(self.buf), C.byref(n), None)
         del keep
@@ -234,6 +330,13 @@ class Encoder:
         pics, sums = _export(self.lib, self.device, [self.enc], [self.cfg], self.slot_used, picture, ssd, [out] if out is not None else None, nv12)
         return (pics[0] if pics else None), (sums[0] if sums is not None else None)
 
+    def source(self, out=None, nv12=False):
+        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made.  `out` and nv12 as in
+        export(); one launch of the egress kernel, ordered on torch's current stream."""
+        if self.slot_used is None:
+            raise RuntimeError("Encoder.source: nothing has been encoded yet")
+        return _export_sources(self.lib, self.device, [self.enc], [self.cfg], self.slot_used, [out] if out is not None else None, nv12)[0]
+
     def close(self):
         if self.enc:
             self.lib.hmr_gpu_enc_destroy(self.enc)
@@ -253,7 +356,7 @@ class BatchEncoder:
     """Several sequences (configurations with wfpp_num_threads > 1: the batch schedule), one picture of each per step(): ONE ingest launch for all their pictures and ONE
     launch for all their CTU stages.  Every sequence has a context - a stream - of its own.
 
-    step(frames): frames[i] is sequence i's next picture (what picture_of takes) or None when it has none this step.  Returns a list with one entry per sequence.
+    step(frames): frames[i] is sequence i's next picture (what picture_of takes, or an RGBFrame; a step that has both kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
     Not pipelined: entry i is the access unit of frames[i] (b"" for None).
     Pipelined (the default): access units are delivered ONE STEP LATE, as by hmr_gpu_enc_encode_batch_pipelined - entry i is the access unit of the picture sequence i was
     given in the previous step (b"" if it was given none), whose download and entropy coding ran beside this step's launch; flush() returns those of the last step.  When
@@ -302,14 +405,8 @@ class BatchEncoder:
         if self.outstanding is not None and self.outstanding != live:
             out.update(self.flush_dict())
         if live:
-            n = len(live)
-            pics, keep = (Picture * n)(), []
-            for k, i in enumerate(live):
-                pics[k], t = picture_of(frames[i], self.cfgs[i].width, self.cfgs[i].height)
-                keep.append(t)
-            slots = [self.slot] * n
-            if self.lib.hmr_gpu_enc_load_sources_device((C.c_void_p * n)(*[self.encs[i] for i in live]), n, (C.c_int * n)(*slots), pics, _stream_of(self.device)) != 0:
-                _fail(self.lib, "hmr_gpu_enc_load_sources_device")
+            slots = [self.slot] * len(live)
+            keep = _load(self.lib, self.device, [self.encs[i] for i in live], [self.cfgs[i] for i in live], self.slot, [frames[i] for i in live])
             for i, au in self._call(live, slots, [int(image_types[i]) for i in live] if image_types is not None else None).items():
                 out[i] = out.get(i, b"") + au      # (behind a flush the call itself delivers nothing)
             del keep
@@ -340,6 +437,21 @@ class BatchEncoder:
             table = torch.full((len(self.encs), 3), -1, dtype=torch.int64, device=sums.device)
             table[torch.tensor(live, device=sums.device)] = sums
         return pictures, table
+
+    def source(self, out=None, nv12=False):
+        """As Encoder.source, for every sequence that was given a picture in the last step(), with ONE launch: a list with one entry per sequence (None for a sequence
+        without a picture in that step; `out`, when given, is such a list too)."""
+        live = self.last_live
+        if not live:
+            raise RuntimeError("BatchEncoder.source: the last step encoded nothing")
+        if out is not None and len(out) != len(self.encs):
+            raise ValueError(f"BatchEncoder.source: {len(self.encs)} sequences, {len(out)} outputs")
+        pics = _export_sources(self.lib, self.device, [self.encs[i] for i in live], [self.cfgs[i] for i in live], self.slot_used,
+                               [out[i] for i in live] if out is not None else None, nv12)
+        pictures = [None] * len(self.encs)
+        for k, i in enumerate(live):
+            pictures[i] = pics[k]
+        return pictures
 
     def flush_dict(self):
         if self.outstanding is None:

@@ -763,6 +763,58 @@ int hmr_gpu_enc_export_picture_device(hmr_gpu_enc *enc, const hmr_gpu_picture *p
 int hmr_gpu_psnr(const uint64_t ssd[3], int width, int height, double psnr[3]);
 
 /* ------------------------------------------------------------------------------------------------
+ * 12f. RGB pictures in device memory: colour conversion inside the ingest (no counterpart in the reference)
+ *     A renderer leaves packed RGBA, a tensor library a [3, H, W] tensor, usually float in 0 .. 1.  hmr_gpu_enc_load_sources_rgb_device converts n such pictures
+ *     (1 .. 512; formats, matrices and ranges may be mixed within a call) to 8-bit 4:2:0 Y'CbCr and into picture slots of their encoders with ONE launch of a
+ *     bandwidth-bound kernel (k_ingest_rgb, picture_io.hip): every source sample is read once, nothing is written but the slot.  It carries the contract of 12d word
+ *     for word: the launch runs on the first encoder's stream behind what producer_stream holds now, producer_stream and the other encoders' streams go on behind it,
+ *     the host waits for nothing (but for a slot that has to be allocated first); only the bytes of the rows are read, nothing outside width x height of the slot is
+ *     written; a slot filled this way is indistinguishable, to every encode call, from one filled by hmr_gpu_enc_load_sources_device with the converted I420 picture.
+ *     Refused as in 12d, plus whatever hmr_gpu_rgb_picture_check refuses.
+ *     The arithmetic is defined in integers, so that a caller can reproduce every sample (homerhevc_amd/csrc/rgb_yuv.h holds it once, for the kernel and the host):
+ *       inputs: 8-bit R, G, B.  A float sample x (binary16 widened exactly to binary32) becomes q = x > 0 ? (x < 1 ? x : 1) : 0 (NaN: 0), v = (int)rintf(q * 255.0f) -
+ *         one binary32 product, round half to even, what np.rint(np.float32(q) * np.float32(255)) gives.
+ *       luma, per pixel:     Y = ((Yr R + Yg G + Yb B + 32768) >> 16) + yoff
+ *       chroma, per 2 x 2 block, SR, SG, SB the sums of its four pixels (the block's average, sited at its centre):
+ *                            U = clamp(((Ur SR + Ug SG + Ub SB + 131072) >> 18) + 128, 0, 255), V likewise; >> is an arithmetic shift of a 32-bit signed value
+ *       matrix, range     Yr, Yg, Yb            Ur, Ug, Ub               Vr, Vg, Vb              yoff
+ *       BT.601 limited    16829, 33039, 6416    -9714, -19070, 28784     28784, -24103, -4681    16
+ *       BT.601 full       19595, 38470, 7471    -11058, -21710, 32768    32768, -27439, -5329    0
+ *       BT.709 limited    11966, 40254, 4064    -6596, -22188, 28784     28784, -26145, -2639    16
+ *       BT.709 full       13933, 46871, 4732    -7509, -25259, 32768     32768, -29763, -3005    0
+ *     Every output is within 0.51 of the real-valued BT formula; grey gives U = V = 128 at every level; limited-range luma stays in 16 .. 235 and chroma in 16 .. 240.
+ *     The stream does NOT say which matrix or range was used: the parameter sets stay byte-identical to the reference's, which writes no colour description into the VUI.
+ *     Whoever decodes the stream has to be told by other means.  (Out of scope as well: other chroma sitings, 10-bit, bfloat16, alpha - a fourth byte is ignored.)
+ *     hmr_gpu_rgb_picture_check: pure host, like hmr_gpu_picture_check; names the field.  Refused: NULL descriptor, unknown format, matrix, full_range outside 0 / 1,
+ *     non-zero reserved, odd or non-positive width / height; PACKED8: pixel_bytes not 3 or 4, an offset outside 0 .. pixel_bytes - 1 or repeated, plane[0] NULL,
+ *     plane[1] or plane[2] given; planar: pixel_bytes or an offset not 0, a NULL plane; a negative pitch or one below a row's bytes (width x pixel_bytes, width x
+ *     element size); float formats: a plane or a pitch that is not a multiple of the element size.
+ *     hmr_gpu_rgb_convert_host: the same arithmetic in a plain loop over HOST memory - the descriptor's planes are host pointers here - into tightly packed I420 planes
+ *     (y: width x height, u, v: width / 2 x height / 2).  No device, no context.  A utility in the spirit of hmr_gpu_psnr, e.g. to compute quality against the
+ *     samples that were encoded; it is not a fallback for encoding.
+ *     hmr_gpu_enc_export_sources_device writes what picture slots hold - the pictures the encoders were given, after conversion - as 8-bit I420 or NV12 into the
+ *     caller's DEVICE pictures (descriptors as in 12e: written through the plane pointers), ONE launch of k_egress on the first encoder's stream.  It is ordered behind
+ *     consumer_stream and behind the encoders' own streams (a load into the slot); consumer_stream and those streams go on behind it; the host waits for nothing.
+ *     Refused: n outside 1 .. 512, a NULL encoder, encoders on different devices, a slot that does not exist, a descriptor hmr_gpu_picture_check refuses, an output
+ *     plane that is not device memory of the encoders' device.
+ * ------------------------------------------------------------------------------------------------ */
+enum { HMR_GPU_RGB_PACKED8 = 0, HMR_GPU_RGB_PLANAR8 = 1, HMR_GPU_RGB_PLANAR_F16 = 2, HMR_GPU_RGB_PLANAR_F32 = 3 };
+enum { HMR_GPU_MATRIX_BT601 = 0, HMR_GPU_MATRIX_BT709 = 1 };
+typedef struct hmr_gpu_rgb_picture {
+	int32_t format, matrix, full_range, reserved;   /* HMR_GPU_RGB_*; HMR_GPU_MATRIX_*; 0: limited range, 1: full range; 0 */
+	int32_t pixel_bytes;           /* PACKED8: 3 or 4; otherwise 0 */
+	int32_t offset[3];             /* PACKED8: byte of R, G, B inside a pixel, distinct, < pixel_bytes (RGB, BGR, RGBA, BGRA, ARGB ...; a fourth byte is ignored); otherwise 0 */
+	const void *plane[3];          /* PACKED8: plane[0] only, the others NULL; planar: R, G, B */
+	int64_t pitch[3];              /* bytes from row to row, >= a row's bytes; float formats: a multiple of the element size, planes aligned to it */
+} hmr_gpu_rgb_picture;
+int hmr_gpu_rgb_picture_check(const hmr_gpu_rgb_picture *pic, int width, int height);
+int hmr_gpu_rgb_convert_host(const hmr_gpu_rgb_picture *pic, int width, int height, uint8_t *y, uint8_t *u, uint8_t *v);
+int hmr_gpu_enc_load_source_rgb_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_rgb_picture *pic, void *producer_stream);
+int hmr_gpu_enc_load_sources_rgb_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_rgb_picture *pics, void *producer_stream);
+int hmr_gpu_enc_export_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_picture *out, void *consumer_stream);
+int hmr_gpu_enc_export_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *outs, void *consumer_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
  *     Replaces the per-block interpolation calls of the motion search and of motion compensation - the sixteen planes of
  *     hmr_half_pixel_estimation_luma_hm / hmr_quarter_pixel_estimation_luma_hm (hmr_motion_inter.c:395,442) and
