@@ -15,6 +15,9 @@
 // 3-byte pixels, four for 4-byte pixels, one per plane for planar 8-bit, two / four per plane for binary16 / binary32), channels picked by v_alignbyte_b32 / v_bfe_u32 with
 // the job's byte offsets, four 16-byte stores of int16 luma and one each of eight U and eight V samples.  A row's tail of fewer than 16 pixels goes sample by sample, a lane per 2 x 2 block.
 //
+// k_downscale (section 12g): 8-bit pictures of a larger size into the same int16 planes, area-averaged by the integer arithmetic of scale_area.h in the same pass; its
+// mapping (tiles through LDS) is described at the kernel.
+//
 // Mapping (struct Chunk): blockIdx.y = picture (a record of the job table), blockIdx.x = a chunk of CHUNK_ROWS rows of it - first the luma rows, then the chroma rows (a
 // chroma row is its U and its V part: as many 8-bit bytes as a luma row) - so that one grid covers the three planes of every picture; pictures smaller than the largest
 // of the launch leave their last chunks empty.  A lane takes a span of 16 samples.  Ingest: one 16-byte load, two 16-byte stores of int16; NV12 chroma: one 16-byte load
@@ -29,6 +32,7 @@
 // (global_atomic_add_x2).  Integer sums: exact whatever the order.  A chunk holds at most CHUNK_ROWS x EGRESS_MAX_WIDTH samples of one plane, each difference at most 255:
 // 8 x 8192 x 255^2 = 4 261 478 400 < 2^32, so neither a lane's nor a wavefront's accumulator wraps; a picture's sum does not fit 32 bits (255^2 x 3840 x 2160 = 5.4e11).
 #include <math.h>
+#include <string.h>
 #include "picture_io.h"
 
 namespace {
@@ -339,6 +343,137 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ingest_rgb(const RgbIngestJob *jo
 	}
 }
 
+// ---- downscaling ingest (section 12g) ----
+// k_downscale: 8-bit pictures of one size, area-averaged (scale_area.h) into the int16 planes of a smaller - or equal - size.  1.5 Ws Hs bytes read, 3 Wd Hd written per
+// picture (hmr_scale_bytes in picture_io.h).  blockIdx.y = picture; blockIdx.x = a tile of tile_rows output rows x SCALE_TILE_W output columns of one plane class - the
+// luma tiles first, then the chroma tiles (a chroma tile holds SCALE_TILE_W / 2 columns of U and as many of V, so that NV12's pairs are read once); smaller pictures
+// leave their last blocks empty.  Vertical pass first: a lane takes a span of 16 bytes of the source columns the tile covers and ONE output row, walks that row's source
+// rows (at most nine) with 16-byte loads at whatever address the pitch gives and keeps the sixteen weighted column sums in 32-bit registers; they go to LDS, a span in
+// SCALE_SPAN_WORDS words (16 and 4 of padding: the eight lanes of a 16-byte LDS store hit eight different quads of banks).  NV12's pairs stay interleaved in LDS - the
+// vertical pass works on bytes - and the horizontal pass picks every second column.  Horizontal pass: a lane per output sample, consecutive lanes consecutive columns,
+// the taps read from LDS, ONE division (a multiplication by the job's reciprocal, exact: hmr_scale_div), the int16 result to a second LDS tile; from there a lane per
+// eight samples writes whole 16-byte stores (the int16 side is 16-byte aligned: tiles start at multiples of 128 / 64 columns), a row's tail sample by sample.
+// A source row that two output rows of a tile share is loaded by two lanes of the same workgroup; the row or column two TILES share is read by both.  No lane reads a
+// byte outside [plane + y * pitch, plane + y * pitch + row bytes) or writes outside dst_w x dst_h.
+// tile_rows: the LDS holds SCALE_LDS_WORDS column sums; a tile row needs (spans of the tile) x SCALE_SPAN_WORDS of them, at most SCALE_MAX_SPANS spans at ratio 8
+// (128 x 8 + 1 luma columns: 65 spans; 2 x (64 x 8 + 1) chroma columns: 66), so 8 rows always fit and a picture scaled by less gets taller tiles, up to 32 rows:
+// more loads in flight per workgroup.  42 240 + 8 192 bytes of LDS: three workgroups a CU.
+constexpr int SCALE_TILE_W = 128, SCALE_SPAN_WORDS = 20, SCALE_MIN_ROWS = 8, SCALE_MAX_ROWS = 32, SCALE_MAX_SPANS = 66;
+constexpr int SCALE_LDS_WORDS = SCALE_MIN_ROWS * SCALE_MAX_SPANS * SCALE_SPAN_WORDS;
+static_assert((SCALE_TILE_W * HMR_SCALE_MAX_RATIO + 1 + 15) / 16 <= SCALE_MAX_SPANS && 2 * ((SCALE_TILE_W / 2 * HMR_SCALE_MAX_RATIO + 1 + 15) / 16) <= SCALE_MAX_SPANS, "a tile row at the largest ratio");
+static_assert(SCALE_LDS_WORDS * 4 + SCALE_MAX_ROWS * SCALE_TILE_W * 2 <= 80 * 1024, "two workgroups a CU at least");
+
+// The tile of block b of a picture: its class and plane size, its outputs [x0, x0 + nx) x [y0, y0 + ny), the source columns [c0, c1) they touch, and how those are
+// read: `streams` runs of `spans` 16-byte spans per source row, starting at byte `b0` of a row of `row_bytes` bytes.
+struct ScaleTile {
+	bool luma, empty, pairs;      // pairs: NV12 chroma
+	int x0, nx, y0, ny, c0, streams, spans, b0, row_bytes;
+	__host__ __device__ __forceinline__ int total() const { return streams * spans; }
+};
+__host__ __device__ __forceinline__ int scale_tiles_x(int w, bool luma) { return luma ? (w + SCALE_TILE_W - 1) / SCALE_TILE_W : ((w >> 1) + SCALE_TILE_W / 2 - 1) / (SCALE_TILE_W / 2); }
+__host__ __device__ __forceinline__ int scale_tiles_y(int h, int rows, bool luma) { return ((luma ? h : h >> 1) + rows - 1) / rows; }
+__host__ __device__ __forceinline__ int scale_tiles(const ScaleJob &j)
+{
+	return scale_tiles_x(j.dst_w, true) * scale_tiles_y(j.dst_h, j.tile_rows, true) + scale_tiles_x(j.dst_w, false) * scale_tiles_y(j.dst_h, j.tile_rows, false);
+}
+__host__ __device__ __forceinline__ ScaleTile scale_tile(const ScaleJob &j, int b)
+{
+	ScaleTile t;
+	const int luma_tiles = scale_tiles_x(j.dst_w, true) * scale_tiles_y(j.dst_h, j.tile_rows, true);
+	t.luma = b < luma_tiles;
+	if (!t.luma) b -= luma_tiles;
+	const int across = scale_tiles_x(j.dst_w, t.luma), down = scale_tiles_y(j.dst_h, j.tile_rows, t.luma);
+	t.empty = b >= across * down;
+	const int ty = b / across, tx = b - ty * across, per = t.luma ? SCALE_TILE_W : SCALE_TILE_W / 2;
+	const int pw = t.luma ? j.dst_w : j.dst_w >> 1, ph = t.luma ? j.dst_h : j.dst_h >> 1, sw = t.luma ? j.src_w : j.src_w >> 1;
+	t.x0 = tx * per; t.nx = pw - t.x0 < per ? pw - t.x0 : per;
+	t.y0 = ty * j.tile_rows; t.ny = ph - t.y0 < j.tile_rows ? ph - t.y0 : j.tile_rows;
+	t.pairs = !t.luma && j.format == HMR_GPU_PIC_NV12;
+	t.c0 = t.empty ? 0 : (int)hmr_scale_first(j.ax, (uint32_t)t.x0);
+	const int c1 = t.empty ? 0 : (int)hmr_scale_end(j.ax, (uint32_t)(t.x0 + t.nx - 1));
+	t.streams = t.luma || t.pairs ? 1 : 2;
+	t.b0 = t.pairs ? 2 * t.c0 : t.c0;
+	t.row_bytes = t.pairs ? 2 * sw : sw;
+	t.spans = ((t.pairs ? 2 : 1) * (c1 - t.c0) + 15) >> 4;
+	return t;
+}
+
+// the word of LDS (inside a tile row) that holds the column sum of byte `b` of a stream's window
+__device__ __forceinline__ int scale_word(int b) { return (b >> 4) * SCALE_SPAN_WORDS + (b & 15); }
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_downscale(const ScaleJob *jobs)
+{
+	__shared__ u32x4 sums4[SCALE_LDS_WORDS / 4];
+	__shared__ u32x4 outs4[SCALE_MAX_ROWS * SCALE_TILE_W / 8];
+	uint32_t *sums = (uint32_t *)sums4;
+	int16_t *outs = (int16_t *)outs4;
+	const ScaleJob j = jobs[blockIdx.y];
+	const ScaleTile k = scale_tile(j, (int)blockIdx.x);
+	if (k.empty) return;
+	const int t = (int)threadIdx.x, total = k.total(), row_words = total * SCALE_SPAN_WORDS;
+	const ScaleAxis ax = j.ax, ay = j.ay;
+
+	// vertical: (output row, span) per lane
+	for (int i = t; i < total * k.ny; i += HMR_BLOCK) {
+		const int r = i / total, p = i - r * total;
+		const bool second = p >= k.spans;      // (I420 chroma: the V plane's spans behind the U plane's)
+		const int b = k.b0 + ((second ? p - k.spans : p) << 4);
+		const bytes_in plane = (bytes_in)(k.luma ? j.src[0] : second ? j.src[2] : j.src[1]);
+		const int64_t pitch = k.luma ? j.pitch[0] : second ? j.pitch[2] : j.pitch[1];
+		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
+		uint32_t acc[16];
+#pragma unroll
+		for (int m = 0; m < 16; m++) acc[m] = 0;
+		const bool whole = b + 16 <= k.row_bytes;
+		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
+			const uint32_t w = hmr_scale_weight(ay, y, sy);
+			const bytes_in row = plane + (int64_t)sy * pitch + b;
+			if (whole) {
+				const u32x4 v = load16(row);
+				const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+				for (int m = 0; m < 16; m++) acc[m] += w * ((d[m >> 2] >> (8 * (m & 3))) & 255u);
+			} else {
+#pragma unroll
+				for (int m = 0; m < 16; m++) acc[m] += b + m < k.row_bytes ? w * row[m] : 0u;      // (the row's last bytes: sample by sample)
+			}
+		}
+		u32x4 *o = &sums4[(r * row_words + p * SCALE_SPAN_WORDS) >> 2];
+#pragma unroll
+		for (int m = 0; m < 4; m++) o[m] = u32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
+	}
+	__syncthreads();
+
+	// horizontal: an output sample per lane; a chroma tile row: SCALE_TILE_W / 2 of U, then as many of V
+	const int half_w = SCALE_TILE_W / 2;
+	for (int i = t; i < k.ny * SCALE_TILE_W; i += HMR_BLOCK) {
+		const int r = i / SCALE_TILE_W, q = i - r * SCALE_TILE_W;
+		const int second = k.luma ? 0 : q / half_w, xx = k.luma ? q : q - second * half_w;
+		if (xx >= k.nx) continue;
+		const uint32_t x = (uint32_t)(k.x0 + xx), hi = (x + 1) * ax.s;
+		const uint32_t *line = sums + r * row_words + (second && !k.pairs ? k.spans * SCALE_SPAN_WORDS : 0);
+		uint32_t sum = j.den >> 1;
+		for (uint32_t c = hmr_scale_first(ax, x); c * ax.d < hi; c++) {
+			const int rel = (int)c - k.c0;
+			sum += hmr_scale_weight(ax, x, c) * line[scale_word(k.pairs ? 2 * rel + second : rel)];
+		}
+		outs[i] = (int16_t)hmr_scale_div(sum, j.den, j.mden);
+	}
+	__syncthreads();
+
+	// eight samples per lane to the planes
+	const int stride = k.luma ? j.stride_y : j.stride_c;
+	for (int i = t; i < k.ny * (SCALE_TILE_W / 8); i += HMR_BLOCK) {
+		const int r = i / (SCALE_TILE_W / 8), q = i - r * (SCALE_TILE_W / 8);
+		const int second = k.luma ? 0 : q / (half_w / 8), xx = (k.luma ? q : q - second * (half_w / 8)) << 3;
+		if (xx >= k.nx) continue;
+		const samples_out d = (samples_out)(k.luma ? j.dst[0] : second ? j.dst[2] : j.dst[1]) + (size_t)(k.y0 + r) * stride + k.x0 + xx;
+		if (k.nx - xx >= 8) *(GLOBAL_AS u32x4 *)d = outs4[i];
+		else
+			for (int m = 0; m < k.nx - xx; m++) d[m] = outs[8 * i + m];      // (a row's tail)
+	}
+}
+
 // ---- egress ----
 // two dwords of two int16 samples each -> their four low bytes
 __device__ __forceinline__ uint32_t pack4(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x06040200u); }
@@ -471,6 +606,7 @@ __global__ __launch_bounds__(64) void k_picture_jobs(const uint32_t *h_jobs, uin
 inline int chunks_of(const IngestJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
 inline int chunks_of(const EgressJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
 inline int chunks_of(const RgbIngestJob &j) { return rgb_chunks(j.height); }
+inline int chunks_of(const ScaleJob &j) { return scale_tiles(j); }
 
 template <class Job>
 int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n)
@@ -489,6 +625,32 @@ int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, J
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n) { return launch(k_ingest, stream, h_jobs, d_jobs, n); }
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n) { return launch(k_egress, stream, h_jobs, d_jobs, n); }
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n) { return launch(k_ingest_rgb, stream, h_jobs, d_jobs, n); }
+int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n) { return launch(k_downscale, stream, h_jobs, d_jobs, n); }
+
+ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h)
+{
+	ScaleJob j;
+	memset(&j, 0, sizeof j);
+	for (int c = 0; c < 3; c++) {
+		j.src[c] = pic.plane[c];
+		j.pitch[c] = pic.pitch[c];
+		j.dst[c] = dst[c];
+	}
+	j.stride_y = stride_y; j.stride_c = stride_c;
+	j.src_w = src_w; j.src_h = src_h; j.dst_w = dst_w; j.dst_h = dst_h;
+	j.format = pic.format;
+	j.ax = hmr_scale_axis(src_w, dst_w); j.ay = hmr_scale_axis(src_h, dst_h);
+	j.den = j.ax.s * j.ay.s; j.mden = hmr_scale_magic(j.den);
+	// the widest tile row of this picture, in spans (it does not depend on the tile's rows; at most SCALE_MAX_SPANS at the ratios hmr_gpu_scale_check lets through), and
+	// the rows the LDS then holds
+	j.tile_rows = SCALE_MIN_ROWS;
+	int widest = 1;
+	for (int luma = 0; luma < 2; luma++)
+		for (int tx = 0; tx < scale_tiles_x(dst_w, luma != 0); tx++)
+			widest = std::max(widest, scale_tile(j, (luma ? 0 : scale_tiles_x(dst_w, true) * scale_tiles_y(dst_h, j.tile_rows, true)) + tx).total());
+	j.tile_rows = std::min(SCALE_MAX_ROWS, std::max(SCALE_MIN_ROWS, SCALE_LDS_WORDS / (widest * SCALE_SPAN_WORDS)));
+	return j;
+}
 
 static int refuse(const char *what)
 {
@@ -597,6 +759,45 @@ extern "C" int hmr_gpu_rgb_convert_host(const hmr_gpu_rgb_picture *pic, int widt
 			u[oc] = (uint8_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
 			v[oc] = (uint8_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
 		}
+	return HMR_GPU_OK;
+}
+
+// ---- section 12g: the host side of the downscaling ingest ----
+extern "C" int hmr_gpu_scale_check(int src_w, int src_h, int dst_w, int dst_h)
+{
+	const char *why = hmr_scale_refusal(src_w, src_h, dst_w, dst_h);
+	if (!why) return HMR_GPU_OK;
+	hmr_set_error("hmr_gpu_scale_check: %d x %d -> %d x %d: %s", src_w, src_h, dst_w, dst_h, why);
+	return HMR_GPU_ERR_ARG;
+}
+
+// scale_area.h's arithmetic over host memory: the loop a caller would write from the header's formula
+extern "C" int hmr_gpu_scale_host(const hmr_gpu_scaled_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v)
+{
+	if (!pic) {
+		hmr_set_error("hmr_gpu_scale_host: the descriptor is NULL");
+		return HMR_GPU_ERR_ARG;
+	}
+	const int rc = hmr_gpu_picture_check(&pic->pic, pic->width, pic->height);
+	if (rc) return rc;
+	if (const char *why = hmr_scale_refusal(pic->width, pic->height, dst_w, dst_h, true)) {      // (any ratio: the bound of 8 is the kernel's)
+		hmr_set_error("hmr_gpu_scale_host: %d x %d -> %d x %d: %s", pic->width, pic->height, dst_w, dst_h, why);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!y || !u || !v) {
+		hmr_set_error("hmr_gpu_scale_host: needs the three output planes");
+		return HMR_GPU_ERR_ARG;
+	}
+	const hmr_gpu_picture &p = pic->pic;
+	const int ws = pic->width, hs = pic->height;
+	hmr_scale_plane_host(p.plane[0], p.pitch[0], 1, ws, hs, dst_w, dst_h, y);
+	if (p.format == HMR_GPU_PIC_NV12) {
+		hmr_scale_plane_host(p.plane[1], p.pitch[1], 2, ws / 2, hs / 2, dst_w / 2, dst_h / 2, u);
+		hmr_scale_plane_host(p.plane[1] + 1, p.pitch[1], 2, ws / 2, hs / 2, dst_w / 2, dst_h / 2, v);
+	} else {
+		hmr_scale_plane_host(p.plane[1], p.pitch[1], 1, ws / 2, hs / 2, dst_w / 2, dst_h / 2, u);
+		hmr_scale_plane_host(p.plane[2], p.pitch[2], 1, ws / 2, hs / 2, dst_w / 2, dst_h / 2, v);
+	}
 	return HMR_GPU_OK;
 }
 

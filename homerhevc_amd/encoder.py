@@ -7,11 +7,14 @@
     au, slice_type = enc.encode(RGBFrame(rgb))  # rgb: a [3, H, W] tensor (uint8, or float16 / float32 in 0 .. 1) or packed uint8 [H, W, 3 or 4]; BT.709 limited range
     yuv = enc.source()                          # the 4:2:0 picture that frame was encoded from, as a uint8 CUDA tensor
 
+    ladder = BatchEncoder([EncoderConfig(1920, 1080, ...), EncoderConfig(1280, 720, ...), EncoderConfig(960, 544, ...)])
+    ladder.step([frame, ScaledFrame(frame, 1920, 1080), ScaledFrame(frame, 1920, 1080)])      # one 1080p picture, area-averaged down to each rung by ONE launch
+
     rec, ssd = enc.export(ssd=True)             # the reconstructed picture as a uint8 CUDA tensor, the sums of squared differences to `frame` as int64 [3]
     y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e and 12f).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), both
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f and 12g).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), both
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
@@ -61,6 +64,33 @@ class RgbPicture(C.Structure):
     """hmr_gpu_rgb_picture"""
     _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32), ("reserved", C.c_int32), ("pixel_bytes", C.c_int32), ("offset", C.c_int32 * 3),
                 ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3)]
+
+
+class ScaledPicture(C.Structure):
+    """hmr_gpu_scaled_picture"""
+    _fields_ = [("pic", Picture), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class ScaledFrame:
+    """A 4:2:0 picture that is LARGER than the encoder's, for Encoder.encode / BatchEncoder.step: area-averaged down to the encoder's size by the ingest kernel itself, in
+    the integer arithmetic of include/homer_gpu.h section 12g (every sample can be reproduced from the formula there; hmr_gpu_scale_host is the same arithmetic on the host).
+      frame: anything picture_of takes for a width x height picture (I420 tensor, (y, u, v) or (y, uv) views: a crop is just a view); width, height: ITS size.
+    The same frame may be given to any number of sequences of a step - a resolution ladder - and the step makes ONE scaled load call for all of them.  Downscaling only, by
+    at most 8 per axis; equal sizes are legal and give what the plain frame gives.  source() returns the scaled picture of each rung, and export(ssd=True) gives the sums
+    against that SCALED picture, not against `frame`.
+    RGB sources are not taken here.  What works without a host round trip: encode the top rung from the RGBFrame, take its source(), and give that to the lower rungs as a
+    ScaledFrame."""
+
+    def __init__(self, frame, width, height):
+        if isinstance(frame, (RGBFrame, ScaledFrame)):
+            raise TypeError("ScaledFrame: the frame has to be a 4:2:0 picture (what picture_of takes), not an RGBFrame or a ScaledFrame")
+        self.frame, self.width, self.height = frame, int(width), int(height)
+
+
+def scaled_picture_of(frame):
+    """The descriptor (hmr_gpu_scaled_picture) of a ScaledFrame; nothing is copied.  Returns (ScaledPicture, tensors): keep the tensors until the load call has returned."""
+    pic, keep = picture_of(frame.frame, frame.width, frame.height)
+    return ScaledPicture(pic=pic, width=frame.width, height=frame.height), keep
 
 
 class RGBFrame:
@@ -154,6 +184,8 @@ def load_library():
         lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_load_source_rgb_device.argtypes = [P, I, C.POINTER(RgbPicture), P]
         lib.hmr_gpu_enc_load_sources_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), P]
+        lib.hmr_gpu_enc_load_source_scaled_device.argtypes = [P, I, C.POINTER(ScaledPicture), P]
+        lib.hmr_gpu_enc_load_sources_scaled_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledPicture), P]
         lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
         lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
@@ -247,20 +279,24 @@ def _export(lib, device, encs, cfgs, slot, picture, ssd, outs, nv12):
 
 
 def _load(lib, device, encs, cfgs, slot, frames):
-    """the frames (what picture_of takes, or RGBFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
-    kinds = {False: [], True: []}
+    """the frames (what picture_of takes, RGBFrame or ScaledFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
+    kinds = {"yuv": [], "rgb": [], "scaled": []}
     for k, f in enumerate(frames):
-        kinds[isinstance(f, RGBFrame)].append(k)
+        kinds["rgb" if isinstance(f, RGBFrame) else "scaled" if isinstance(f, ScaledFrame) else "yuv"].append(k)
+    calls = {"yuv": (Picture, "hmr_gpu_enc_load_sources_device"), "rgb": (RgbPicture, "hmr_gpu_enc_load_sources_rgb_device"), "scaled": (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device")}
     keep = []
-    for rgb, members in kinds.items():
+    for kind, members in kinds.items():
         n = len(members)
         if not n:
             continue
-        pics = ((RgbPicture if rgb else Picture) * n)()
+        struct, name = calls[kind]
+        pics = (struct * n)()
         for j, k in enumerate(members):
-            pics[j], t = (rgb_picture_of if rgb else picture_of)(frames[k], cfgs[k].width, cfgs[k].height)
+            if kind == "scaled":
+                pics[j], t = scaled_picture_of(frames[k])
+            else:
+                pics[j], t = (rgb_picture_of if kind == "rgb" else picture_of)(frames[k], cfgs[k].width, cfgs[k].height)
             keep.append(t)
-        name = "hmr_gpu_enc_load_sources_rgb_device" if rgb else "hmr_gpu_enc_load_sources_device"
         if getattr(lib, name)((C.c_void_p * n)(*[encs[k] for k in members]), n, (C.c_int * n)(*([slot] * n)), pics, _stream_of(device)) != 0:
             _fail(lib, name)
     return keep
@@ -306,7 +342,7 @@ class Encoder:
         self.slot_used = None            # the slot of the last encoded frame (export)
 
     def encode(self, frame, image_type=IMAGE_AUTO):
-        """frame: what picture_of takes, or an RGBFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
+        """frame: what picture_of takes, an RGBFrame or a ScaledFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
         2 for I)."""
         lib = self.lib
         keep = _load(lib, self.device, [self.enc], [self.cfg], self.slot, [frame])
@@ -321,7 +357,7 @@ class Encoder:
 
     def export(self, picture=True, ssd=False, out=None, nv12=False):
         """The reconstructed picture of the frame the last encode() encoded (the final picture: after deblocking and SAO, what a decoder makes of the access unit) and / or
-        the three exact sums of squared differences between it and the picture that frame was encoded from.  Returns (picture, ssd); whichever was not asked for is None.
+        the three exact sums of squared differences between it and the picture that frame was encoded from (for a ScaledFrame: the SCALED picture in the slot, what source() returns).  Returns (picture, ssd); whichever was not asked for is None.
         picture: `out` written in place (anything picture_of takes: views into larger tensors are fine, only the rows' bytes are written), else a new contiguous uint8
         tensor [H * 3 // 2, W] (I420), with nv12=True a (y, uv) pair [H, W], [H / 2, W / 2, 2].  ssd: an int64 CUDA tensor [3] (Y, U, V); psnr(ssd.tolist(), W, H) gives dB.
         One launch of the egress kernel, ordered on torch's current stream: what is queued there afterwards sees the results, nothing waits on the host."""
@@ -331,7 +367,7 @@ class Encoder:
         return (pics[0] if pics else None), (sums[0] if sums is not None else None)
 
     def source(self, out=None, nv12=False):
-        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made.  `out` and nv12 as in
+        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a ScaledFrame the scaled picture.  `out` and nv12 as in
         export(); one launch of the egress kernel, ordered on torch's current stream."""
         if self.slot_used is None:
             raise RuntimeError("Encoder.source: nothing has been encoded yet")
@@ -356,7 +392,7 @@ class BatchEncoder:
     """Several sequences (configurations with wfpp_num_threads > 1: the batch schedule), one picture of each per step(): ONE ingest launch for all their pictures and ONE
     launch for all their CTU stages.  Every sequence has a context - a stream - of its own.
 
-    step(frames): frames[i] is sequence i's next picture (what picture_of takes, or an RGBFrame; a step that has both kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
+    step(frames): frames[i] is sequence i's next picture (what picture_of takes, an RGBFrame or a ScaledFrame; a step that has several kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
     Not pipelined: entry i is the access unit of frames[i] (b"" for None).
     Pipelined (the default): access units are delivered ONE STEP LATE, as by hmr_gpu_enc_encode_batch_pipelined - entry i is the access unit of the picture sequence i was
     given in the previous step (b"" if it was given none), whose download and entropy coding ran beside this step's launch; flush() returns those of the last step.  When

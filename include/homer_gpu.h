@@ -815,6 +815,48 @@ int hmr_gpu_enc_export_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_p
 int hmr_gpu_enc_export_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *outs, void *consumer_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 12g. A resolution ladder from pictures in device memory: downscaling inside the ingest (no counterpart in the reference, which has no scaler)
+ *     One decoded or rendered picture is to be encoded at several sizes.  hmr_gpu_enc_load_sources_scaled_device fills picture slots of n encoders (1 .. 512) from
+ *     8-bit 4:2:0 pictures that are LARGER than (or as large as) the encoders' pictures, area-averaged down to each encoder's size, with ONE launch of a kernel
+ *     (k_downscale, picture_io.hip) that reads every source picture once per entry.  The same source picture may appear in any number of entries of a call - that is
+ *     the ladder; sizes, ratios and formats may be mixed freely within a call; an entry whose source has the encoder's size is legal and gives exactly what
+ *     hmr_gpu_enc_load_sources_device gives.  The source is I420 or NV12 at any base address and pitch, so a crop is just a view.
+ *     It carries the contract of 12d word for word: the launch runs on the first encoder's stream behind what producer_stream holds now, producer_stream and the
+ *     other encoders' streams go on behind it, the host waits for nothing (but for a slot that has to be allocated first); only the bytes of the source's rows are
+ *     read, nothing outside width x height of the slot is written; a slot filled this way is indistinguishable, to every encode call, from one filled by
+ *     hmr_gpu_enc_load_sources_device with the host-scaled I420 picture.  hmr_gpu_enc_export_sources_device (12f) returns what the slot holds.
+ *     Refused as in 12d, with the descriptor checked against the SOURCE's size (hmr_gpu_scaled_picture.width, .height), plus whatever hmr_gpu_scale_check refuses
+ *     for (source size -> encoder size).
+ *     The arithmetic is defined in integers, so that a caller can reproduce every sample (homerhevc_amd/csrc/scale_area.h holds it once, for the kernel and the host).
+ *     Area averaging, downscaling only.  Every plane is scaled on its own: luma Ws x Hs -> Wd x Hd, each chroma plane Ws/2 x Hs/2 -> Wd/2 x Hd/2, which keeps the
+ *     4:2:0 siting.  Per axis with source length S and destination length D:
+ *       g = gcd(S, D), s = S / g, d = D / g.  A source sample is d units wide, an output sample s units wide.
+ *       output x covers [x s, (x + 1) s); source sample i covers [i d, (i + 1) d)
+ *       tap weight w(x, i) = min((x + 1) s, (i + 1) d) - max(x s, i d) where that is positive; the weights of one output sum to s; at most ceil(S / D) + 1 taps
+ *     and, with ONE rounding and no intermediate rounding,
+ *       out(x, y) = (sum_j sum_i wy(y, j) wx(x, i) src(i, j) + (sx sy >> 1)) / (sx sy)
+ *     in unsigned 32-bit arithmetic; the division is an unsigned integer division.  The order of the passes therefore cannot change a bit.
+ *     Equal sizes give the identity; 2 : 1 gives (a + b + c + d + 2) >> 2; every output is within 0.5 of the real-valued area average.  sx sy is 9 for
+ *     1920 x 1080 -> 1280 x 720, 540 for 1920 x 1080 -> 416 x 240 and 21945 for 330 x 266 -> 328 x 264.
+ *     hmr_gpu_scale_check: pure host - no device, no context; names the field.  Refused: a non-positive or odd value among the four; dst > src on an axis (no
+ *     upscaling: area averaging degenerates to nearest neighbour there); src > 8 dst on an axis; a source axis above 65536; sx sy 255 + (sx sy >> 1) >= 2^32 (luma
+ *     and chroma have the same sx, sy) - every even size up to 8192 x 4320 passes.
+ *     hmr_gpu_scale_host: the same arithmetic in a plain loop over HOST memory - the descriptor's planes are host pointers here - into tightly packed I420 planes
+ *     (y: dst_w x dst_h; u, v: dst_w / 2 x dst_h / 2).  No device, no context.  A utility in the spirit of hmr_gpu_rgb_convert_host; it is not a fallback for encoding.
+ *     It refuses what hmr_gpu_picture_check and hmr_gpu_scale_check refuse, except that it takes any ratio: the bound of 8 is the kernel's, not the arithmetic's.
+ *     RGB sources are out of scope here; the composition that works without a host round trip: load the top rung with 12f, export its slot
+ *     (hmr_gpu_enc_export_sources_device), and give that picture to the lower rungs through this call.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct hmr_gpu_scaled_picture {
+	hmr_gpu_picture pic;           /* the SOURCE picture, as in 12d */
+	int32_t width, height;         /* the SOURCE's size */
+} hmr_gpu_scaled_picture;
+int hmr_gpu_scale_check(int src_w, int src_h, int dst_w, int dst_h);
+int hmr_gpu_enc_load_sources_scaled_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_scaled_picture *pics, void *producer_stream);
+int hmr_gpu_enc_load_source_scaled_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_picture *pic, void *producer_stream);
+int hmr_gpu_scale_host(const hmr_gpu_scaled_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v);
+
+/* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
  *     Replaces the per-block interpolation calls of the motion search and of motion compensation - the sixteen planes of
  *     hmr_half_pixel_estimation_luma_hm / hmr_quarter_pixel_estimation_luma_hm (hmr_motion_inter.c:395,442) and
