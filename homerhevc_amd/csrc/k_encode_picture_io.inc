@@ -1,9 +1,10 @@
 // Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
-// (include/homer_gpu.h sections 12d, 12e, 12f and 12g).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_downscale / k_egress (picture_io.hip)
+// (include/homer_gpu.h sections 12d, 12e, 12f, 12g and 12h).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim (picture_io.hip)
 // on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
 //   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
 //   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
 //           streams (which may still load the slots); the consumer's stream and all of those streams go on behind it.
+//   ssim:   ordered as export; the final pictures and the slots are read, three sums per encoder are written.
 // Each entry checks the caller's arguments and builds the jobs; the host-memory entries of k_encode_object.inc (widen_packed, narrow_packed) build theirs for a
 // packed picture - the staging buffer, a picture between GPUs - and run the same kernels.
 #include <unordered_set>
@@ -114,6 +115,36 @@ extern "C" int hmr_gpu_enc_load_source_device(hmr_gpu_enc *enc, int slot, const 
 	return hmr_gpu_enc_load_sources_device(&enc, 1, &slot, pic, producer_stream);
 }
 
+namespace {
+// What a launch on `st` that reads the encoders' final pictures and picture slots has to follow, besides the consumer (its work on the output memory: run_jobs): the
+// launches that wrote the final pictures and what the encoders' own streams hold (loads into the slots), every distinct stream once.  The consumer reads the results
+// behind the launch; a later encode call rewrites the final picture, a later load the slot: those streams are added to `behind` and go on behind it too.
+int wait_for_writers(hmr_gpu_enc **encs, int n, hipStream_t st, hipStream_t consumer, std::vector<hipStream_t> &behind)
+{
+	std::unordered_set<hipStream_t> seen = {consumer, st};
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		if (!e->ev_pic_done) {
+			HIP_TRY(hipEventCreateWithFlags(&e->ev_pic_done, hipEventDisableTiming));
+			HIP_TRY(hipEventCreateWithFlags(&e->ev_own_done, hipEventDisableTiming));
+		}
+		const hipStream_t wrote[2] = {e->pic_stream, e->ctx->stream};
+		hipEvent_t const ev[2] = {e->ev_pic_done, e->ev_own_done};
+		for (int k = 0; k < 2; k++) {
+			if (!seen.insert(wrote[k]).second) continue;
+			behind.push_back(wrote[k]);
+			// a stream with nothing in flight has nothing to queue behind (calls on one encoder come from one host thread at a time: nobody is adding to it now);
+			// the query is far cheaper than an event and a wait, and after an encode call most of a batch's streams are idle
+			if (hipStreamQuery(wrote[k]) == hipSuccess) continue;
+			(void)hipGetLastError();
+			HIP_TRY(hipEventRecord(ev[k], wrote[k]));
+			HIP_TRY(hipStreamWaitEvent(st, ev[k], 0));
+		}
+	}
+	return HMR_GPU_OK;
+}
+}  // namespace
+
 extern "C" int hmr_gpu_enc_export_pictures_device(hmr_gpu_enc **encs, int n, const hmr_gpu_picture *pics, const int *slots, uint64_t *dev_ssd, void *consumer_stream)
 {
 	static const char *const fn = "hmr_gpu_enc_export_pictures_device";
@@ -147,30 +178,9 @@ extern "C" int hmr_gpu_enc_export_pictures_device(hmr_gpu_enc **encs, int n, con
 	for (int i = 0; i < n; i++)
 		jobs[i] = egress_job(encs[i], pics ? &pics[i] : nullptr, slots ? encs[i]->src[slots[i]].p : nullptr, dev_ssd ? dev_ssd + 3 * (size_t)i : nullptr);
 	hipStream_t st = encs[0]->ctx->stream, consumer = (hipStream_t)consumer_stream;
-	// Behind the consumer (its work on the output memory and on dev_ssd: run_jobs), and here behind the launches that wrote the final pictures and behind what the
-	// encoders' own streams hold (loads into the slots), every distinct stream once.  The consumer reads the output behind the egress; a later encode call rewrites the
-	// final picture, a later load the slot: those streams go on behind it too.
 	auto behind_the_writers = [&](std::vector<hipStream_t> &behind) -> int {
-		std::unordered_set<hipStream_t> seen = {consumer, st};
-		for (int i = 0; i < n; i++) {
-			hmr_gpu_enc *e = encs[i];
-			if (!e->ev_pic_done) {
-				HIP_TRY(hipEventCreateWithFlags(&e->ev_pic_done, hipEventDisableTiming));
-				HIP_TRY(hipEventCreateWithFlags(&e->ev_own_done, hipEventDisableTiming));
-			}
-			const hipStream_t wrote[2] = {e->pic_stream, e->ctx->stream};
-			hipEvent_t const ev[2] = {e->ev_pic_done, e->ev_own_done};
-			for (int k = 0; k < 2; k++) {
-				if (!seen.insert(wrote[k]).second) continue;
-				behind.push_back(wrote[k]);
-				// a stream with nothing in flight has nothing to queue behind (calls on one encoder come from one host thread at a time: nobody is adding to it now);
-				// the query is far cheaper than an event and a wait, and after an encode call most of a batch's streams are idle
-				if (hipStreamQuery(wrote[k]) == hipSuccess) continue;
-				(void)hipGetLastError();
-				HIP_TRY(hipEventRecord(ev[k], wrote[k]));
-				HIP_TRY(hipStreamWaitEvent(st, ev[k], 0));
-			}
-		}
+		const int rc = wait_for_writers(encs, n, st, consumer, behind);
+		if (rc) return rc;
 		if (dev_ssd) HIP_TRY(hipMemsetAsync(dev_ssd, 0, 3 * (size_t)n * sizeof(uint64_t), st));
 		return HMR_GPU_OK;
 	};
@@ -310,4 +320,54 @@ extern "C" int hmr_gpu_enc_export_sources_device(hmr_gpu_enc **encs, int n, cons
 extern "C" int hmr_gpu_enc_export_source_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_picture *out, void *consumer_stream)
 {
 	return hmr_gpu_enc_export_sources_device(&enc, 1, &slot, out, consumer_stream);
+}
+
+// ---- section 12h: SSIM of the final pictures against picture slots ----
+extern "C" int hmr_gpu_enc_ssim_device(hmr_gpu_enc **encs, int n, const int *slots, int64_t *dev_ssim, void *consumer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_ssim_device";
+	if (!encs || !slots || !dev_ssim || n < 1 || n > PICTURE_MAX_JOBS) {
+		hmr_set_error("%s: needs 1 .. %d encoders with their slots and dev_ssim (n = %d)", fn, PICTURE_MAX_JOBS, n);
+		return HMR_GPU_ERR_ARG;
+	}
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		if (!e) return picture_refuse(fn, i, "the encoder is NULL");
+		if (e->ctx->device != encs[0]->ctx->device) return picture_refuse(fn, i, "the encoder is on another device than the call's first");
+		if (const char *why = hmr_ssim_refusal(e->seq.width, e->seq.height)) return picture_refuse(fn, i, why);
+		if (!e->has_picture) return picture_refuse(fn, i, "the encoder has not encoded a picture yet");
+		if (slots[i] < 0 || slots[i] >= (int)e->src.size()) return picture_refuse(fn, i, "the slot does not exist");
+	}
+	const int device = encs[0]->ctx->device;
+	HIP_TRY(hipSetDevice(device));
+	if (!on_device(dev_ssim, device) || !on_device(dev_ssim + 3 * (size_t)n - 1, device)) return not_device(fn, 0, "dev_ssim", device);
+	std::vector<SsimJob> jobs(n);
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		const Seq &s = e->seq;
+		SsimJob &j = jobs[i];
+		for (int c = 0; c < 3; c++) {
+			j.a[c] = e->src[slots[i]].p[c];
+			j.b[c] = plane0(e, e->cur, c);
+		}
+		j.sum = dev_ssim + 3 * (size_t)i;
+		j.stride_a_y = s.src_stride_y; j.stride_a_c = s.src_stride_c;
+		j.stride_b_y = s.stride_y; j.stride_b_c = s.stride_c;
+		j.width = s.width; j.height = s.height;
+	}
+	hipStream_t st = encs[0]->ctx->stream, consumer = (hipStream_t)consumer_stream;
+	// ordered as the export of 12e: behind the consumer (its work on dev_ssim), the writers of the final pictures and the loads into the slots; the sums are zeroed on
+	// the launch's stream, behind all of them
+	auto behind_the_writers = [&](std::vector<hipStream_t> &behind) -> int {
+		const int rc = wait_for_writers(encs, n, st, consumer, behind);
+		if (rc) return rc;
+		HIP_TRY(hipMemsetAsync(dev_ssim, 0, 3 * (size_t)n * sizeof(int64_t), st));
+		return HMR_GPU_OK;
+	};
+	return run_jobs(encs[0]->ssim, hmr_ssim_launch, st, jobs.data(), n, consumer, std::vector<hipStream_t>(1, consumer), behind_the_writers);
+}
+
+extern "C" int hmr_gpu_enc_ssim_one_device(hmr_gpu_enc *enc, int slot, int64_t *dev_ssim, void *consumer_stream)
+{
+	return hmr_gpu_enc_ssim_device(&enc, 1, &slot, dev_ssim, consumer_stream);
 }

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "rgb_yuv.h"
 #include "scale_area.h"
+#include "ssim_window.h"
 
 #define PICTURE_MAX_JOBS 512         // pictures per launch (the batch calls' limit)
 #define PICTURE_RING 4               // job tables of one direction in flight
@@ -62,6 +63,19 @@ struct ScaleJob {
 };
 static_assert(sizeof(ScaleJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
+// one picture of an SSIM launch (k_ssim): the sums of ssim_window.h's window values between the int16 planes a and b
+struct SsimJob {
+	const int16_t *a[3];         // the slot's planes at sample (0, 0); 16-byte aligned, read-only
+	const int16_t *b[3];         // the final picture's planes at sample (0, 0); 16-byte aligned, read-only
+	int64_t *sum;                // three sums (zeroed in front of the launch)
+	int32_t stride_a_y, stride_a_c, stride_b_y, stride_b_c;      // elements, multiples of 8
+	int32_t width, height;       // multiples of 8, at least 16
+};
+static_assert(sizeof(SsimJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
+
+// Algorithmic bytes of one width x height picture through k_ssim (tools/ssim_bench.py restates it): the int16 planes of both pictures are read once.
+static inline double hmr_ssim_bytes(int width, int height) { return 6.0 * (double)width * height; }
+
 // Algorithmic bytes of one picture through k_downscale (tools/scale_ingest_bench.py restates it): every sample of the source is read once, the int16 Y, U, V
 // planes of the destination are written.
 static inline double hmr_scale_bytes(int src_w, int src_h, int dst_w, int dst_h) { return 1.5 * (double)src_w * src_h + 3.0 * (double)dst_w * dst_h; }
@@ -84,11 +98,12 @@ static inline double hmr_egress_bytes(int width, int height, int picture, int su
 }
 
 // The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of k_ingest /
-// k_ingest_rgb / k_downscale / k_egress handles all n pictures; both on `stream`, nothing is waited for.
+// k_ingest_rgb / k_downscale / k_egress / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n);
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n);
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n);
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n);
+int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n);
 // the job of one picture: the sizes have passed hmr_gpu_scale_check; the ratios, their reciprocals and the tile height are derived here
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
 

@@ -595,6 +595,111 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_egress(const EgressJob *jobs)
 	if (sums) add_sums(ssd + 1, acc_u, acc_v, true);
 }
 
+// ---- SSIM (section 12h) ----
+// k_ssim: the exact sums of ssim_window.h's fixed-point SSIM values over every window of every plane, between the int16 planes of a picture slot (a) and the final
+// picture's (b).  Both pictures are read, 6 W H bytes per picture (hmr_ssim_bytes in picture_io.h); nothing is written but three 64-bit sums.  blockIdx.y = picture;
+// blockIdx.x = a tile of SSIM_TW x SSIM_TH windows of one plane, row by row - the luma tiles first, then U's, then V's; smaller pictures leave their last blocks empty.
+// A tile of 32 x 8 windows needs 33 x 9 blocks of 4 x 4 samples.
+// Stage 1, a lane per (block row, 16-byte span): tiles start at even block columns, so a span of 8 samples is two adjacent blocks and is 16-byte aligned in both
+// pictures (strides and margins are multiples of 8 elements); four 16-byte loads of each picture, the sums and products of the sample pairs by v_dot2_i32_i16, three
+// words per block to LDS: s1 | s2 << 16, ss, s12.  33 blocks are 17 spans: 153 of the 256 lanes load, all eight loads of a lane are in flight at once, and the 34th
+// block of a row is loaded but not used - 34 x 9 / (32 x 8) = 1.20 times the plane's bytes leave the caches, the re-read part from a tile that a neighbouring
+// workgroup reads at about the same time.  The last span of a plane with an odd number of block columns reaches 4 samples beyond the row's end: inside the row's
+// stride (a multiple of 8 elements), never used.  No load leaves [row, row + stride) of the plane's h rows.
+// Stage 2, a lane per window, consecutive lanes consecutive columns: the four blocks' words are read from LDS at a 3-word stride between lanes - 3 is odd, so the 32
+// lanes of a window row hit 32 different banks - and the window's q comes from hmr_ssim_window: a few 32-bit products and six 64-bit divisions.
+// The lanes' 64-bit values are summed over the wavefront, the workgroup's four wavefronts through LDS, and one lane adds the workgroup's sum to the picture's sum of
+// that plane with ONE 64-bit vector atomic (two's complement: the signed sum is exact whatever the order).
+// Why 32 x 8: 256 windows are one per lane, so each stage is ONE pass without a loop and the division, the costly part, runs with every lane busy; a 32 x 16 tile
+// would re-read 1.13 instead of 1.20 times the plane, but needs two passes per stage with 33 of 256 lanes busy in the second load pass, twice the registers of
+// stage 2 or a loop around it, and wastes more of the last tile row (1080p: 269 window rows are 33 tiles of 8 and 5 rows, against 16 of 16 and 13).  3.7 KB of LDS and
+// no loop-carried state: eight workgroups a CU, whose loads cover each other's divisions.
+constexpr int SSIM_TW = 32, SSIM_TH = 8, SSIM_SPANS = (SSIM_TW + 2) / 2, SSIM_ROW_WORDS = 3 * 2 * SSIM_SPANS;
+static_assert(SSIM_TW * SSIM_TH == HMR_BLOCK && SSIM_SPANS * (SSIM_TH + 1) <= HMR_BLOCK && SSIM_TW % 2 == 0, "one pass per stage, tiles start at even block columns");
+
+// The tile of block b of a W x H picture: its plane (3: none), the plane's size in blocks, the tile's first block and its windows [0, nx) x [0, ny).
+struct SsimTile {
+	int plane, bw, bh, bx0, by0, nx, ny;
+};
+__host__ __device__ __forceinline__ int ssim_tiles_x(int w) { return ((w >> 2) - 1 + SSIM_TW - 1) / SSIM_TW; }
+__host__ __device__ __forceinline__ int ssim_tiles_y(int h) { return ((h >> 2) - 1 + SSIM_TH - 1) / SSIM_TH; }
+__host__ __device__ __forceinline__ int ssim_tiles(int W, int H) { return ssim_tiles_x(W) * ssim_tiles_y(H) + 2 * ssim_tiles_x(W >> 1) * ssim_tiles_y(H >> 1); }
+__host__ __device__ __forceinline__ SsimTile ssim_tile(int W, int H, int b)
+{
+	SsimTile t;
+	const int luma = ssim_tiles_x(W) * ssim_tiles_y(H), chroma = ssim_tiles_x(W >> 1) * ssim_tiles_y(H >> 1);
+	t.plane = b < luma ? 0 : b < luma + chroma ? 1 : b < luma + 2 * chroma ? 2 : 3;
+	if (t.plane) b -= luma + (t.plane - 1) * chroma;
+	const int w = t.plane ? W >> 1 : W, h = t.plane ? H >> 1 : H, across = ssim_tiles_x(w);
+	const int ty = b / across, tx = b - ty * across;
+	t.bw = w >> 2; t.bh = h >> 2;
+	t.bx0 = tx * SSIM_TW; t.by0 = ty * SSIM_TH;
+	t.nx = t.bw - 1 - t.bx0 < SSIM_TW ? t.bw - 1 - t.bx0 : SSIM_TW;
+	t.ny = t.bh - 1 - t.by0 < SSIM_TH ? t.bh - 1 - t.by0 : SSIM_TH;
+	return t;
+}
+
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t dot2(uint32_t a, uint32_t b, uint32_t c) { return (uint32_t)__builtin_amdgcn_sdot2(__builtin_bit_cast(i16x2, a), __builtin_bit_cast(i16x2, b), (int)c, false); }
+
+// The loader, the only part that knows the planes hold int16: the 8 samples at (x, y) of four rows, two to a dword (x a multiple of 8).
+__device__ __forceinline__ void ssim_load(samples_in plane, int stride, int x, int y, u32x4 rows[4])
+{
+#pragma unroll
+	for (int i = 0; i < 4; i++) rows[i] = *(const GLOBAL_AS u32x4 *)(plane + (size_t)(y + i) * stride + x);
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_ssim(const SsimJob *jobs)
+{
+	__shared__ uint32_t blocks[(SSIM_TH + 1) * SSIM_ROW_WORDS];
+	__shared__ int64_t part[HMR_WAVES_PER_BLOCK];
+	const SsimJob &j = jobs[blockIdx.y];      // (read where it lies: the planes are picked by a run-time index, which a copy in registers would turn into scratch)
+	const SsimTile k = ssim_tile(j.width, j.height, (int)blockIdx.x);
+	if (k.plane == 3) return;
+	const int t = (int)threadIdx.x;
+
+	// stage 1: the sums of two adjacent blocks per lane
+	const int r = t / SSIM_SPANS, p = t - r * SSIM_SPANS;
+	if (r <= k.ny && 2 * p <= k.nx) {      // (ny + 1 block rows, nx + 1 block columns)
+		const int x = 4 * (k.bx0 + 2 * p), y = 4 * (k.by0 + r);
+		u32x4 a[4], b[4];
+		ssim_load((samples_in)j.a[k.plane], k.plane ? j.stride_a_c : j.stride_a_y, x, y, a);
+		ssim_load((samples_in)j.b[k.plane], k.plane ? j.stride_b_c : j.stride_b_y, x, y, b);
+		uint32_t *o = blocks + r * SSIM_ROW_WORDS + 6 * p;
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			uint32_t s1 = 0, s2 = 0, ss = 0, s12 = 0;
+#pragma unroll
+			for (int i = 0; i < 4; i++) {
+				const uint32_t a0 = h ? a[i].z : a[i].x, a1 = h ? a[i].w : a[i].y, b0 = h ? b[i].z : b[i].x, b1 = h ? b[i].w : b[i].y;
+				s1 = dot2(a0, 0x00010001u, dot2(a1, 0x00010001u, s1));
+				s2 = dot2(b0, 0x00010001u, dot2(b1, 0x00010001u, s2));
+				ss = dot2(a0, a0, dot2(a1, a1, dot2(b0, b0, dot2(b1, b1, ss))));
+				s12 = dot2(a0, b0, dot2(a1, b1, s12));
+			}
+			o[3 * h] = s1 | s2 << 16; o[3 * h + 1] = ss; o[3 * h + 2] = s12;
+		}
+	}
+	__syncthreads();
+
+	// stage 2: a window per lane
+	const int wy = t / SSIM_TW, wx = t - wy * SSIM_TW;
+	int64_t q = 0;
+	if (wx < k.nx && wy < k.ny) {
+		const uint32_t *top = blocks + wy * SSIM_ROW_WORDS + 3 * wx, *bottom = top + SSIM_ROW_WORDS;
+		const uint32_t s = top[0] + top[3] + bottom[0] + bottom[3];      // (the halves do not carry: S1, S2 <= 16320)
+		q = hmr_ssim_window(s & 0xffffu, s >> 16, top[1] + top[4] + bottom[1] + bottom[4], top[2] + top[5] + bottom[2] + bottom[5]);
+	}
+	const int64_t w = wave_sum(q);
+	if (lane_id() == 0) part[wave_in_block()] = w;
+	__syncthreads();
+	if (t == 0) {
+		int64_t total = 0;
+		for (int i = 0; i < HMR_WAVES_PER_BLOCK; i++) total += part[i];
+		if (total) __hip_atomic_fetch_add((GLOBAL_AS uint64_t *)j.sum + k.plane, (uint64_t)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
 // ---- launches ----
 // a job table from page-locked host memory to the device by a kernel, `words` 32-bit words per job: a host-to-device copy would queue on the copy engines behind a
 // batch's multi-megabyte download (k_encode_batch.inc, k_batch_stage)
@@ -607,6 +712,7 @@ inline int chunks_of(const IngestJob &j) { return Chunk{0, j.width, j.height}.ch
 inline int chunks_of(const EgressJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
 inline int chunks_of(const RgbIngestJob &j) { return rgb_chunks(j.height); }
 inline int chunks_of(const ScaleJob &j) { return scale_tiles(j); }
+inline int chunks_of(const SsimJob &j) { return ssim_tiles(j.width, j.height); }
 
 template <class Job>
 int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n)
@@ -626,6 +732,7 @@ int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n) { return launch(k_egress, stream, h_jobs, d_jobs, n); }
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n) { return launch(k_ingest_rgb, stream, h_jobs, d_jobs, n); }
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n) { return launch(k_downscale, stream, h_jobs, d_jobs, n); }
+int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n) { return launch(k_ssim, stream, h_jobs, d_jobs, n); }
 
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h)
 {
@@ -811,6 +918,55 @@ extern "C" int hmr_gpu_psnr(const uint64_t ssd[3], int width, int height, double
 	for (int c = 0; c < 3; c++) {
 		const double samples = c ? (double)(width / 2) * (height / 2) : (double)width * height;
 		psnr[c] = ssd[c] ? 10.0 * log10(255.0 * 255.0 * samples / (double)ssd[c]) : 99.99;
+	}
+	return HMR_GPU_OK;
+}
+
+// ---- section 12h: the host side of SSIM ----
+// the mean SSIM of each plane from its sum: pure host
+extern "C" int hmr_gpu_ssim(const int64_t sums[3], int width, int height, double ssim[3])
+{
+	if (!sums || !ssim) {
+		hmr_set_error("hmr_gpu_ssim: needs three sums and three results");
+		return HMR_GPU_ERR_ARG;
+	}
+	if (const char *why = hmr_ssim_refusal(width, height)) {
+		hmr_set_error("hmr_gpu_ssim: %d x %d: %s", width, height, why);
+		return HMR_GPU_ERR_ARG;
+	}
+	for (int c = 0; c < 3; c++) {
+		const int64_t windows = c ? hmr_ssim_windows(width / 2, height / 2) : hmr_ssim_windows(width, height);
+		if (sums[c] > (windows << HMR_SSIM_ONE_BITS) || sums[c] < -(windows << HMR_SSIM_ONE_BITS)) {
+			hmr_set_error("hmr_gpu_ssim: sums[%d] = %lld is outside +- 2^30 x %lld windows of a %d x %d picture", c, (long long)sums[c], (long long)windows, width, height);
+			return HMR_GPU_ERR_ARG;
+		}
+		ssim[c] = (double)sums[c] / (double)(windows << HMR_SSIM_ONE_BITS);      // (both conversions exact below 2^53: ONE rounding)
+	}
+	return HMR_GPU_OK;
+}
+
+// ssim_window.h's arithmetic over host memory: the loop a caller would write from the header's definition
+extern "C" int hmr_gpu_ssim_host(const hmr_gpu_picture *a, const hmr_gpu_picture *b, int width, int height, int64_t sums[3])
+{
+	int rc;
+	if ((rc = hmr_gpu_picture_check(a, width, height)) || (rc = hmr_gpu_picture_check(b, width, height))) return rc;
+	if (const char *why = hmr_ssim_refusal(width, height)) {
+		hmr_set_error("hmr_gpu_ssim_host: %d x %d: %s", width, height, why);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!sums) {
+		hmr_set_error("hmr_gpu_ssim_host: needs the three sums");
+		return HMR_GPU_ERR_ARG;
+	}
+	// plane c of a picture: its first sample, its pitch, the bytes from sample to sample
+	struct View { const uint8_t *p; int64_t pitch; int step; };
+	auto view = [](const hmr_gpu_picture &pic, int c) {
+		if (c == 0 || pic.format == HMR_GPU_PIC_I420) return View{pic.plane[c], pic.pitch[c], 1};
+		return View{pic.plane[1] + (c - 1), pic.pitch[1], 2};
+	};
+	for (int c = 0; c < 3; c++) {
+		const View va = view(*a, c), vb = view(*b, c);
+		sums[c] = hmr_ssim_plane_host(va.p, va.pitch, va.step, vb.p, vb.pitch, vb.step, c ? width / 2 : width, c ? height / 2 : height);
 	}
 	return HMR_GPU_OK;
 }

@@ -12,9 +12,11 @@
 
     rec, ssd = enc.export(ssd=True)             # the reconstructed picture as a uint8 CUDA tensor, the sums of squared differences to `frame` as int64 [3]
     y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
+    sums = enc.ssim()                           # the exact fixed-point SSIM sums between the reconstructed picture and `frame` as int64 [3], by one launch of k_ssim
+    y, u, v = ssim(sums.tolist(), 1920, 1080)   # the mean SSIM of each plane, 1.0 for identical pictures
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f and 12g).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), both
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g and 12h).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), all
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
@@ -162,6 +164,22 @@ def psnr(ssd, width, height):
     return tuple(out)
 
 
+def ssim(sums, width, height):
+    """The mean SSIM of each plane (Y, U, V; 1.0 for identical pictures, negative for inverted ones) from three SSIM sums - Python ints, e.g. Encoder.ssim().tolist() - of a
+    width x height 4:2:0 picture, through hmr_gpu_ssim: sum / (2^30 x the plane's windows), include/homer_gpu.h section 12h.  Pure host arithmetic: needs neither torch
+    nor a GPU."""
+    lib = _lib or _host_lib or C.CDLL(LIB_PATH)
+    lib.hmr_gpu_last_error.restype = C.c_char_p
+    lib.hmr_gpu_ssim.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    values = [int(v) for v in sums]
+    if len(values) != 3 or not all(-(1 << 63) <= v < 1 << 63 for v in values):
+        raise ValueError(f"ssim: three 64-bit sums, got {values}")
+    out = (C.c_double * 3)()
+    if lib.hmr_gpu_ssim((C.c_int64 * 3)(*values), int(width), int(height), out) != 0:
+        raise ValueError((lib.hmr_gpu_last_error() or b"hmr_gpu_ssim").decode(errors="replace"))
+    return tuple(out)
+
+
 def load_library():
     """libhomer_gpu.so with the argument types of the calls this module makes.  torch brings up its HIP runtime first where it finds a GPU."""
     global _lib
@@ -189,6 +207,7 @@ def load_library():
         lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
         lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
+        lib.hmr_gpu_enc_ssim_device.argtypes = [C.POINTER(P), I, C.POINTER(I), P, P]
         batch = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
         lib.hmr_gpu_enc_encode_batch.argtypes = batch
         lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = batch
@@ -278,6 +297,16 @@ def _export(lib, device, encs, cfgs, slot, picture, ssd, outs, nv12):
     return results, sums
 
 
+def _ssim(lib, device, encs, slot):
+    """ONE hmr_gpu_enc_ssim_device for the encoders `encs`: an int64 tensor [len(encs), 3]"""
+    import torch
+    n = len(encs)
+    sums = torch.empty((n, 3), dtype=torch.int64, device=f"cuda:{device}")
+    if lib.hmr_gpu_enc_ssim_device((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([slot] * n)), C.c_void_p(sums.data_ptr()), _stream_of(device)) != 0:
+        _fail(lib, "hmr_gpu_enc_ssim_device")
+    return sums
+
+
 def _load(lib, device, encs, cfgs, slot, frames):
     """the frames (what picture_of takes, RGBFrame or ScaledFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
     kinds = {"yuv": [], "rgb": [], "scaled": []}
@@ -365,6 +394,15 @@ class Encoder:
             raise RuntimeError("Encoder.export: nothing has been encoded yet")
         pics, sums = _export(self.lib, self.device, [self.enc], [self.cfg], self.slot_used, picture, ssd, [out] if out is not None else None, nv12)
         return (pics[0] if pics else None), (sums[0] if sums is not None else None)
+
+    def ssim(self):
+        """The three exact SSIM sums (Y, U, V) between the reconstructed picture of the frame the last encode() encoded and the picture that frame was encoded from (for a
+        ScaledFrame: the SCALED picture in the slot), as an int64 CUDA tensor [3]; ssim(sums.tolist(), W, H) gives the mean SSIM of each plane.  Integer arithmetic
+        (include/homer_gpu.h section 12h): the sums are the same bit for bit on every run.  One launch of k_ssim, ordered on torch's current stream: what is queued there
+        afterwards sees the sums, nothing waits on the host."""
+        if self.slot_used is None:
+            raise RuntimeError("Encoder.ssim: nothing has been encoded yet")
+        return _ssim(self.lib, self.device, [self.enc], self.slot_used)[0]
 
     def source(self, out=None, nv12=False):
         """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a ScaledFrame the scaled picture.  `out` and nv12 as in
@@ -473,6 +511,18 @@ class BatchEncoder:
             table = torch.full((len(self.encs), 3), -1, dtype=torch.int64, device=sums.device)
             table[torch.tensor(live, device=sums.device)] = sums
         return pictures, table
+
+    def ssim(self):
+        """As Encoder.ssim, for every sequence that was given a picture in the last step(), with ONE launch: an int64 CUDA tensor [sequences, 3]; the rows of idle sequences
+        hold -2^63 (no sum reaches it; -1 is a possible sum)."""
+        import torch
+        live = self.last_live
+        if not live:
+            raise RuntimeError("BatchEncoder.ssim: the last step encoded nothing")
+        sums = _ssim(self.lib, self.device, [self.encs[i] for i in live], self.slot_used)
+        table = torch.full((len(self.encs), 3), -(1 << 63), dtype=torch.int64, device=sums.device)
+        table[torch.tensor(live, device=sums.device)] = sums
+        return table
 
     def source(self, out=None, nv12=False):
         """As Encoder.source, for every sequence that was given a picture in the last step(), with ONE launch: a list with one entry per sequence (None for a sequence

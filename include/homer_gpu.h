@@ -857,6 +857,54 @@ int hmr_gpu_enc_load_source_scaled_device(hmr_gpu_enc *enc, int slot, const hmr_
 int hmr_gpu_scale_host(const hmr_gpu_scaled_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v);
 
 /* ------------------------------------------------------------------------------------------------
+ * 12h. SSIM of the reconstructed pictures, left in device memory (no counterpart in the reference, whose only metric is homer_psnr)
+ *     PSNR ranks the rungs of a ladder and quantisers that blur differently badly; the metric expected beside it is SSIM.  hmr_gpu_enc_ssim_device leaves, for n
+ *     encoders (1 .. 512), the exact sums of a fixed-point SSIM value over all windows of each plane between the encoder's final picture and a picture slot, with ONE
+ *     launch of a kernel (k_ssim, picture_io.hip) that reads both pictures' int16 planes once (plus a tile's rim) and writes nothing but the sums; no host
+ *     synchronisation.  "The picture" of an encoder is 12e's: the final picture of the frame its last encode call encoded - single, batch, pipelined batch (an
+ *     encoder with an access unit outstanding is accepted) or chain (every object holds its own frame's picture); the slot is whatever slots[i] of encs[i] holds
+ *     when the launch runs - normally the slot the frame was encoded from; any loaded slot is legal.
+ *     The arithmetic is defined in integers, so that a caller can reproduce every sum (homerhevc_amd/csrc/ssim_window.h holds it once, for the kernel and the host).
+ *     Every plane on its own: luma width x height, each chroma plane width / 2 x height / 2; a = the slot's samples, b = the final picture's.  Every size the frame
+ *     encoder accepts is a multiple of 8, so a w x h plane is an exact grid of bw x bh = (w / 4) x (h / 4) BLOCKS of 4 x 4 samples.
+ *       block sums, over a block's 16 samples:   s1 = sum a    s2 = sum b    ss = sum (a a + b b)    s12 = sum a b
+ *       windows: every 2 x 2 group of adjacent blocks - 8 x 8 samples; neighbouring windows overlap by one block; (bw - 1) (bh - 1) windows a plane.
+ *         S1, S2, SS, S12 = the sums of the four blocks' sums
+ *       per window, in exact integers, C1 = 416 = floor((0.01 255)^2 64 + 0.5), C2 = 235963 = floor((0.03 255)^2 64 63 + 0.5) (the usual 8 x 8 block-SSIM constants):
+ *         var = 64 SS - S1 S1 - S2 S2        cov = 64 S12 - S1 S2
+ *         N = (2 S1 S2 + C1) (2 cov + C2)    D = (S1 S1 + S2 S2 + C1) (var + C2)
+ *         q = floor(2^30 N / D), the floor towards minus infinity (N may be negative: a window of a picture against its inverse)
+ *       per plane:  sum[c] = the sum of q over the plane's windows, a signed 64-bit integer - exact in any order of addition.  It does not fit 32 bits: a 2160p luma
+ *         plane of identical pictures gives 2^30 x 959 x 539 = 5.5e14.
+ *       mean SSIM of plane c = sum[c] / (2^30 windows[c]): hmr_gpu_ssim, one double division on the host.
+ *     Bounds: 0 < D < 2^57, |N| <= D, so -2^30 <= q <= 2^30, and q = 2^30 exactly when the window's samples are equal in a and b (ssim_window.h derives them).
+ *     2^30 N does not fit 64 bits; ssim_window.h says how the exact quotient is reached in 64-bit arithmetic - the result is the formula's, bit for bit.
+ *     What is read: the h rows (chroma: h / 2) of each int16 plane, [row, row + stride) of each - a plane with an odd number of block columns has a last 16-byte span
+ *     whose second half lies beyond the row's w samples, inside the row's stride (strides are multiples of 8 elements); those values are ignored.
+ *     dev_ssim (device memory, n x 3 values): dev_ssim[3 * i + c] = sum[c] of encs[i].
+ *     consumer_stream: as in 12e, word for word.  The launch runs on the first encoder's stream behind an event recorded on consumer_stream (the consumer may still be
+ *     using dev_ssim), behind the launches that wrote the final pictures and behind whatever the encoders' streams hold (a load into the slot); the sums are zeroed on
+ *     that stream in front of the launch.  Behind the launch the library records an event that consumer_stream and the streams of all the call's encoders wait for:
+ *     what the caller queues on consumer_stream after the call sees the sums, a later encode call and a later load into the slot run after the kernel has read the
+ *     pictures.  The host waits for nothing in either direction.
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is queued, every encoder left working: n outside 1 .. 512, NULL encs, slots or
+ *     dev_ssim, a NULL encoder, encoders on different devices, a slot that does not exist, an encoder without an encoded picture, a picture below 16 samples in width
+ *     or height (a chroma plane with fewer than two block rows or columns has no window), dev_ssim that hipPointerGetAttributes does not report as device memory of
+ *     the encoders' device.
+ *     hmr_gpu_ssim: sums[c] / (2^30 windows[c]) for the three planes of a width x height picture, in double: both operands are exact below 2^53, so the result is the
+ *     correctly rounded quotient.  Pure host code: no device, no context.  Refused: NULL arguments, a width or height that is not a positive multiple of 8 or is below
+ *     16, a sum outside +- 2^30 windows.
+ *     hmr_gpu_ssim_host: the same arithmetic in plain nested loops over two 8-bit pictures in HOST memory - the descriptors' planes are host pointers here; I420 or
+ *     NV12 (the two may differ), any pitch - into sums[3].  No device, no context.  A utility in the spirit of hmr_gpu_scale_host.  It refuses what
+ *     hmr_gpu_picture_check refuses for either picture, the sizes hmr_gpu_ssim refuses, and NULL sums.
+ *     Out of scope: a call on arbitrary 8-bit device pictures, MS-SSIM, Gaussian windows, one figure for Y, U and V together.
+ * ------------------------------------------------------------------------------------------------ */
+int hmr_gpu_enc_ssim_device(hmr_gpu_enc **encs, int n, const int *slots, int64_t *dev_ssim, void *consumer_stream);
+int hmr_gpu_enc_ssim_one_device(hmr_gpu_enc *enc, int slot, int64_t *dev_ssim, void *consumer_stream);
+int hmr_gpu_ssim(const int64_t sums[3], int width, int height, double ssim[3]);
+int hmr_gpu_ssim_host(const hmr_gpu_picture *a, const hmr_gpu_picture *b, int width, int height, int64_t sums[3]);
+
+/* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
  *     Replaces the per-block interpolation calls of the motion search and of motion compensation - the sixteen planes of
  *     hmr_half_pixel_estimation_luma_hm / hmr_quarter_pixel_estimation_luma_hm (hmr_motion_inter.c:395,442) and
