@@ -18,7 +18,7 @@ hmr_gpu_ctx *hmr_default_ctx();
 
 namespace {
 
-enum { PT_SAD = 1, PT_SSD, PT_PREDICT, PT_RECONST, PT_VARIANCE, PT_INTRA_PRED, PT_FILL_REFS, PT_ADI_FILTER, PT_TRANSFORM, PT_ITRANSFORM, PT_QUANT, PT_INV_QUANT, PT_SAD_U8 };
+enum { PT_SAD = 1, PT_SSD, PT_PREDICT, PT_RECONST, PT_VARIANCE, PT_INTRA_PRED, PT_FILL_REFS, PT_ADI_FILTER, PT_TRANSFORM, PT_ITRANSFORM, PT_QUANT, PT_INV_QUANT };
 
 struct PtArgs {
 	int op, bytes;
@@ -38,13 +38,6 @@ __global__ __launch_bounds__(64) void k_primtest(PtArgs a, int16_t *arena, uint8
 	uint32_t r = 0;
 	switch (a.op) {
 	case PT_SAD: r = blk_sad(g, A(0), p[0], A(1), p[1], p[2]); break;
-	case PT_SAD_U8: {      // the device's motion search: candidates against byte planes (multi_sad_u8; the source block at pitch 64)
-		const uint8_t *cand[4] = {B(1), nullptr, B(1) + 1, nullptr};
-		uint32_t out[4];
-		multi_sad_u8<4>(g, B(0), p[2], cand, p[1], out);
-		r = out[0];
-		break;
-	}
 	case PT_SSD: r = a.bytes ? blk_ssd(g, B(0), p[0], B(1), p[1], p[2]) : blk_ssd(g, A(0), p[0], A(1), p[1], p[2]); break;
 	case PT_PREDICT:
 		if (a.bytes) blk_predict(g, B(0), p[0], B(1), p[1], A(2), p[2], p[3]);
@@ -121,6 +114,30 @@ uint32_t run(int op, const int *p, int np, Operand *ops, int nops)
 	return r;
 }
 
+// the motion search's multi-candidate byte SAD as cand_sads (enc_inter.h) calls it: one list of candidates per workgroup, every result
+template <int MAXC>
+__device__ __forceinline__ void multi_sad_all(const WaveGrp g, const uint8_t *src, const uint8_t *plane, const long long *off, int stride, int n, uint32_t *out)
+{
+	const uint8_t *cand[MAXC];
+#pragma unroll
+	for (int k = 0; k < MAXC; k++) cand[k] = off[k] < 0 ? nullptr : plane + off[k];
+	uint32_t r[MAXC];
+	multi_sad_u8<MAXC>(g, src, n, cand, stride, r);
+	if (g.tid == 0) {
+#pragma unroll
+		for (int k = 0; k < MAXC; k++) out[k] = r[k];
+	}
+}
+__global__ __launch_bounds__(64) void k_primtest_multi_sad(int maxc, const uint8_t *src, const uint8_t *plane, const long long *off, int stride, int n, uint32_t *out)
+{
+	const WaveGrp g{(int)threadIdx.x};
+	off += (size_t)blockIdx.x * maxc;
+	out += (size_t)blockIdx.x * maxc;
+	if (maxc == 4) multi_sad_all<4>(g, src, plane, off, stride, n, out);
+	else if (maxc == 8) multi_sad_all<8>(g, src, plane, off, stride, n, out);
+	else multi_sad_all<9>(g, src, plane, off, stride, n, out);
+}
+
 size_t span(int stride, int rows, int cols) { return stride ? (size_t)stride * (rows - 1) + cols : (size_t)cols; }
 
 }  // namespace
@@ -131,12 +148,23 @@ void hmr_gpu_prim_bytes(int on) { g_bytes = on ? 1 : 0; }
 
 uint32_t hmr_gpu_prim_sad(int16_t *src, uint32_t src_stride, int16_t *pred, uint32_t pred_stride, int size)
 {
-	if (g_bytes) {      // the device's search: the source block at the worker's pitch of 64, the candidate in a byte plane
-		std::vector<int16_t> blk(64 * 64, 0);
-		for (int y = 0; y < size; y++) memcpy(&blk[y * 64], src + (size_t)y * src_stride, size * 2);
-		Operand ops[2] = {{blk.data(), nullptr, blk.size()}, {pred, nullptr, span((int)pred_stride, size, size) + 8}};
-		const int p[3] = {64, (int)pred_stride, size};
-		return run(PT_SAD_U8, p, 3, ops, 2);
+	if (g_bytes) {      // the device's search: the source block at the worker's pitch of 64, the candidate in a byte plane - twice among skipped ones, every result looked at
+		std::vector<uint8_t> blk(64 * 64, 0), plane(span((int)pred_stride, size, size));
+		for (int y = 0; y < size; y++)
+			for (int x = 0; x < size; x++) {
+				blk[y * 64 + x] = (uint8_t)src[(size_t)y * src_stride + x];
+				plane[(size_t)y * pred_stride + x] = (uint8_t)pred[(size_t)y * pred_stride + x];
+			}
+		const int64_t off[4] = {0, -1, 0, -1};
+		uint32_t out[4] = {0, 0, 0, 0};
+		// (a failure is reported as a sum no block has, which no comparison with a reference passes, and in hmr_gpu_last_error: the caller's process goes on)
+		if (hmr_gpu_prim_multi_sad(4, blk.data(), plane.data(), plane.size(), off, 1, (int)pred_stride, size, out) != HMR_GPU_OK) { fprintf(stderr, "hmr_gpu_prim_sad: %s\n", hmr_gpu_last_error()); return 0xFFFFFFFFu; }
+		if (out[1] != 0 || out[3] != 0 || out[2] != out[0]) {
+			hmr_set_error("hmr_gpu_prim_sad: candidates {p, -, p, -} gave %u %u %u %u", out[0], out[1], out[2], out[3]);
+			fprintf(stderr, "%s\n", hmr_gpu_last_error());
+			return 0xFFFFFFFFu;
+		}
+		return out[0];
 	}
 	Operand ops[2] = {{src, nullptr, span((int)src_stride, size, size)}, {pred, nullptr, span((int)pred_stride, size, size)}};
 	const int p[3] = {(int)src_stride, (int)pred_stride, size};
@@ -227,6 +255,42 @@ void hmr_gpu_prim_inv_quant(int16_t *src, int16_t *dst, int depth, int comp, int
 	Operand ops[2] = {{src, nullptr, (size_t)cu_size * cu_size}, {nullptr, dst, (size_t)cu_size * cu_size}};
 	const int p[6] = {depth, comp, is_intra, cu_size, per, rem};
 	run(PT_INV_QUANT, p, 6, ops, 2);
+}
+int hmr_gpu_prim_multi_sad(int maxc, const uint8_t *src, const uint8_t *plane, size_t plane_bytes, const int64_t *cand_off, int ncalls, int stride, int n, uint32_t *out)
+{
+	if (!src || !plane || !cand_off || !out || ncalls < 1 || ncalls > 65536 || (maxc != 4 && maxc != 8 && maxc != 9) || (n != 8 && n != 16 && n != 32 && n != 64) || stride < 1) {
+		hmr_set_error("hmr_gpu_prim_multi_sad: maxc 4 / 8 / 9, n 8 / 16 / 32 / 64, a stride of at least 1, 1 .. 65536 lists");
+		return HMR_GPU_ERR_ARG;
+	}
+	for (int i = 0; i < ncalls * maxc; i++) {
+		const int64_t o = cand_off[i];
+		if (o == -1) continue;
+		if (o < 0 || (uint64_t)o + (uint64_t)(n - 1) * (uint64_t)stride + (uint64_t)n > (uint64_t)plane_bytes) {
+			hmr_set_error("hmr_gpu_prim_multi_sad: candidate %d of list %d does not lie inside the plane", i % maxc, i / maxc);
+			return HMR_GPU_ERR_ARG;
+		}
+	}
+	hmr_gpu_ctx *c = hmr_default_ctx();
+	if (!c) { hmr_set_error("hmr_gpu_prim_multi_sad: no device"); return HMR_GPU_ERR_NO_DEVICE; }
+	HIP_TRY(hipSetDevice(c->device));
+	struct Bufs {
+		void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+		~Bufs() { for (void *q : p) if (q) (void)hipFree(q); }
+	} b;
+	const size_t nres = (size_t)ncalls * maxc;
+	HIP_TRY(hipMalloc(&b.p[0], 64 * 64));
+	HIP_TRY(hipMalloc(&b.p[1], plane_bytes));
+	HIP_TRY(hipMalloc(&b.p[2], nres * 8));
+	HIP_TRY(hipMalloc(&b.p[3], nres * 4));
+	HIP_TRY(hipMemsetAsync(b.p[0], 0, 64 * 64, c->stream));
+	HIP_TRY(hipMemcpyAsync(b.p[0], src, (size_t)64 * n, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(b.p[1], plane, plane_bytes, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(b.p[2], cand_off, nres * 8, hipMemcpyHostToDevice, c->stream));
+	hipLaunchKernelGGL(k_primtest_multi_sad, dim3(ncalls), dim3(64), 0, c->stream, maxc, (const uint8_t *)b.p[0], (const uint8_t *)b.p[1], (const long long *)b.p[2], stride, n, (uint32_t *)b.p[3]);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, b.p[3], nres * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return HMR_GPU_OK;
 }
 
 }  // extern "C"

@@ -955,6 +955,58 @@ void hmr_gpu_prim_itransform(int16_t *block, int16_t *coeff, int block_stride, i
 void hmr_gpu_prim_quant(int16_t *src, int16_t *dst, int16_t *delta_u, int scan_mode, int depth, int comp, int is_intra, int slice_is_intra, int sign_hiding, int *ac_sum,
 			int cu_size, int per, int rem);
 void hmr_gpu_prim_inv_quant(int16_t *src, int16_t *dst, int depth, int comp, int is_intra, int cu_size, int per, int rem);
+/* The motion search's multi-candidate byte SAD (multi_sad_u8<MAXC>, the instantiations the walk uses: maxc = 4, 8, 9), every result.  src: the source block, n rows at a pitch
+ * of 64 bytes (64 x n bytes are read); plane: plane_bytes bytes; cand_off: ncalls lists of maxc byte offsets into the plane, -1 = a candidate that is skipped (a NULL pointer
+ * in the walk: its result is 0); stride: the plane's row pitch; n: 8, 16, 32 or 64; out: ncalls x maxc sums.  One launch, a workgroup per list.  HMR_GPU_ERR_ARG (nothing is
+ * launched) for another maxc or n, a stride below 1, or a candidate block that does not lie inside the plane. */
+int hmr_gpu_prim_multi_sad(int maxc, const uint8_t *src, const uint8_t *plane, size_t plane_bytes, const int64_t *cand_off, int ncalls, int stride, int n, uint32_t *out);
+
+/* ------------------------------------------------------------------------------------------------
+ * 16. Test aid: the device-only forms of the CTU walk, one step at a time on a synthetic worker
+ *     The merge tiles (homerhevc_amd/csrc/enc/enc_quad.h quad_chain: the inter TU chains of all merge slots of an 8 x 8 or 16 x 16 CU in one matrix-core tile) and the
+ *     two-halves instantiation of the inter TU chain (encode_inter_tu<PairGrp>: the helper wavefront's U and V plane side by side) exist on the device only.  This entry
+ *     lays one worker's LDS out as k_encode_pool does, fills what a step reads from the case, runs the step as the walk calls it and returns what it left
+ *     (tests/test_gpu_walk_forms.py).  Host pointers, synchronous, default context: one upload, one launch, one download per call.
+ *     arena: every byte the cases read, addressed by byte offsets:
+ *       curr, pred   6144 bytes each: the worker's source / prediction windows of the CTU - 64 x 64 luma at pitch 64, then U and V, 32 x 32 at pitch 32 (multiples of 4;
+ *                    pred may be -1 for a QUAD step, which does not read it);
+ *       sub_y, sub_c FrameCtx::sub_y / sub_c[2]: the first valid sample of plane 0 of the phase planes in the addressing of section 13 (row y of luma plane f starts at
+ *                    (y * 16 + f) * stride_y, chroma (y * 64 + f) * stride_c); a QUAD step reads, for slot s, the N x N bytes at
+ *                    luma:   sub_y + ((mv.y & 3) * 4 + (mv.x & 3)) * stride_y + (ctu_y + y + (mv.y >> 2)) * 16 * stride_y + ctu_x + x + (mv.x >> 2),
+ *                    chroma: sub_c[p] + ((mv.y & 7) * 8 + (mv.x & 7)) * stride_c + ((ctu_y >> 1) + yc + (mv.y >> 3)) * 64 * stride_c + (ctu_x >> 1) + xc + (mv.x >> 3)
+ *                    with (x, y) / (xc, yc) the node's place in the CTU and mv = mv[s] (all four slots are read).
+ *     node: the partition node (breadth first: 5 .. 20 the 16 x 16 CUs, 21 .. 84 the 8 x 8 CUs, both in z-order).  Steps:
+ *       QUAD8_Y / QUAD8_C      quad_chain<8, luma> / quad_chroma_job(8) on an 8 x 8 CU: four slots;
+ *       QUAD16_Y / QUAD16_C    quad_chain<16, luma> for slot one_slot / quad_chroma_job(16) on a 16 x 16 CU: two slots;
+ *       TU                     encode_inter_tu<WaveGrp> for component comp: the node as one TU at its own depth, the prediction from the prediction window;
+ *       TU_PAIR                encode_inter_tu<PairGrp>, U and V as helper_serve calls it.
+ *     The two TU steps run the templates under group types of the harness's own, derived from WaveGrp and PairGrp (as WaveGrpLat is): every choice in the chain is by
+ *     G::n, so the statements are the walk's, but the machine code is a second instantiation of them, not the one inside k_encode_pool (whose registers, scratch and
+ *     inlining a further caller of its instantiations would change).  The QUAD steps run the walk's own instantiations.
+ *     out[i]: per slot (a TU step: slot 0) and component distortion, level sum, no-residual distortion and cbf; pred / rec / lv: the slot's prediction, reconstruction and
+ *     final levels, row by row - a luma step's N x N block, a chroma step's U block followed by its V block (a TU step on V alone: at the V block's place); stray (TU steps):
+ *     32-bit words of the worker's windows in HBM (WorkSlow) outside the TU's level and reconstruction areas that the step changed.  Fields a step does not write are 0.
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is launched: a field outside its range, a node of the wrong size, a window or a
+ *     prediction block that does not lie inside the arena.
+ * ------------------------------------------------------------------------------------------------ */
+enum hmr_gpu_walk_step { HMR_GPU_WALK_QUAD8_Y = 1, HMR_GPU_WALK_QUAD8_C, HMR_GPU_WALK_QUAD16_Y, HMR_GPU_WALK_QUAD16_C, HMR_GPU_WALK_TU, HMR_GPU_WALK_TU_PAIR };
+typedef struct hmr_gpu_walk_case {
+	int32_t step, node, comp, one_slot;
+	int32_t qp, ctu_x, ctu_y, slice_type;            /* the node's QP; CtuPublic::x / y; 1 = P, 2 = I */
+	int32_t sign_hiding, chroma_qp_offset, stride_y, stride_c;
+	int32_t mv[4][2];                                /* QuadScratch::mv: x, y in quarter samples */
+	double avg_dist, chroma_weight;
+	int64_t sub_y, sub_c[2], curr, pred;
+} hmr_gpu_walk_case;
+typedef struct hmr_gpu_walk_out {
+	uint32_t dist[4][3];
+	int32_t sum[4][3];
+	uint32_t raw[4][3], cbf[4][3];
+	uint32_t stray, reserved[15];
+	uint8_t pred[4][256];
+	int16_t rec[4][256], lv[4][256];
+} hmr_gpu_walk_out;
+int hmr_gpu_walk_forms(const hmr_gpu_walk_case *cases, int ncases, const uint8_t *arena, size_t arena_bytes, hmr_gpu_walk_out *out);
 
 #ifdef __cplusplus
 }
