@@ -278,6 +278,11 @@ HENC_HD bool bg_take(const G g, Enc &__restrict__ e, int ni, int *mode, int *bit
 #define HENC_HELPERS(e) false
 #endif
 
+// Is this picture decided with full RDO?  Every test of Seq::rd_mode against RDM_FULL in the code a group runs goes through here: for a group compiled without full RDO
+// (G::rdfull false, enc_platform.h WaveGrpLean) the answer is a constant and the code behind it is not there.
+template <class G>
+HENC_INLINE bool rd_full(const G, const Seq &S) { return G::rdfull && S.rd_mode == RDM_FULL; }
+
 // The quadtree walks (enc_ctu.h, enc_inter.h, enc_intra.h) keep a state (0 .. 4: which child is next) and a running cost per depth and address both with the current depth.  Registers cannot be
 // indexed with a run-time value: as arrays they lived in private memory, a trip to scratch per access (seen in the ISA).  DepthState packs the five states into
 // one word; DepthCosts keeps five scalars and selects with compares.  Both are plain values (nothing takes their address).

@@ -427,7 +427,7 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 				// the intra evaluation below starts with a mode search that depends on nothing the motion search and the inter transform tree change: the helper
 				// starts on it now (enc_common.h bg_post), for the CU sizes whose intra evaluation does not depend on the motion search's SAD
 				if constexpr (G::bg)
-					if (NHELP == 1 && perf_fast_skip && curr_depth >= perf_min_depth && !is_skipped && q.size < 32 && S.rd_mode != RDM_FULL && e.f->lockstep) bg_post(g, e, curr, curr_depth);
+					if (NHELP == 1 && perf_fast_skip && curr_depth >= perf_min_depth && !is_skipped && q.size < 32 && !rd_full(g, S) && e.f->lockstep) bg_post(g, e, curr, curr_depth);
 				if (curr_depth >= perf_min_depth) {
 					if (!is_skipped) sad = (uint32_t)cu_motion_estimation(g, e, curr_depth, position, PART_2Nx2N, action);   // timed inside (PF_ME_INT / PF_ME_SUB)
 					if (!is_skipped && (q.size < 64 || sad < 100u * num_part_in_cu)) {
@@ -482,7 +482,7 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 						{ HENC_PROF_T0(); cl = encode_intra_luma(g, e, curr_depth, position, PART_2Nx2N); HENC_PROF_ADD(e, PF_INTRA_TU); } HENC_TRACE_PW(e, "iluma");
 						const double add_lb = hclip(avg_distortion - 400, 40., avg_distortion) / 1.75 * curr_depth;
 						const double lb = intra_cost_with_ratio((double)cl, .15, add_lb, cost_rd(e.f->avg_dist, nd.sum));
-						if (S.rd_mode != RDM_FULL && e.f->lockstep && lb > cost + 1.) intra_dist = cl;
+						if (!rd_full(g, S) && e.f->lockstep && lb > cost + 1.) intra_dist = cl;
 						else {
 							uint32_t cc;
 							{ HENC_PROF_T0(); cc = encode_intra_chroma(g, e, curr_depth, position, PART_2Nx2N); HENC_PROF_ADD(e, PF_INTRA_CHROMA); } HENC_TRACE_PW(e, "ichroma");
@@ -629,7 +629,7 @@ HENC_HD uint32_t motion_intra_ctu(const G g, Enc &__restrict__ e)
 	const int initial_depth = 0, initial_position = 0;
 	depth_state.set(0, initial_position);
 	e.w->thread_seen_intra = 1;   // (every lane stores the same value) hmr_motion_intra.c:1783: from now on this thread's shadow CTU reads "intra"
-	if (S.rd_mode == RDM_FULL) {      // motion_intra :1993: the shadow CTU starts as a copy of the CTU's descriptor (its side-info pointers at the CTU's arrays), all INTRA
+	if (rd_full(g, S)) {      // motion_intra :1993: the shadow CTU starts as a copy of the CTU's descriptor (its side-info pointers at the CTU's arrays), all INTRA
 		bytes_set(g, e.wrd->rd_pred_mode, PM_INTRA, NPART);
 		e.rd_luma_depth = -1;
 		e.rd_chroma_state = 0;

@@ -158,7 +158,7 @@ HENC_HD int intra_mode_search(const G g, Enc &__restrict__ e, int ni, int depth,
 	e.rd_luma_depth = curr_depth;      // (homer_loop1_motion_intra :1103 aims the shadow CTU's luma directions at this depth's buffer "for rd")
 	intra_neighbour_dirs(e, ni, curr_depth, dirs, src);
 	mpm_from_dirs(dirs[0], dirs[1], preds);
-	const int rd_fast = e.seq->rd_mode == RDM_FAST ? 1 : (e.seq->rd_mode == RDM_FULL ? 2 : 0);      // (how the walk prices a direction)
+	const int rd_fast = e.seq->rd_mode == RDM_FAST ? 1 : (rd_full(g, *e.seq) ? 2 : 0);      // (how the walk prices a direction)
 	// a search whose candidate list rests on a guess is logged (every lane writes the same values)
 	SearchLog *lg = nullptr;
 	e.last_slog = -1;
@@ -247,7 +247,7 @@ HENC_HD uint32_t encode_intra_tu(const G g, Enc &__restrict__ e, int ni, int dep
 	nd.intra_cbf[COMP_Y] = (sum ? 1 : 0) << tr;
 	nd.intra_tr_idx = tr;
 	nd.intra_mode[COMP_Y] = cu_mode;
-	if (e.seq->rd_mode == RDM_FULL) set_intra_info_buffs(g, e, curr_depth, ni);      // :1041: what the bit estimate of this node reads
+	if (rd_full(g, *e.seq)) set_intra_info_buffs(g, e, curr_depth, ni);      // :1041: what the bit estimate of this node reads
 	if (sum) {
 		lin_copy_nosync(g, iquant, quant, n * n);
 		dequantize(g, HENC_FT(e), e.T, iquant, iquant, curr_depth, COMP_Y, 1, n, per, rem);
@@ -270,7 +270,7 @@ HENC_WALK_FN HENC_HD uint32_t encode_intra_luma(const G g, Enc &__restrict__ e, 
 	int cu_mode;
 	double search_cost;
 	int bitcost_cu_mode;
-	const bool rd_full = S.rd_mode == RDM_FULL;
+	const bool rd_full = henc::rd_full(g, S);
 	if (rd_full) {      // :1287: the shadow CTU's partition size and prediction depth of this CU
 		const Geo &tq = e.geo[top_ni];
 		bytes_set(g, &e.wrd->rd_part_size[tq.abs_index], part_size_type, tq.num_part);
@@ -432,7 +432,7 @@ HENC_WALK_FN HENC_HD uint32_t encode_intra_luma(const G g, Enc &__restrict__ e, 
 			g.sync();
 		}
 	}
-	if (S.rd_mode != RDM_FULL) {
+	if (!rd_full) {
 		const double correction = calc_mv_correction(tn.qp, e.f->avg_dist);
 		if (e.last_slog >= 0) e.ctu_g->slog[e.last_slog].tu_cost = tn.cost;
 		return intra_luma_cost(tn.cost, bitcost_cu_mode, correction);
@@ -560,7 +560,7 @@ HENC_WALK_FN HENC_HD uint32_t encode_intra_chroma(const G g, Enc &__restrict__ e
 			distortion += sad_v[mi];
 			cost += distortion;
 			uint32_t bit_cost = mode_list[mi] == DM_CHROMA_IDX ? 1 : 12;
-			if (S.rd_mode == RDM_FULL) {      // hmr_motion_intra_chroma.c:228: the candidate goes into the depth's direction buffer and is priced by the counter
+			if (rd_full(g, S)) {      // hmr_motion_intra_chroma.c:228: the candidate goes into the depth's direction buffer and is priced by the counter
 				const Geo &sq = e.geo[curr];
 				bytes_set(g, &w.intra_mode_buffs[COMP_CHR][depth][sq.abs_index], mode_list[mi], sq.num_part);
 				RdViews &rv = rd_views_of(e);
@@ -676,14 +676,14 @@ HENC_WALK_FN HENC_HD uint32_t encode_intra_chroma(const G g, Enc &__restrict__ e
 			if (nxn) top = e.geo[top].parent;
 		}
 		cost = distortion;
-		if (S.rd_mode == RDM_FULL && cost < best_cost) {      // :417: the chroma syntax of the CU with the winner of the search
+		if (rd_full(g, S) && cost < best_cost) {      // :417: the chroma syntax of the CU with the winner of the search
 			const Geo &tq = e.geo[top];
 			bytes_set(g, &w.intra_mode_buffs[COMP_CHR][depth][tq.abs_index], best_modes[0], tq.num_part);
 			RdViews &rv = rd_views_of(e);
 			rd_make_views(g, e, rv, depth, depth, w.cbf_chroma[0], w.cbf_chroma[1], depth, nullptr, tq_ptr(w, qwnd, COMP_U), tq_ptr(w, qwnd, COMP_V));
 			const uint32_t bits = rd_get_intra_bits_qt(g, e, rv, top, 0);
 			cost += (uint32_t)(bits * e.f->lambda + .5);
-		} else if (S.rd_mode != RDM_FULL && cost < best_cost) {
+		} else if (!rd_full(g, S) && cost < best_cost) {
 			const double correction = calc_mv_correction(node_of(e, top).qp, e.f->avg_dist);
 			cost += (uint32_t)(bit_cost * correction + .5);
 		}

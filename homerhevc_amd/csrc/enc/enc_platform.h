@@ -49,6 +49,13 @@ struct WaveGrp {
 	int tid;
 	static constexpr int n = 64;
 	static constexpr bool bg = false;      // (WaveGrpLat: the walk of the latency kernel, whose helper runs background intra searches - enc_common.h bg_post)
+	// does the code compiled for this group carry full RDO (rd_mode = RD_FULL: enc_rdo.h and its hooks in the walk - rd_full below)?  WaveGrpLean: it does not.
+	// (-DHENC_NO_RDFULL: an experiment build that folds it out of every device group, for comparing against; hmr_gpu_enc_create of such a library refuses RD_FULL)
+#if defined(HENC_NO_RDFULL)
+	static constexpr bool rdfull = false;
+#else
+	static constexpr bool rdfull = true;
+#endif
 	// the group is ONE wavefront: its lanes run in lockstep, so ordering its own memory operations is all a "barrier" has to do (the workgroup may hold
 	// helper wavefronts that are doing something else, see HelperBox in enc_common.h)
 	__device__ __forceinline__ void sync() const
@@ -91,15 +98,25 @@ struct WaveGrp {
 struct WaveGrpLat : WaveGrp {
 	static constexpr bool bg = true;
 };
+// ... and as the group of the throughput kernel (k_encode_pool), which only gets launches without an RD_FULL picture (launch_pool, k_encode_object.inc): its walk is
+// compiled without full RDO - a tenth of the P-slice walk and a quarter of the I-slice walk are that code, spread through them behind tests of Seq::rd_mode.  A walk
+// that only passes it still pays: measured, the lean walk executes 3.5 % fewer instructions (the tests, their scalar loads and jumps, what the compiler kept alive
+// across the dead regions) and a batch step is about 1 % shorter; the instruction-cache miss rate does not move (profiles/r07_history.md).  Launches with an
+// RD_FULL picture run k_encode_full, the generic walk.
+struct WaveGrpLean : WaveGrp {
+	static constexpr bool rdfull = false;
+};
 
 // Two groups of 32 lanes in one wavefront, each with a block of its own (the helper's two chroma planes of a small TU: a 4 x 4 or 8 x 8 chain keeps 4 - 16 lanes busy,
 // and two of them one after the other made the helper the slower side of a small CU).  The halves run the same code on different operands; where their control flow
 // parts (one plane has levels, the other has not) the hardware masks the lanes, and nothing in the group operations crosses the halves: sums add up a half's two
 // 16-lane rows, the ballot is the half's 32 bits.
-struct PairGrp {
+template <class P>      // (P: the wavefront's group, whose rdfull trait the halves keep)
+struct PairGrpOf {
 	int tid, half;           // lane within the half, the half (0 / 1)
 	static constexpr int n = 32;
 	static constexpr bool bg = false;
+	static constexpr bool rdfull = P::rdfull;
 	__device__ __forceinline__ void sync() const
 	{
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -119,6 +136,7 @@ struct PairGrp {
 	__device__ __forceinline__ uint64_t ballot(bool p) const { const uint64_t m = __ballot(p); return half ? m >> 32 : m & 0xffffffffull; }
 	__device__ __forceinline__ uint32_t any(bool p) const { return ballot(p) != 0; }
 };
+using PairGrp = PairGrpOf<WaveGrp>;
 
 #endif
 
@@ -229,6 +247,7 @@ struct CpuGrp {
 	static constexpr int tid = 0;
 	static constexpr int n = 1;
 	static constexpr bool bg = false;
+	static constexpr bool rdfull = true;
 	void sync() const {}
 	uint32_t sum(uint32_t v) const { return v; }
 	int64_t sum64(int64_t v) const { return v; }

@@ -151,7 +151,10 @@ static_assert(LDS_BYTES - LDS_RD == 0 && LDS_WORK == 0 && LDS_NODES == 0 && LDS_
 
 // a helper wavefront: run the jobs the worker posts (HelperBox, enc_common.h) until it says quit
 // one ordinary job of helper h (the one with sequence number seq, which has been posted); false: it was HJOB_QUIT
-__device__ __forceinline__ bool helper_serve(HelperBox *box, int h, int16_t *scratch, const WaveGrp g, int seq)
+// (G: the group of the worker's walk, or - the latency kernel - WaveGrp: a kernel's helpers and its worker then call the same instantiations of the out-of-line block
+// primitives, as they did when there was one group type; what a second copy of those 45 KB would cost a batch has not been measured)
+template <class G>
+__device__ __forceinline__ bool helper_serve(HelperBox *box, int h, int16_t *scratch, const G g, int seq)
 {
 	extern __shared__ __align__(16) uint8_t lds[];
 	Enc &e = *(Enc *)(lds + LDS_OFF_ENC + (1 + h) * LDS_ENC_BYTES);      // (this helper's own context; LDS starts zeroed)
@@ -179,7 +182,7 @@ __device__ __forceinline__ bool helper_serve(HelperBox *box, int h, int16_t *scr
 			if (NHELP == 1 && a[1] == COMP_UV && e.geo[a[0]].size_chroma <= 8) {
 				// both planes of a small TU side by side, a half of the wavefront each (enc_platform.h PairGrp): one after the other they made the helper the
 				// slower side of every 8 x 8 and 16 x 16 CU (two chains against the worker's one)
-				const PairGrp pg{g.tid & 31, g.tid >> 5};
+				const PairGrpOf<G> pg{g.tid & 31, g.tid >> 5};
 				const uint32_t d = encode_inter_tu(pg, e, a[0], COMP_U + pg.half, a[2], a[3], &sum, &raw, pg.half * 512);
 				r0 = (uint32_t)__builtin_amdgcn_readlane((int)d, 0); r1 = (uint32_t)__builtin_amdgcn_readlane(sum, 0); r2 = (uint32_t)__builtin_amdgcn_readlane((int)raw, 0);
 				r3 = (uint32_t)__builtin_amdgcn_readlane((int)d, 32); r4 = (uint32_t)__builtin_amdgcn_readlane(sum, 32); r5 = (uint32_t)__builtin_amdgcn_readlane((int)raw, 32);
@@ -303,10 +306,10 @@ __device__ __attribute__((noinline)) bool helper_bg_search(HelperBox *box, int h
 // LAT: the kernel of launches with at most one worker per CU (k_encode_pool_lat), whose helpers also run the background search; the throughput kernel keeps the plain
 // loop (the out-of-line dispatch and the second poll cost a batch 8 % when both kernels shared one loop - the code the helper wavefronts run counts: two CUs share an
 // instruction cache)
-template <bool LAT>
+template <bool LAT, class G = WaveGrp>
 __device__ __attribute__((noinline)) void helper_loop(HelperBox *box, int h, int16_t *scratch)      // (out of line, as it was before it became a template: inlined it costs the kernel 38 spilled registers)
 {
-	WaveGrp g{(int)(threadIdx.x & 63)};
+	G g{(int)(threadIdx.x & 63)};
 	if constexpr (!LAT) {
 		for (int seq = 1;; seq++) {
 			while (__hip_atomic_load(&box->cmd[h], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq) __builtin_amdgcn_s_sleep(1);   // (two workgroups share a CU now: a helper that spins takes issue cycles from the other workgroup's worker on its SIMD)
@@ -331,7 +334,7 @@ __device__ __attribute__((noinline)) void helper_loop(HelperBox *box, int h, int
 
 // A workgroup is a row worker (wavefront 0) and its two helpers.  rows_enter sets the mailbox up and sends the helper wavefronts into their service loop; it
 // returns true on the worker only.  release_helpers lets them go (without it the workgroup never ends).
-template <bool LAT = false>
+template <bool LAT = false, class G = WaveGrp>
 __device__ __forceinline__ bool rows_enter(unsigned lds_bytes)
 {
 	extern __shared__ __align__(16) uint8_t lds[];
@@ -341,7 +344,7 @@ __device__ __forceinline__ bool rows_enter(unsigned lds_bytes)
 	for (int i = (int)threadIdx.x; i < (int)(lds_bytes / 4); i += ENC_THREADS) ((uint32_t *)lds)[i] = 0;
 	__syncthreads();
 	if (wave > 0) {
-		helper_loop<LAT>(box, wave - 1, (int16_t *)(lds + LDS_WORK + LDS_NODES) + (wave - 1) * HSCRATCH_ELEMS);
+		helper_loop<LAT, G>(box, wave - 1, (int16_t *)(lds + LDS_WORK + LDS_NODES) + (wave - 1) * HSCRATCH_ELEMS);
 		return false;
 	}
 	return true;
@@ -532,7 +535,7 @@ __device__ void pool_encode_ctu(const EncDev &d, Enc &__restrict__ e, const G g,
 	wave_copy_words(&e.w->intra_mode_buffs[0][0][0], d.rowstate + (size_t)me * ROW_STATE_BYTES, MODE_STATE_BYTES, g.tid);
 	wave_copy_quads(e.w->pred_y, d.rowstate + (size_t)me * ROW_STATE_BYTES + MODE_STATE_BYTES, PRED_STATE_BYTES, g.tid);
 	if (g.tid == 0) e.w->thread_seen_intra = d.thread_seen[me];
-	if (S.rd_mode == RDM_FULL) {
+	if (rd_full(g, S)) {
 		// RD_FULL: the thread's shadow CTU keeps its prediction modes from CTU to CTU - all INTRA once the thread has taken the intra walk (motion_intra :2003),
 		// the zeroes it was created with before (the worker's fast memory is not the thread's: enc_rdo.h)
 		const int seen = d.thread_seen[me];
@@ -548,7 +551,7 @@ __device__ void pool_encode_ctu(const EncDev &d, Enc &__restrict__ e, const G g,
 	// rate control: the bits and the number of the CTUs the reference has entropy coded when this step starts
 	uint32_t rc_bits = 0;
 	int rc_ctus = 0;
-	if (S.rd_mode == RDM_FULL) {
+	if (rd_full(g, S)) {
 		const int code = d.rd_src[n], kind = code >> 28, slot = (code >> 24) & 15;
 		const size_t off = (size_t)(code & 0x00ffffff) * RD_CTX_BYTES;
 		e.rd_ctx = kind == 3 ? d.rd_ring + ((size_t)slot * S.nctu) * RD_CTX_BYTES + off : d.rd_init + (size_t)(kind ? 1 + slot : 0) * RD_CTX_BYTES;
@@ -679,15 +682,17 @@ __device__ __attribute__((noinline)) int pool_post_drain_run(const EncDev &d, co
 	return ran;
 }
 
-template <bool LAT>
+// G: the group of the worker's walk - WaveGrpLean (k_encode_pool), WaveGrpLat (k_encode_pool_lat) or WaveGrp (k_encode_full): enc_platform.h
+template <class G>
 __device__ __forceinline__ void encode_pool_body(const EncDev *devs, int nseq, int *state, int *finished, WorkSlow *slow, unsigned long long watchdog_ticks, unsigned lds_bytes)
 {
 	// finished[0]: pictures whose last task is done; finished[1]: abort - a worker has waited longer than the watchdog allows (a faulted or starved peer): everybody
 	// leaves and the host reports an error instead of the launch hanging
 	unsigned long long t_start = wall_clock64();      // when this worker last had something to do (the watchdog's clock)
-	if (!rows_enter<LAT>(lds_bytes)) return;
+	constexpr bool LAT = G::bg;
+	if (!rows_enter<LAT, typename std::conditional<LAT, WaveGrp, G>::type>(lds_bytes)) return;      // (the latency kernel's helpers: the plain group, its loop has the background search)
 	extern __shared__ __align__(16) uint8_t lds[];
-	typename std::conditional<LAT, WaveGrpLat, WaveGrp>::type g{(int)(threadIdx.x & 63)};      // (the latency kernel's walk is an instantiation of its own: enc_platform.h)
+	G g{(int)(threadIdx.x & 63)};
 	Work *lw = (Work *)lds;
 	HelperBox *box = (HelperBox *)(lds + LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU);
 	Seq *lseq = (Seq *)(lds + LDS_WORK + LDS_NODES + LDS_GEO);
@@ -856,14 +861,19 @@ __device__ __forceinline__ void encode_pool_body(const EncDev *devs, int nseq, i
 	for (int h = 0; h < NHELP; h++) hseq[h] = e.hseq[h];
 	release_helpers(hseq);
 }
-// the throughput kernel (many pictures, four workers per CU) and the latency kernel (at most one worker per CU: the helpers also run the background intra search)
+// the throughput kernel (many pictures, four workers per CU, none of them RD_FULL: the walk without full RDO), the generic kernel of launches with an RD_FULL picture,
+// and the latency kernel (at most one worker per CU: the helpers also run the background intra search); launch_pool (k_encode_object.inc) chooses
 __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(HENC_WAVES_PER_EU))) void k_encode_pool(const EncDev *devs, int nseq, int *state, int *finished, WorkSlow *slow, unsigned long long watchdog_ticks, unsigned lds_bytes)
 {
-	encode_pool_body<false>(devs, nseq, state, finished, slow, watchdog_ticks, lds_bytes);
+	encode_pool_body<WaveGrpLean>(devs, nseq, state, finished, slow, watchdog_ticks, lds_bytes);
+}
+__global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(HENC_WAVES_PER_EU))) void k_encode_full(const EncDev *devs, int nseq, int *state, int *finished, WorkSlow *slow, unsigned long long watchdog_ticks, unsigned lds_bytes)
+{
+	encode_pool_body<WaveGrp>(devs, nseq, state, finished, slow, watchdog_ticks, lds_bytes);
 }
 __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(HENC_WAVES_PER_EU))) void k_encode_pool_lat(const EncDev *devs, int nseq, int *state, int *finished, WorkSlow *slow, unsigned long long watchdog_ticks, unsigned lds_bytes)
 {
-	encode_pool_body<true>(devs, nseq, state, finished, slow, watchdog_ticks, lds_bytes);
+	encode_pool_body<WaveGrpLat>(devs, nseq, state, finished, slow, watchdog_ticks, lds_bytes);
 }
 
 // the true chains in raster order: threads 0..255 one unit column of the mode buffers each, thread 256 the intra counter

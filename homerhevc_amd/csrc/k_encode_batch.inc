@@ -152,7 +152,7 @@ int batch_launch(hmr_gpu_enc **encs, int n, const int *slots, const int *image_t
 	hipLaunchKernelGGL(k_batch_stage, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->h_devs, (const FrameCtx *)lead->h_frames, (EncDev *)lead->d_batch, lead->d_frames);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(lead->ev_batch0, bst));
-	if ((rc = launch_pool(lead, n, rows_total, needs_rd, bst))) return rc;
+	if ((rc = launch_pool(lead, lead->h_devs, n, rows_total, needs_rd, bst))) return rc;
 	(void)hipEventRecord(lead->ev_batch1, bst);
 	hipLaunchKernelGGL(k_gather_results, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->d_batch, lead->d_gather, pitch, (const int *)(lead->d_pool_state + BATCH_MAX * POOL_STRIDE));
 	HIP_TRY(hipGetLastError());
@@ -466,7 +466,7 @@ extern "C" int hmr_gpu_enc_encode_chain(hmr_gpu_enc **encs, int n, hmr_gpu_enc *
 	hipLaunchKernelGGL(k_batch_stage, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->h_devs, (const FrameCtx *)lead->h_frames, (EncDev *)lead->d_batch, lead->d_frames);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(lead->ev_batch0, bst));
-	if ((rc = launch_pool(lead, n, rows_total, needs_rd, bst))) return rc;
+	if ((rc = launch_pool(lead, lead->h_devs, n, rows_total, needs_rd, bst))) return rc;
 	(void)hipEventRecord(lead->ev_batch1, bst);
 	hipLaunchKernelGGL(k_gather_results, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->d_batch, lead->d_gather, pitch, (const int *)(lead->d_pool_state + BATCH_MAX * POOL_STRIDE));
 	HIP_TRY(hipGetLastError());

@@ -147,6 +147,7 @@ struct hmr_gpu_enc {
 	int *d_pool_state = nullptr;                         // k_encode_pool: per picture of the launch the open step and the steps' ticket / done counters, then the finished-pictures counter
 	WorkSlow *d_pool_slow = nullptr;                     // the pool workers' transform / decoded windows
 	int pool_workers = 0;
+	int last_pool_kernel = -1;                           // (lead) which kernel the last pool launch ran - 0: k_encode_pool_lat, 1: k_encode_pool, 2: k_encode_full; -1: none yet
 	// picture conversion (picture_io.h, k_encode_picture_io.inc): the job tables and events of the k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim launches this encoder leads - as the first
 	// encoder of a load / export call, and alone in the host-memory entries (widen_packed, narrow_packed)
 	JobRing<IngestJob> ingest;
@@ -325,8 +326,9 @@ static int pool_inflight(const Seq &s, int raster = 0)
 	const int by_step = s.hctu < (s.wctu + 1) / 2 ? s.hctu : (s.wctu + 1) / 2;
 	return s.bitrate_mode != 0 ? (by_step + 1) / 2 : by_step;
 }
-// the row-per-thread schedule of n pictures (their EncDev records already at lead->d_batch) as ONE pool launch on `st`; rows_total: the sum of their pool_inflight()
-int launch_pool(hmr_gpu_enc *lead, int n, int rows_total, bool needs_rd, hipStream_t st)
+// the row-per-thread schedule of n pictures (their EncDev records already at lead->d_batch, `host` the copies they were made from) as ONE pool launch on `st`;
+// rows_total: the sum of their pool_inflight(); needs_rd: one of them at least is RD_FULL
+int launch_pool(hmr_gpu_enc *lead, const EncDev *host, int n, int rows_total, bool needs_rd, hipStream_t st)
 {
 	if (!lead->n_cus) HIP_TRY(hipDeviceGetAttribute(&lead->n_cus, hipDeviceAttributeMultiprocessorCount, lead->ctx->device));
 	// a worker's LDS: without RD_FULL pictures in the launch the RD arrays at its end are left out (a fourth worker then fits a CU)
@@ -344,6 +346,15 @@ int launch_pool(hmr_gpu_enc *lead, int n, int rows_total, bool needs_rd, hipStre
 	int workers = rows_total < cap ? rows_total : cap;                        // (a picture never has more CTUs in flight than rows)
 	if (workers < 1) workers = 1;
 	if (getenv("HENC_POOL_WORKERS") && atoi(getenv("HENC_POOL_WORKERS")) > 0 && atoi(getenv("HENC_POOL_WORKERS")) < workers) workers = atoi(getenv("HENC_POOL_WORKERS"));      // (experiment)
+	// at most one worker per CU: the latency kernel, whose helpers also run a CU's intra mode search under its inter evaluation (enc_common.h bg_post).  Otherwise the
+	// throughput kernel, whose walk is compiled without full RDO (enc_platform.h WaveGrpLean) - or, with an RD_FULL picture in the launch, the generic kernel.
+	const int kernel = workers <= lead->n_cus ? 0 : (needs_rd ? 2 : 1);
+	if (kernel == 1)      // (set_frame gives the record of an RD_FULL picture, and no other, the sources of its bit estimates)
+		for (int i = 0; i < n; i++)
+			if (host[i].rd_src) {
+				hmr_set_error("k_encode_pool: picture %d of the launch is RD_FULL, and this kernel's walk is compiled without full RDO (needs_rd was not set)", i);
+				return HMR_GPU_ERR_ARG;
+			}
 	if (!lead->d_pool_state) HIP_TRY(hipMalloc((void **)&lead->d_pool_state, sizeof(int) * (BATCH_MAX * POOL_STRIDE + 4)));
 	if (lead->pool_workers < workers) {
 		if (lead->d_pool_slow) (void)hipFree(lead->d_pool_slow);
@@ -358,16 +369,15 @@ int launch_pool(hmr_gpu_enc *lead, int n, int rows_total, bool needs_rd, hipStre
 	double watchdog_s = getenv("HENC_WATCHDOG_S") ? atof(getenv("HENC_WATCHDOG_S")) : 120.0;
 	if (!(watchdog_s > 0)) watchdog_s = 120.0;
 	const unsigned long long watchdog = (unsigned long long)(watchdog_s * 1e8);
-	// (at most one worker per CU: the latency kernel, whose helpers also run a CU's intra mode search under its inter evaluation - enc_common.h bg_post)
-	if (workers <= 256) hipLaunchKernelGGL(k_encode_pool_lat, dim3(workers), dim3(ENC_THREADS), lds_bytes, st, (const EncDev *)lead->d_batch, n, lead->d_pool_state, lead->d_pool_state + BATCH_MAX * POOL_STRIDE,
-			   lead->d_pool_slow, watchdog, (unsigned)lds_default);
-	else hipLaunchKernelGGL(k_encode_pool, dim3(workers), dim3(ENC_THREADS), lds_bytes, st, (const EncDev *)lead->d_batch, n, lead->d_pool_state, lead->d_pool_state + BATCH_MAX * POOL_STRIDE,
+	auto *const fn = kernel == 0 ? k_encode_pool_lat : (kernel == 1 ? k_encode_pool : k_encode_full);
+	hipLaunchKernelGGL(fn, dim3(workers), dim3(ENC_THREADS), lds_bytes, st, (const EncDev *)lead->d_batch, n, lead->d_pool_state, lead->d_pool_state + BATCH_MAX * POOL_STRIDE,
 			   lead->d_pool_slow, watchdog, (unsigned)lds_default);
 	const hipError_t launched = hipGetLastError();
 	if (launched != hipSuccess) {
 		hmr_set_error("k_encode_pool: %s", hipGetErrorString(launched));
 		return HMR_GPU_ERR_HIP;
 	}
+	lead->last_pool_kernel = kernel;
 	return HMR_GPU_OK;
 }
 
@@ -383,7 +393,7 @@ int run_ctu_passes(hmr_gpu_enc *e)
 		// wfpp_num_threads > 1: the synchronous wavefront, one launch, nothing to verify - the picture's CTUs as a pool of tasks (k_encode_pool)
 		if (!e->d_batch) HIP_TRY(hipMalloc((void **)&e->d_batch, BATCH_MAX * sizeof(EncDev)));
 		HIP_TRY(hipMemcpyAsync(e->d_batch, &e->d, sizeof(EncDev), hipMemcpyHostToDevice, st));
-		if ((rc = launch_pool(e, 1, e->raster ? pool_inflight(s, 1) : s.hctu, s.rd_mode == RDM_FULL, st))) return rc;      // (one picture: a worker per row, each on a CU of its own)
+		if ((rc = launch_pool(e, &e->d, 1, e->raster ? pool_inflight(s, 1) : s.hctu, s.rd_mode == RDM_FULL, st))) return rc;      // (one picture: a worker per row, each on a CU of its own)
 		HIP_TRY(hipEventRecord(e->ctx->ev1, st));
 		if ((rc = lockstep_collect(e))) return rc;      // (waits for the launch)
 		HIP_TRY(hipEventElapsedTime(&e->last_ms, e->ctx->ev0, e->ctx->ev1));
@@ -565,6 +575,13 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 		return HMR_GPU_ERR_ARG;
 	}
 	if (engine_index >= e->st.engines) { delete e; return HMR_GPU_ERR_ARG; }
+#if defined(HENC_NO_RDFULL)
+	if (e->seq.rd_mode == RDM_FULL) {      // (the experiment build of enc_platform.h: no kernel of it carries full RDO)
+		hmr_set_error("hmr_gpu_enc_create: this library was built with -DHENC_NO_RDFULL and cannot encode rd_mode RD_FULL");
+		delete e;
+		return HMR_GPU_ERR_ARG;
+	}
+#endif
 	if (e->cfg.bitrate_mode != 0) host_rc_init(e->cfg, e->seq, e->st);
 	g_plane_pool.encoder_created();      // (hmr_gpu_enc_destroy - also the guard's - takes it back)
 	struct Guard {               // a failure further down (HIP_TRY / DEV_ALLOC return) frees what has been allocated so far
@@ -606,6 +623,7 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_ctus, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
 	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_pool, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_pool_lat, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_full, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	HIP_TRY(hipEventCreate(&e->ev_frame));
 	HIP_TRY(hipEventCreate(&e->ev_ready));
 	HIP_TRY(hipEventCreate(&e->ev_batch0));
@@ -926,6 +944,8 @@ extern "C" int hmr_gpu_enc_last_stats(hmr_gpu_enc *e, int *passes, int *ctu_enco
 	if (frame_ms) *frame_ms = e->last_total_ms;
 	return HMR_GPU_OK;
 }
+
+extern "C" int hmr_gpu_enc_last_pool_kernel(hmr_gpu_enc *e) { return e ? e->last_pool_kernel : -1; }
 
 // profiling build: per CTU, 100 MHz timestamps of {wait start, encode start, first use of the intra share (0: none), end} in the row-per-thread schedule
 extern "C" int hmr_gpu_enc_timeline(hmr_gpu_enc *e, unsigned long long *out)

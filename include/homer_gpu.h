@@ -639,6 +639,10 @@ int hmr_gpu_enc_encode_batch(hmr_gpu_enc **encs, int n, const int *slots, const 
 int hmr_gpu_enc_encode_batch_pipelined(hmr_gpu_enc **encs, int n, const int *slots, const int *image_types, uint8_t **streams, const long *caps, long *stream_bytes);
 /* the last frame: passes of the CTU schedule, CTU encodes (>= the number of CTUs), device milliseconds of the CTU passes and of the whole frame */
 int hmr_gpu_enc_last_stats(hmr_gpu_enc *enc, int *passes, int *ctu_encodes, float *ctu_ms, float *frame_ms);
+/* which kernel ran the last pool launch this encoder led (alone, or as the first encoder of a batch call) - 0: the latency kernel (at most one worker per compute
+ * unit), 1: the throughput kernel, whose decision walk is compiled without full RDO (no RD_FULL picture in the launch), 2: the generic kernel (a launch with an
+ * RD_FULL picture); -1: none yet */
+int hmr_gpu_enc_last_pool_kernel(hmr_gpu_enc *enc);
 /* The one place where byte identity with the reference is not guaranteed, counted: a merge candidate whose vector points outside the padded reference picture
  * (more than 80 samples beyond the frame) is evaluated by the reference on whatever its thread's prediction window holds (check_rd_cost_merge_2nx2n leaves out
  * the motion compensation and nothing else, hmr_motion_inter.c:3651).  The window travels with the thread here too (the stream is the

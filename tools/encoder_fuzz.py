@@ -8,6 +8,8 @@ usage: tools/encoder_fuzz.py [--cases N] [--seed S] [--max-ctus M]        (print
        tools/encoder_fuzz.py --gpu ...                                     (GPU box: the device encoder, hmr_gpu_enc_encode, instead of the checker build; the
                                                                             compiled reference travels there as oracle/_ref/)
        ... --gpu --batch K                                                  (K cases per hmr_gpu_enc_encode_batch call: one launch for all their CTU stages)
+       ... --gpu --batch K --split-rd                                       (RD_FULL cases and the others in launches of their own: a large K then draws the throughput
+                                                                            kernel without full RDO AND the generic one - a mixed launch always runs the generic one)
        ... --gpu --engines-only --chain-sets M                              (several engines through hmr_gpu_enc_encode_chain, M objects per engine)
        ... --threads-only / --extra-keys / --max-cols C --max-rows R        (several WPP threads only; also draw me= and cqo=; larger CTU grids)
        ... --content noise,extremes,flat,motion,chroma (or all)             (the picture content of each case drawn from these tools/gen_yuv.py families)
@@ -131,6 +133,7 @@ def device(lib, ctx, width, height, frames, clip_seed, keys):
 
 
 SERIAL_POOL = False      # --serial-batch: one-thread cases as batches through hmr_gpu_enc_create_serial_pool
+POOL_KERNELS = {}        # --batch: launches per pool kernel (hmr_gpu_enc_last_pool_kernel: 0 latency, 1 throughput without full RDO, 2 generic)
 
 
 def device_batch(lib, group):
@@ -163,6 +166,8 @@ def device_batch(lib, group):
         caps = (C.c_long * n)(*[len(bufs[i]) for i in live])
         got = (C.c_long * n)()
         assert lib.hmr_gpu_enc_encode_batch(e_arr, n, slots, its, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
+        kernel = lib.hmr_gpu_enc_last_pool_kernel(e_arr[0])
+        POOL_KERNELS[kernel] = POOL_KERNELS.get(kernel, 0) + 1
         for k, i in enumerate(live):
             out[i].append(bufs[i].raw[:got[k]])
     stale = []
@@ -351,6 +356,7 @@ def main():
     ap.add_argument("--combos", action="store_true", help="only rate control / RD_FULL with one WPP thread or with several engines (accepted since round 6)")
     ap.add_argument("--engines-only", action="store_true", help="only cases with several engines and several WPP threads")
     ap.add_argument("--batch", type=int, default=1, help="with --gpu: this many cases per hmr_gpu_enc_encode_batch call (cases the batch call does not take are left out)")
+    ap.add_argument("--split-rd", action="store_true", help="with --gpu --batch N: the RD_FULL cases are batched among themselves, and so are the others")
     ap.add_argument("--tolerate-q12", action="store_true", help="do not count a differing case that had evaluations on a stale prediction window (the documented exception) in the exit code")
     ap.add_argument("--serial-batch", action="store_true", help="with --gpu --batch N: only cases with one WPP thread and one engine, created with hmr_gpu_enc_create_serial_pool and encoded N per batch call "
                                                                 "(the reference's single-thread order as a batch schedule)")
@@ -404,11 +410,16 @@ def main():
                 if int(c[4].get("rd", 0)) == 1 and int(c[4].get("bitrate_mode", 0)):
                     c[4].pop("bitrate_mode"); c[4].pop("bitrate", None)
         ok_cases = [c for c in cases if a.serial_batch or (int(c[4].get("wpp", 1)) > 1 and int(c[4].get("engines", 1)) == 1)]
-        for k in range(0, len(ok_cases), a.batch):
-            group = ok_cases[k:k + a.batch]
-            units, stale = device_batch(lib, group)
-            for c, u, st in zip(group, units, stale):
-                batched[id(c)] = (u, st)
+        lib.hmr_gpu_enc_last_pool_kernel.argtypes = [C.c_void_p]
+        parts = [[c for c in ok_cases if int(c[4].get("rd", 0)) != 1], [c for c in ok_cases if int(c[4].get("rd", 0)) == 1]] if a.split_rd else [ok_cases]
+        for part in parts:
+            for k in range(0, len(part), a.batch):
+                group = part[k:k + a.batch]
+                units, stale = device_batch(lib, group)
+                for c, u, st in zip(group, units, stale):
+                    batched[id(c)] = (u, st)
+        # (stderr: stdout is one line per case, and tests/test_fuzz.py reads every unindented line of it as a case)
+        print("pool launches by kernel (0 latency, 1 throughput without full RDO, 2 generic):", dict(sorted(POOL_KERNELS.items())), file=sys.stderr, flush=True)
         cases = ok_cases
     global STALE
     varying = 0

@@ -4,20 +4,22 @@ Prints, for each gap between the end of a pool launch and the start of the next,
 import csv
 import sys
 
+POOL_KERNELS = ("k_encode_pool", "k_encode_full")      # the pool body's kernels: k_encode_pool, k_encode_pool_lat, k_encode_full
+
 
 def main():
     rows = []
     for r in csv.DictReader(open(sys.argv[1])):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0]))
     rows.sort()
-    pools = [r for r in rows if r[2].startswith("k_encode_pool")]
+    pools = [r for r in rows if r[2].startswith(POOL_KERNELS)]
     pools = [p for p in pools if p[1] - p[0] > float(sys.argv[2]) * 1e6] if len(sys.argv) > 2 else pools        # (ms: only launches longer than this, e.g. the batch launches)
     out = []
     for a, b in zip(pools, pools[1:]):
         gap0, gap1 = a[1], b[0]
         if gap1 - gap0 > 2e9:
             continue
-        inside = [r for r in rows if r[0] >= gap0 - 1 and r[1] <= gap1 + 1 and not r[2].startswith("k_encode_pool")]
+        inside = [r for r in rows if r[0] >= gap0 - 1 and r[1] <= gap1 + 1 and not r[2].startswith(POOL_KERNELS)]
         names = {}
         for s, e, n in inside:
             d = names.setdefault(n, [s, e, 0, 0])

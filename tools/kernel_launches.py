@@ -11,7 +11,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bench_record
 
-rows = [r for r in csv.DictReader(open(sys.argv[1])) if "k_encode_pool" in r["Kernel_Name"]]
+rows = [r for r in csv.DictReader(open(sys.argv[1])) if "k_encode_pool" in r["Kernel_Name"] or "k_encode_full" in r["Kernel_Name"]]      # (the pool body's kernels: throughput, latency, generic)
 # the bench's headline is the batch of sequences (a launch of as many workgroups as the GPU has CUs); the single-sequence run beside it (17 workgroups) is not listed here
 gkey = next((k for k in ("Grid_Size", "Grid_Size_X", "Workgroup_Count") if rows and k in rows[0]), None)
 if gkey:

@@ -48,7 +48,7 @@ def main():
             tot = k.get("TCC_HIT_sum", 0) + k.get("TCC_MISS_sum", 0)
             if tot:
                 d["l2_hit_rate"] = round(k["TCC_HIT_sum"] / tot, 4)
-        if name.startswith("k_encode_ctus") or name.startswith("k_encode_pool"):
+        if name.startswith(("k_encode_ctus", "k_encode_pool", "k_encode_full")):      # (the pool body's three kernels: k_encode_pool, k_encode_pool_lat, k_encode_full)
             d["note"] = (f"rocprofv3 --pmc passes of `{cmd}`; sums over all launches of the kernel (two wavefronts per workgroup: the row worker and its "
                          "helper, whose polling counts as waiting); SQ cycle counters in quad-cycles")
             if k.get("SQ_WAVE_CYCLES"):
@@ -58,7 +58,9 @@ def main():
         # (`frames` counts every picture the command encodes; those of launches with at most one worker per CU - one picture each here - go through the latency kernel
         # k_encode_pool_lat and are not k_encode_pool's)
         lat = kernels.get("k_encode_pool_lat", {}).get("launches", 0)      # (launches of ONE pass, as every count in this summary)
-        kernels["frames_encoded_by_k_encode_pool"] = frames - lat
+        # ... and a command whose launches hold RD_FULL pictures (cfg5, a mixed batch) runs k_encode_full instead of k_encode_pool: the frames are those of whichever ran
+        full = "k_encode_full" in kernels and "k_encode_pool" not in kernels
+        kernels["frames_encoded_by_k_encode_full" if full else "frames_encoded_by_k_encode_pool"] = frames - lat
         if lat:
             kernels["frames_encoded_by_k_encode_pool_lat"] = lat
     try:      # the build the passes ran on (the tree the GPU box was given: HEAD when the working tree is clean)
