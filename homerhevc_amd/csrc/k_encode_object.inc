@@ -148,13 +148,14 @@ struct hmr_gpu_enc {
 	WorkSlow *d_pool_slow = nullptr;                     // the pool workers' transform / decoded windows
 	int pool_workers = 0;
 	int last_pool_kernel = -1;                           // (lead) which kernel the last pool launch ran - 0: k_encode_pool_lat, 1: k_encode_pool, 2: k_encode_full; -1: none yet
-	// picture conversion (picture_io.h, k_encode_picture_io.inc): the job tables and events of the k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim launches this encoder leads - as the first
+	// picture conversion (picture_io.h, k_encode_picture_io.inc): the job tables and events of the k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim / k_egress_rgb launches this encoder leads - as the first
 	// encoder of a load / export call, and alone in the host-memory entries (widen_packed, narrow_packed)
 	JobRing<IngestJob> ingest;
 	JobRing<RgbIngestJob> ingest_rgb;
 	JobRing<ScaleJob> scale;
 	JobRing<EgressJob> egress;
 	JobRing<SsimJob> ssim;
+	JobRing<RgbEgressJob> egress_rgb;
 	// every encoder: whether d_pic[cur] holds an encoded frame's final picture, the stream whose work wrote it (its own, or the lead's of a batch or chain launch),
 	// events for that stream and its own (an export call waits behind both)
 	bool has_picture = false;
@@ -887,6 +888,7 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	e->scale.release();
 	e->egress.release();
 	e->ssim.release();
+	e->egress_rgb.release();
 	if (e->ev_pic_done) (void)hipEventDestroy(e->ev_pic_done);
 	if (e->ev_own_done) (void)hipEventDestroy(e->ev_own_done);
 	if (e->d_batch) (void)hipFree(e->d_batch);

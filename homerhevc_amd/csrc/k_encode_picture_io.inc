@@ -1,10 +1,11 @@
 // Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
-// (include/homer_gpu.h sections 12d, 12e, 12f, 12g and 12h).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim (picture_io.hip)
+// (include/homer_gpu.h sections 12d, 12e, 12f, 12g, 12h and 12i).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim / k_egress_rgb (picture_io.hip)
 // on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
 //   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
 //   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
 //           streams (which may still load the slots); the consumer's stream and all of those streams go on behind it.
 //   ssim:   ordered as export; the final pictures and the slots are read, three sums per encoder are written.
+//   export as RGB: ordered as export; the consumer's stream is also the one that holds the producer of the reference pictures.
 // Each entry checks the caller's arguments and builds the jobs; the host-memory entries of k_encode_object.inc (widen_packed, narrow_packed) build theirs for a
 // packed picture - the staging buffer, a picture between GPUs - and run the same kernels.
 #include <unordered_set>
@@ -119,6 +120,8 @@ namespace {
 // What a launch on `st` that reads the encoders' final pictures and picture slots has to follow, besides the consumer (its work on the output memory: run_jobs): the
 // launches that wrote the final pictures and what the encoders' own streams hold (loads into the slots), every distinct stream once.  The consumer reads the results
 // behind the launch; a later encode call rewrites the final picture, a later load the slot: those streams are added to `behind` and go on behind it too.
+// An encoder that has not encoded anything has no final picture and no stream that wrote one: only its own stream counts (the RGB export of a slot, section 12i; the
+// other callers refuse such an encoder before they come here).
 int wait_for_writers(hmr_gpu_enc **encs, int n, hipStream_t st, hipStream_t consumer, std::vector<hipStream_t> &behind)
 {
 	std::unordered_set<hipStream_t> seen = {consumer, st};
@@ -131,6 +134,7 @@ int wait_for_writers(hmr_gpu_enc **encs, int n, hipStream_t st, hipStream_t cons
 		const hipStream_t wrote[2] = {e->pic_stream, e->ctx->stream};
 		hipEvent_t const ev[2] = {e->ev_pic_done, e->ev_own_done};
 		for (int k = 0; k < 2; k++) {
+			if (k == 0 && !e->has_picture) continue;      // (a slot's picture alone is asked for, section 12i: nothing has written a final picture)
 			if (!seen.insert(wrote[k]).second) continue;
 			behind.push_back(wrote[k]);
 			// a stream with nothing in flight has nothing to queue behind (calls on one encoder come from one host thread at a time: nobody is adding to it now);
@@ -370,4 +374,88 @@ extern "C" int hmr_gpu_enc_ssim_device(hmr_gpu_enc **encs, int n, const int *slo
 extern "C" int hmr_gpu_enc_ssim_one_device(hmr_gpu_enc *enc, int slot, int64_t *dev_ssim, void *consumer_stream)
 {
 	return hmr_gpu_enc_ssim_device(&enc, 1, &slot, dev_ssim, consumer_stream);
+}
+
+// ---- section 12i: the final pictures or the slots' pictures out as RGB, and their distance to the caller's RGB pictures ----
+extern "C" int hmr_gpu_enc_export_pictures_rgb_device(hmr_gpu_enc **encs, int n, const int *which, const hmr_gpu_rgb_picture *outs, const hmr_gpu_rgb_picture *refs, uint64_t *dev_ssd,
+						      void *consumer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_export_pictures_rgb_device";
+	if (!encs || !which || n < 1 || n > PICTURE_MAX_JOBS) {
+		hmr_set_error("%s: needs 1 .. %d encoders with `which` (n = %d)", fn, PICTURE_MAX_JOBS, n);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!outs && !refs) {
+		hmr_set_error("%s: neither outs nor refs: nothing to do", fn);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!refs != !dev_ssd) {
+		hmr_set_error("%s: refs and dev_ssd go together (the sums of squared differences against the reference pictures)", fn);
+		return HMR_GPU_ERR_ARG;
+	}
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		if (!e) return picture_refuse(fn, i, "the encoder is NULL");
+		if (e->ctx->device != encs[0]->ctx->device) return picture_refuse(fn, i, "the encoder is on another device than the call's first");
+		if (which[i] < -1) return picture_refuse(fn, i, "which: below -1 (-1: the final picture, otherwise a picture slot)");
+		if (which[i] >= (int)e->src.size()) return picture_refuse(fn, i, "which: the slot does not exist");
+		if (which[i] == -1 && !e->has_picture) return picture_refuse(fn, i, "which: -1 and the encoder has not encoded a picture yet");
+		if (refs && e->seq.width > EGRESS_MAX_WIDTH) return picture_refuse(fn, i, "sums are made for pictures up to 8192 samples wide");
+		for (const hmr_gpu_rgb_picture *pics : {outs, refs})
+			if (pics && hmr_gpu_rgb_picture_check(&pics[i], e->seq.width, e->seq.height) != HMR_GPU_OK) {
+				const std::string why = std::string(pics == outs ? "outs: " : "refs: ") + hmr_gpu_last_error();
+				return picture_refuse(fn, i, why.c_str());
+			}
+	}
+	const int device = encs[0]->ctx->device;
+	HIP_TRY(hipSetDevice(device));
+	static const char *const out_names[3] = {"outs plane[0]", "outs plane[1]", "outs plane[2]"}, *const ref_names[3] = {"refs plane[0]", "refs plane[1]", "refs plane[2]"};
+	for (const hmr_gpu_rgb_picture *pics : {outs, refs})
+		for (int i = 0; pics && i < n; i++)
+			for (int c = 0; c < (pics[i].format == HMR_GPU_RGB_PACKED8 ? 1 : 3); c++)
+				if (!on_device(pics[i].plane[c], device)) return not_device(fn, i, (pics == outs ? out_names : ref_names)[c], device);
+	if (dev_ssd && (!on_device(dev_ssd, device) || !on_device(dev_ssd + 3 * (size_t)n - 1, device))) return not_device(fn, 0, "dev_ssd", device);
+	std::vector<RgbEgressJob> jobs(n);
+	for (int i = 0; i < n; i++) {
+		hmr_gpu_enc *e = encs[i];
+		const Seq &s = e->seq;
+		RgbEgressJob &j = jobs[i];
+		memset(&j, 0, sizeof j);
+		const bool final_picture = which[i] < 0;
+		for (int c = 0; c < 3; c++) {
+			j.yuv[c] = final_picture ? plane0(e, e->cur, c) : e->src[which[i]].p[c];
+			if (outs) {
+				j.dst[c] = (uint8_t *)const_cast<void *>(outs[i].plane[c]);      // (as the output descriptor of 12e: the call writes through the plane pointers)
+				j.dst_pitch[c] = outs[i].pitch[c];
+				j.offset[c] = outs[i].offset[c];
+			}
+			if (refs) {
+				j.src[c] = (const uint8_t *)refs[i].plane[c];
+				j.pitch[c] = refs[i].pitch[c];
+				j.src_offset[c] = refs[i].offset[c];
+			}
+		}
+		j.ssd = dev_ssd ? dev_ssd + 3 * (size_t)i : nullptr;
+		j.stride_y = final_picture ? s.stride_y : s.src_stride_y; j.stride_c = final_picture ? s.stride_c : s.src_stride_c;
+		j.width = s.width; j.height = s.height;
+		j.format = outs ? outs[i].format : -1; j.pixel_bytes = outs ? outs[i].pixel_bytes : 0;
+		j.src_format = refs ? refs[i].format : -1; j.src_pixel_bytes = refs ? refs[i].pixel_bytes : 0;
+		const hmr_gpu_rgb_picture &colour = outs ? outs[i] : refs[i];      // (sums alone: the table comes from the reference's fields)
+		j.m = hmr_yuv_matrix(colour.matrix, colour.full_range);
+	}
+	hipStream_t st = encs[0]->ctx->stream, consumer = (hipStream_t)consumer_stream;
+	// ordered as the export of 12e: behind the consumer (its work on the output memory and on dev_ssd, the producer of the reference pictures), the writers of the final
+	// pictures and the loads into the slots; the sums are zeroed on the launch's stream, behind all of them
+	auto behind_the_writers = [&](std::vector<hipStream_t> &behind) -> int {
+		const int rc = wait_for_writers(encs, n, st, consumer, behind);
+		if (rc) return rc;
+		if (dev_ssd) HIP_TRY(hipMemsetAsync(dev_ssd, 0, 3 * (size_t)n * sizeof(uint64_t), st));
+		return HMR_GPU_OK;
+	};
+	return run_jobs(encs[0]->egress_rgb, hmr_egress_rgb_launch, st, jobs.data(), n, consumer, std::vector<hipStream_t>(1, consumer), behind_the_writers);
+}
+
+extern "C" int hmr_gpu_enc_export_picture_rgb_device(hmr_gpu_enc *enc, int which, const hmr_gpu_rgb_picture *out, const hmr_gpu_rgb_picture *ref, uint64_t *dev_ssd, void *consumer_stream)
+{
+	return hmr_gpu_enc_export_pictures_rgb_device(&enc, 1, &which, out, ref, dev_ssd, consumer_stream);
 }

@@ -1,7 +1,8 @@
 // Picture conversion on the device (picture_io.hip): 8-bit 4:2:0 pictures in device memory <-> the int16 planes of the frame encoder, a batch of pictures per launch.
 // Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture); RGB pictures (8-bit packed or planar, binary16, binary32) -> the same planes, colour
 // converted in the same pass (rgb_yuv.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h).  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
-// squared differences against the int16 source planes of a picture slot.  A launch reads its pictures from a job table; JobRing holds the tables of one encoder and
+// squared differences against the int16 source planes of a picture slot; the final pictures or the slots' pictures -> RGB pictures in any of the ingest's forms, colour
+// converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  A launch reads its pictures from a job table; JobRing holds the tables of one encoder and
 // run_jobs queues one launch, ordered against the caller's stream by events (k_encode_picture_io.inc and the host-memory entries of k_encode_object.inc use it).
 #pragma once
 #include <algorithm>
@@ -9,6 +10,7 @@
 #include <vector>
 #include "common.h"
 #include "rgb_yuv.h"
+#include "yuv_rgb.h"
 #include "scale_area.h"
 #include "ssim_window.h"
 
@@ -49,6 +51,23 @@ struct RgbIngestJob {
 	int32_t reserved[3];
 };
 static_assert(sizeof(RgbIngestJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
+
+// one picture of an RGB egress launch (k_egress_rgb): int16 planes (a final picture, a picture slot) into the caller's RGB picture by yuv_rgb.h's arithmetic, and / or
+// the sums of squared differences between the 8-bit RGB values and the caller's reference RGB picture
+struct RgbEgressJob {
+	const int16_t *yuv[3];       // the planes at sample (0, 0); 16-byte aligned, read-only
+	const uint8_t *src[3];       // the reference picture (src_format < 0: none) - HMR_GPU_RGB_PACKED8: src[0] alone; planar: R, G, B
+	int64_t pitch[3];            // bytes from row to row of src
+	uint8_t *dst[3];             // the output picture (format < 0: none), planes as src
+	int64_t dst_pitch[3];
+	uint64_t *ssd;               // three sums (zeroed in front of the launch), or NULL
+	int32_t stride_y, stride_c;  // of yuv, elements, multiples of 8
+	int32_t width, height;
+	int32_t format, pixel_bytes, offset[3];                // of dst
+	int32_t src_format, src_pixel_bytes, src_offset[3];    // of src
+	YuvMatrix m;                 // the five coefficients and yoff: a launch mixes matrices and ranges
+};
+static_assert(sizeof(RgbEgressJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
 // one picture of a downscaling ingest launch (k_downscale): the caller's src_w x src_h picture, area-averaged by scale_area.h's arithmetic into the dst_w x dst_h planes
 struct ScaleJob {
@@ -97,13 +116,27 @@ static inline double hmr_egress_bytes(int width, int height, int picture, int su
 	return 3.0 * wh + (sums ? 3.0 * wh : 0.0) + (picture ? 1.5 * wh : 0.0);
 }
 
+// Bytes of a row of `width` pixels of an RGB picture, per pixel: 3 or 4 packed, 3 planar 8-bit, 6 planar binary16, 12 planar binary32
+static inline double hmr_rgb_pixel_bytes(int format, int pixel_bytes)
+{
+	return format == HMR_GPU_RGB_PACKED8 ? pixel_bytes : format == HMR_GPU_RGB_PLANAR8 ? 3 : format == HMR_GPU_RGB_PLANAR_F16 ? 6 : 12;
+}
+// Algorithmic bytes of one width x height picture through k_egress_rgb (tools/rgb_egress_bench.py restates it): the int16 planes are read (3 W H), the reference
+// picture is read when sums are asked for (ref_format >= 0), the RGB picture is written when one is asked for (format >= 0).
+static inline double hmr_egress_rgb_bytes(int width, int height, int format, int pixel_bytes, int ref_format, int ref_pixel_bytes)
+{
+	const double wh = (double)width * height;
+	return (3.0 + (format >= 0 ? hmr_rgb_pixel_bytes(format, pixel_bytes) : 0.0) + (ref_format >= 0 ? hmr_rgb_pixel_bytes(ref_format, ref_pixel_bytes) : 0.0)) * wh;
+}
+
 // The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of k_ingest /
-// k_ingest_rgb / k_downscale / k_egress / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
+// k_ingest_rgb / k_downscale / k_egress / k_egress_rgb / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n);
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n);
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n);
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n);
 int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n);
+int hmr_egress_rgb_launch(hipStream_t stream, const RgbEgressJob *h_jobs, RgbEgressJob *d_jobs, int n);
 // the job of one picture: the sizes have passed hmr_gpu_scale_check; the ratios, their reciprocals and the tile height are derived here
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
 

@@ -177,8 +177,8 @@ template <int V> struct RgbForm {
 };
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-template <int V>
-__device__ __forceinline__ void rgb_load_row(const RgbIngestJob &j, int x, int y, uint32_t *raw)
+template <int V, class Job>
+__device__ __forceinline__ void rgb_load_row(const Job &j, int x, int y, uint32_t *raw)
 {
 	typedef RgbForm<V> F;
 	if (V == RGB_PACKED3 || V == RGB_PACKED4) {
@@ -595,6 +595,260 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_egress(const EgressJob *jobs)
 	if (sums) add_sums(ssd + 1, acc_u, acc_v, true);
 }
 
+// ---- RGB egress (section 12i) ----
+// k_egress_rgb: int16 planes - a final picture (with margins) or a picture slot (without: every chroma index is clamped here) - into RGB pictures in any of the ingest's
+// forms by the integer arithmetic of yuv_rgb.h, and / or the exact sums of squared differences between the 8-bit R, G, B values and a reference RGB picture in any form.
+// 3 W H bytes read, the reference's 3, 4, 3, 6 or 12 W H read, 3, 4, 3, 6 or 12 W H written per picture (hmr_egress_rgb_bytes in picture_io.h).
+// blockIdx.y = picture, blockIdx.x = a chunk of RGB_PAIRS row pairs; pair p is the luma rows 2 p - 1 and 2 p, which both take their chroma from rows p - 1 and p (the
+// pairs 0 and H / 2 have one row, and one chroma row twice: the clamp): H / 2 + 1 pairs, at most CHUNK_ROWS luma rows a chunk.  A lane takes a span of 16 pixels of a
+// pair: one aligned 16-byte load of eight samples per chroma row and plane plus the two neighbour columns (clamped; they are another lane's span: served from cache),
+// weighted vertically two samples to a dword (3 a + b <= 1020: the halves do not carry), then per luma row two 16-byte loads, the sixteen pixels' arithmetic, the
+// channels packed four pixels to a dword, and 16-byte stores at whatever address the pitch gives: one per plane (planar 8-bit), two / four per plane (binary16 /
+// binary32), three / four (3- / 4-byte pixels, the bytes placed by the job's offsets, the fourth byte 255).  The reference's row is read by the ingest's loaders
+// (rgb_load_row, rgb_pixel).  A row's tail of fewer than 16 pixels goes sample by sample, a lane per pixel.  No lane writes a byte outside
+// [plane + y * pitch, plane + y * pitch + row bytes).  Sums: a lane's three 32-bit accumulators through add_sums; a chunk holds at most CHUNK_ROWS x EGRESS_MAX_WIDTH
+// pixels, each difference at most 255: the bound at the top of the file.
+constexpr int RGB_PAIRS = CHUNK_ROWS / 2;
+__host__ __device__ __forceinline__ int rgb_egress_chunks(int height) { return ((height >> 1) + 1 + RGB_PAIRS - 1) / RGB_PAIRS; }
+
+// a sample of an RGB picture written as 8 bits' worth: host and device pointers alike (hmr_gpu_rgb_from_yuv_host, a row's tail)
+template <class Bytes, class Halves, class Floats>
+__host__ __device__ __forceinline__ void rgb_put(Bytes plane, int64_t pitch, int format, int pixel_bytes, int offset, int x, int y, int v)
+{
+	const Bytes row = plane + (int64_t)y * pitch;
+	switch (format) {
+	case HMR_GPU_RGB_PACKED8: row[x * pixel_bytes + offset] = (uint8_t)v; break;
+	case HMR_GPU_RGB_PLANAR8: row[x] = (uint8_t)v; break;
+	case HMR_GPU_RGB_PLANAR_F16: ((Halves)row)[x] = (_Float16)hmr_rgb_unit(v); break;
+	default: ((Floats)row)[x] = hmr_rgb_unit(v); break;
+	}
+}
+// the byte of a 4-byte pixel that holds no channel
+__host__ __device__ __forceinline__ int rgb_alpha_offset(const int32_t offset[3]) { return 6 - offset[0] - offset[1] - offset[2]; }
+
+__device__ __forceinline__ uint32_t byte_of(const uint32_t *p, int i) { return (p[i >> 2] >> (8 * (i & 3))) & 255u; }
+
+// sixteen pixels of a luma row: ya, yb its int16 samples, two to a dword; cu, cv the vertically weighted chroma of columns x / 2 - 1 .. x / 2 + 8; the channels come
+// back as bytes, four pixels to a dword
+__device__ __forceinline__ void yuv_row16(const YuvMatrix &m, u32x4 ya, u32x4 yb, const int *cu, const int *cv, uint32_t *pr, uint32_t *pg, uint32_t *pb)
+{
+	const uint32_t yw[8] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w};
+#pragma unroll
+	for (int d = 0; d < 4; d++) {
+		uint32_t r4 = 0, g4 = 0, b4 = 0;
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const int i = 4 * d + k, c = i >> 1;
+			const int y = (int)((yw[i >> 1] >> (16 * (i & 1))) & 255u);
+			const int u16 = (i & 1) ? 3 * cu[c + 1] + cu[c + 2] : cu[c] + 3 * cu[c + 1];
+			const int v16 = (i & 1) ? 3 * cv[c + 1] + cv[c + 2] : cv[c] + 3 * cv[c + 1];
+			int r, g, b;
+			hmr_yuv_rgb(m, y, u16, v16, r, g, b);
+			// (opaque: AMD clang 22.0.0git of ROCm 7.2.0 otherwise fuses shift, clamp and packing of two pixels into v_ashr_pk_u8_i32 and takes the upper half of its
+			// result for zero; on the MI355X the bytes of the two other pixels, or-ed in above it, then came out with stray bits.  Masking r, g, b with 255 does not
+			// help: the compiler knows them to be inside 0 .. 255 and drops the mask.  tests/test_gpu_rgb_egress.py's equality tests hold this.)
+			asm("" : "+v"(r), "+v"(g), "+v"(b));
+			r4 |= (uint32_t)r << (8 * k); g4 |= (uint32_t)g << (8 * k); b4 |= (uint32_t)b << (8 * k);
+		}
+		// (opaque to the optimiser: it would otherwise see through the packing and keep the 48 values themselves alive until the row's stores, instead of 12 dwords)
+		asm volatile("" : "+v"(r4), "+v"(g4), "+v"(b4));
+		pr[d] = r4; pg[d] = g4; pb[d] = b4;
+	}
+}
+
+// Sixteen pixels at (x, y) of the reference picture, read in form V, quantised to 8 bits (rgb_yuv.h) and packed like the converted row: four pixels of a channel to a
+// dword.  The packed forms through the ingest's loaders (the three channels lie in the same bytes); the planar forms plane by plane.
+template <int V>
+__device__ __forceinline__ void rgb_ref_row(const RgbEgressJob &j, int x, int y, uint32_t *qr, uint32_t *qg, uint32_t *qb)
+{
+	if (V == RGB_PACKED3 || V == RGB_PACKED4) {
+		typedef RgbForm<V> F;
+		const int sh[3] = {8 * j.src_offset[0], 8 * j.src_offset[1], 8 * j.src_offset[2]};
+		uint32_t raw[F::WORDS];
+		rgb_load_row<V>(j, x, y, raw);
+#pragma unroll
+		for (int d = 0; d < 4; d++) {
+			uint32_t r4 = 0, g4 = 0, b4 = 0;
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				int r, g, b;
+				rgb_pixel<V>(raw, 4 * d + k, sh, r, g, b);
+				r4 |= (uint32_t)r << (8 * k); g4 |= (uint32_t)g << (8 * k); b4 |= (uint32_t)b << (8 * k);
+			}
+			qr[d] = r4; qg[d] = g4; qb[d] = b4;
+		}
+		return;
+	}
+	constexpr int elem = V == RGB_PLANAR8 ? 1 : V == RGB_F16 ? 2 : 4;
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		uint32_t *q = c == 0 ? qr : c == 1 ? qg : qb;
+		const bytes_in s = (bytes_in)j.src[c] + (int64_t)y * j.pitch[c] + (int64_t)x * elem;
+#pragma unroll
+		for (int k = 0; k < elem; k++) {      // sixteen bytes of the plane: 16 / elem samples
+			const u32x4 v = load16(s + 16 * k);
+			const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+			if (V == RGB_PLANAR8) { q[0] = w[0]; q[1] = w[1]; q[2] = w[2]; q[3] = w[3]; }
+			else if (V == RGB_F16) {
+#pragma unroll
+				for (int d = 0; d < 2; d++) {
+					const f16x2 h0 = __builtin_bit_cast(f16x2, w[2 * d]), h1 = __builtin_bit_cast(f16x2, w[2 * d + 1]);
+					q[2 * k + d] = (uint32_t)hmr_rgb_quantize((float)h0.x) | (uint32_t)hmr_rgb_quantize((float)h0.y) << 8 | (uint32_t)hmr_rgb_quantize((float)h1.x) << 16 |
+						       (uint32_t)hmr_rgb_quantize((float)h1.y) << 24;
+				}
+			} else
+				q[k] = (uint32_t)hmr_rgb_quantize(__builtin_bit_cast(float, w[0])) | (uint32_t)hmr_rgb_quantize(__builtin_bit_cast(float, w[1])) << 8 |
+				       (uint32_t)hmr_rgb_quantize(__builtin_bit_cast(float, w[2])) << 16 | (uint32_t)hmr_rgb_quantize(__builtin_bit_cast(float, w[3])) << 24;
+		}
+	}
+}
+// acc + the squared differences of the sixteen bytes of q and p: sum (q - p)^2 = sum q q + sum p p - 2 sum q p, each a v_dot4_u32_u8 per dword (modulo 2^32: exact,
+// the result is not negative)
+__device__ __forceinline__ uint32_t sq_bytes(uint32_t acc, const uint32_t *q, const uint32_t *p)
+{
+	uint32_t cross = 0;
+#pragma unroll
+	for (int d = 0; d < 4; d++) {
+		acc = __builtin_amdgcn_udot4(q[d], q[d], __builtin_amdgcn_udot4(p[d], p[d], acc, false), false);
+		cross = __builtin_amdgcn_udot4(q[d], p[d], cross, false);
+	}
+	return acc - 2u * cross;
+}
+
+// Sixteen pixels at (x, y) of the output picture, written in the form `form` (uniform over the workgroup).  The forms that share arithmetic share its code - the two
+// packed forms a pixel's dword, the two float forms the division - and branch where they differ, group of four values by group: written as one case per form, the
+// compiler hoists the shared arithmetic of ALL sixteen pixels in front of the branch and a lane holds 48 quotients at once.
+__device__ __forceinline__ void rgb_store_row(const RgbEgressJob &j, int form, int x, int y, const uint32_t *pr, const uint32_t *pg, const uint32_t *pb)
+{
+	if (form == RGB_PACKED3 || form == RGB_PACKED4) {
+		const bool four = form == RGB_PACKED4;
+		const int s0 = 8 * j.offset[0], s1 = 8 * j.offset[1], s2 = 8 * j.offset[2];
+		const uint32_t alpha = four ? 255u << (8 * rgb_alpha_offset(j.offset)) : 0u;
+		const bytes_out d = (bytes_out)j.dst[0] + (int64_t)y * j.dst_pitch[0] + (int64_t)x * (four ? 4 : 3);
+		uint32_t o[12];      // (3-byte pixels: four pixels in three dwords)
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			uint32_t w[4];
+#pragma unroll
+			for (int i = 0; i < 4; i++) w[i] = byte_of(pr, 4 * k + i) << s0 | byte_of(pg, 4 * k + i) << s1 | byte_of(pb, 4 * k + i) << s2 | alpha;
+			if (four) store16(d + 16 * k, u32x4{w[0], w[1], w[2], w[3]});
+			else {
+				o[3 * k] = w[0] | w[1] << 24;
+				o[3 * k + 1] = w[1] >> 8 | w[2] << 16;
+				o[3 * k + 2] = w[2] >> 16 | w[3] << 8;
+			}
+		}
+		if (!four) {
+#pragma unroll
+			for (int k = 0; k < 3; k++) store16(d + 16 * k, u32x4{o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]});
+		}
+		return;
+	}
+	const bool halves = form == RGB_F16;
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		const uint32_t *p = c == 0 ? pr : c == 1 ? pg : pb;
+		const bytes_out d = (bytes_out)j.dst[c] + (int64_t)y * j.dst_pitch[c] + (int64_t)x * (form == RGB_PLANAR8 ? 1 : halves ? 2 : 4);
+		if (form == RGB_PLANAR8) {
+			store16(d, u32x4{p[0], p[1], p[2], p[3]});
+			continue;
+		}
+		uint32_t h[4];
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const float f0 = hmr_rgb_unit((int)byte_of(p, 4 * k)), f1 = hmr_rgb_unit((int)byte_of(p, 4 * k + 1)), f2 = hmr_rgb_unit((int)byte_of(p, 4 * k + 2)), f3 = hmr_rgb_unit((int)byte_of(p, 4 * k + 3));
+			if (!halves) {
+				store16(d + 16 * k, u32x4{__builtin_bit_cast(uint32_t, f0), __builtin_bit_cast(uint32_t, f1), __builtin_bit_cast(uint32_t, f2), __builtin_bit_cast(uint32_t, f3)});
+				continue;
+			}
+			const f16x2 a = {(_Float16)f0, (_Float16)f1}, b = {(_Float16)f2, (_Float16)f3};
+			h[2 * (k & 1)] = __builtin_bit_cast(uint32_t, a); h[2 * (k & 1) + 1] = __builtin_bit_cast(uint32_t, b);
+			if (k & 1) store16(d + 16 * (k >> 1), u32x4{h[0], h[1], h[2], h[3]});
+		}
+	}
+}
+
+// which of the forms RGB_PACKED3 .. RGB_F32 a descriptor's format and pixel bytes are
+__host__ __device__ __forceinline__ int rgb_form(int format, int pixel_bytes)
+{
+	return format == HMR_GPU_RGB_PACKED8 ? (pixel_bytes == 3 ? RGB_PACKED3 : RGB_PACKED4) : format == HMR_GPU_RGB_PLANAR8 ? RGB_PLANAR8 : format == HMR_GPU_RGB_PLANAR_F16 ? RGB_F16 : RGB_F32;
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_egress_rgb(const RgbEgressJob *jobs)
+{
+	const RgbEgressJob j = jobs[blockIdx.y];
+	const int W = j.width, H = j.height, cw = W >> 1, ch = H >> 1, t = (int)threadIdx.x;
+	const int p0 = (int)blockIdx.x * RGB_PAIRS;
+	if (p0 > ch) return;
+	const int pairs = ch + 1 - p0 < RGB_PAIRS ? ch + 1 - p0 : RGB_PAIRS, per_row = W >> 4;      // (whole spans)
+	const bool sums = j.src_format >= 0, picture = j.format >= 0;
+	const int src_form = rgb_form(j.src_format, j.src_pixel_bytes), dst_form = rgb_form(j.format, j.pixel_bytes);
+	const samples_in py = (samples_in)j.yuv[0], pu = (samples_in)j.yuv[1], pv = (samples_in)j.yuv[2];
+	uint32_t acc_r = 0, acc_g = 0, acc_b = 0;
+	for (int i = t; i < pairs * per_row; i += HMR_BLOCK) {
+		const int r = i / per_row, x = (i - r * per_row) << 4, p = p0 + r, cx = x >> 1;
+		const int ca = p > 0 ? p - 1 : 0, cb = p < ch ? p : ch - 1, cl = cx > 0 ? cx - 1 : 0, cr = cx + 8 < cw ? cx + 8 : cw - 1;
+		const size_t oa = (size_t)ca * j.stride_c, ob = (size_t)cb * j.stride_c;
+		const u32x4 ua = *(const GLOBAL_AS u32x4 *)(pu + oa + cx) & 0x00ff00ffu, ub = *(const GLOBAL_AS u32x4 *)(pu + ob + cx) & 0x00ff00ffu;
+		const u32x4 va = *(const GLOBAL_AS u32x4 *)(pv + oa + cx) & 0x00ff00ffu, vb = *(const GLOBAL_AS u32x4 *)(pv + ob + cx) & 0x00ff00ffu;
+		// the neighbour columns of both rows, left | right << 16: weighted like the spans
+		const uint32_t una = (uint32_t)(pu[oa + cl] & 255) | (uint32_t)(pu[oa + cr] & 255) << 16, unb = (uint32_t)(pu[ob + cl] & 255) | (uint32_t)(pu[ob + cr] & 255) << 16;
+		const uint32_t vna = (uint32_t)(pv[oa + cl] & 255) | (uint32_t)(pv[oa + cr] & 255) << 16, vnb = (uint32_t)(pv[ob + cl] & 255) | (uint32_t)(pv[ob + cr] & 255) << 16;
+#pragma unroll 1
+		for (int half = 0; half < 2; half++) {
+			const int y = 2 * p - 1 + half;
+			if (y < 0 || y >= H) continue;
+			const uint32_t wa = half ? 1u : 3u, wb = 4u - wa;      // (row 2 p - 1 is the odd row of chroma row p - 1, row 2 p the even row of chroma row p)
+			const u32x4 u2 = ua * wa + ub * wb, v2 = va * wa + vb * wb;
+			const uint32_t un = una * wa + unb * wb, vn = vna * wa + vnb * wb;
+			const int cu[10] = {(int)(un & 0xffffu), (int)(u2.x & 0xffffu), (int)(u2.x >> 16), (int)(u2.y & 0xffffu), (int)(u2.y >> 16), (int)(u2.z & 0xffffu), (int)(u2.z >> 16),
+					    (int)(u2.w & 0xffffu), (int)(u2.w >> 16), (int)(un >> 16)};
+			const int cv[10] = {(int)(vn & 0xffffu), (int)(v2.x & 0xffffu), (int)(v2.x >> 16), (int)(v2.y & 0xffffu), (int)(v2.y >> 16), (int)(v2.z & 0xffffu), (int)(v2.z >> 16),
+					    (int)(v2.w & 0xffffu), (int)(v2.w >> 16), (int)(vn >> 16)};
+			const GLOBAL_AS u32x4 *ly = (const GLOBAL_AS u32x4 *)(py + (size_t)y * j.stride_y + x);
+			uint32_t pr[4], pg[4], pb[4];
+			yuv_row16(j.m, ly[0], ly[1], cu, cv, pr, pg, pb);
+			if (sums) {
+				uint32_t qr[4], qg[4], qb[4];
+				switch (src_form) {
+				case RGB_PACKED3: rgb_ref_row<RGB_PACKED3>(j, x, y, qr, qg, qb); break;
+				case RGB_PACKED4: rgb_ref_row<RGB_PACKED4>(j, x, y, qr, qg, qb); break;
+				case RGB_PLANAR8: rgb_ref_row<RGB_PLANAR8>(j, x, y, qr, qg, qb); break;
+				case RGB_F16: rgb_ref_row<RGB_F16>(j, x, y, qr, qg, qb); break;
+				default: rgb_ref_row<RGB_F32>(j, x, y, qr, qg, qb); break;
+				}
+				acc_r = sq_bytes(acc_r, qr, pr); acc_g = sq_bytes(acc_g, qg, pg); acc_b = sq_bytes(acc_b, qb, pb);
+			}
+			if (picture) rgb_store_row(j, dst_form, x, y, pr, pg, pb);
+		}
+	}
+	// a row's tail of fewer than 16 pixels: a lane per pixel of the chunk's rows 2 p0 - 1 .. 2 (p0 + pairs - 1)
+	const int tail = W & 15, x0 = W & ~15, y0 = p0 ? 2 * p0 - 1 : 0, y1 = 2 * (p0 + pairs - 1) < H ? 2 * (p0 + pairs - 1) : H - 1;
+	const bool src_packed = j.src_format == HMR_GPU_RGB_PACKED8, dst_packed = j.format == HMR_GPU_RGB_PACKED8;
+	for (int i = t; i < (y1 - y0 + 1) * tail; i += HMR_BLOCK) {
+		const int r = i / tail, x = x0 + i - r * tail, y = y0 + r;
+		int c3[3];
+		hmr_yuv_rgb(j.m, py[(size_t)y * j.stride_y + x] & 255, hmr_yuv_chroma16(pu, j.stride_c, cw, ch, x, y), hmr_yuv_chroma16(pv, j.stride_c, cw, ch, x, y), c3[0], c3[1], c3[2]);
+		if (sums) {
+			const int dr = c3[0] - rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[0], j.pitch[0], j.src_format, j.src_pixel_bytes, j.src_offset[0], x, y);
+			const int dg = c3[1] - rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[src_packed ? 0 : 1], j.pitch[src_packed ? 0 : 1], j.src_format, j.src_pixel_bytes, j.src_offset[1], x, y);
+			const int db = c3[2] - rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[src_packed ? 0 : 2], j.pitch[src_packed ? 0 : 2], j.src_format, j.src_pixel_bytes, j.src_offset[2], x, y);
+			acc_r += (uint32_t)(dr * dr); acc_g += (uint32_t)(dg * dg); acc_b += (uint32_t)(db * db);
+		}
+		if (picture) {
+			rgb_put<bytes_out, GLOBAL_AS _Float16 *, GLOBAL_AS float *>((bytes_out)j.dst[0], j.dst_pitch[0], j.format, j.pixel_bytes, j.offset[0], x, y, c3[0]);
+			rgb_put<bytes_out, GLOBAL_AS _Float16 *, GLOBAL_AS float *>((bytes_out)j.dst[dst_packed ? 0 : 1], j.dst_pitch[dst_packed ? 0 : 1], j.format, j.pixel_bytes, j.offset[1], x, y, c3[1]);
+			rgb_put<bytes_out, GLOBAL_AS _Float16 *, GLOBAL_AS float *>((bytes_out)j.dst[dst_packed ? 0 : 2], j.dst_pitch[dst_packed ? 0 : 2], j.format, j.pixel_bytes, j.offset[2], x, y, c3[2]);
+			if (dst_packed && j.pixel_bytes == 4) ((bytes_out)j.dst[0])[(int64_t)y * j.dst_pitch[0] + 4 * x + rgb_alpha_offset(j.offset)] = 255;
+		}
+	}
+	if (!sums) return;
+	GLOBAL_AS uint64_t *ssd = (GLOBAL_AS uint64_t *)j.ssd;
+	add_sums(ssd, acc_r, acc_g, true);
+	__syncthreads();      // (add_sums' partial sums are read by two lanes while the other wavefronts go on)
+	add_sums(ssd + 2, acc_b, 0, false);
+}
+
 // ---- SSIM (section 12h) ----
 // k_ssim: the exact sums of ssim_window.h's fixed-point SSIM values over every window of every plane, between the int16 planes of a picture slot (a) and the final
 // picture's (b).  Both pictures are read, 6 W H bytes per picture (hmr_ssim_bytes in picture_io.h); nothing is written but three 64-bit sums.  blockIdx.y = picture;
@@ -713,6 +967,7 @@ inline int chunks_of(const EgressJob &j) { return Chunk{0, j.width, j.height}.ch
 inline int chunks_of(const RgbIngestJob &j) { return rgb_chunks(j.height); }
 inline int chunks_of(const ScaleJob &j) { return scale_tiles(j); }
 inline int chunks_of(const SsimJob &j) { return ssim_tiles(j.width, j.height); }
+inline int chunks_of(const RgbEgressJob &j) { return rgb_egress_chunks(j.height); }
 
 template <class Job>
 int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n)
@@ -733,6 +988,7 @@ int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n) { return launch(k_ingest_rgb, stream, h_jobs, d_jobs, n); }
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n) { return launch(k_downscale, stream, h_jobs, d_jobs, n); }
 int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n) { return launch(k_ssim, stream, h_jobs, d_jobs, n); }
+int hmr_egress_rgb_launch(hipStream_t stream, const RgbEgressJob *h_jobs, RgbEgressJob *d_jobs, int n) { return launch(k_egress_rgb, stream, h_jobs, d_jobs, n); }
 
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h)
 {
@@ -919,6 +1175,71 @@ extern "C" int hmr_gpu_psnr(const uint64_t ssd[3], int width, int height, double
 		const double samples = c ? (double)(width / 2) * (height / 2) : (double)width * height;
 		psnr[c] = ssd[c] ? 10.0 * log10(255.0 * 255.0 * samples / (double)ssd[c]) : 99.99;
 	}
+	return HMR_GPU_OK;
+}
+
+// ---- section 12i: the host side of the RGB egress ----
+// yuv_rgb.h's arithmetic over host memory: the loop a caller would write from the header's formulas
+extern "C" int hmr_gpu_rgb_from_yuv_host(const uint8_t *y, const uint8_t *u, const uint8_t *v, int width, int height, const hmr_gpu_rgb_picture *out)
+{
+	const int rc = hmr_gpu_rgb_picture_check(out, width, height);
+	if (rc) return rc;
+	if (!y || !u || !v) {
+		hmr_set_error("hmr_gpu_rgb_from_yuv_host: needs the three input planes");
+		return HMR_GPU_ERR_ARG;
+	}
+	const YuvMatrix m = hmr_yuv_matrix(out->matrix, out->full_range);
+	const bool packed = out->format == HMR_GPU_RGB_PACKED8;
+	const int cw = width >> 1, ch = height >> 1;
+	for (int py = 0; py < height; py++)
+		for (int px = 0; px < width; px++) {
+			int c3[3];
+			hmr_yuv_rgb(m, y[(size_t)py * width + px], hmr_yuv_chroma16(u, cw, cw, ch, px, py), hmr_yuv_chroma16(v, cw, cw, ch, px, py), c3[0], c3[1], c3[2]);
+			for (int c = 0; c < 3; c++)
+				rgb_put<uint8_t *, _Float16 *, float *>((uint8_t *)const_cast<void *>(out->plane[packed ? 0 : c]), out->pitch[packed ? 0 : c], out->format, out->pixel_bytes, out->offset[c], px, py, c3[c]);
+			if (packed && out->pixel_bytes == 4) ((uint8_t *)const_cast<void *>(out->plane[0]))[(int64_t)py * out->pitch[0] + 4 * px + rgb_alpha_offset(out->offset)] = 255;
+		}
+	return HMR_GPU_OK;
+}
+
+// the three sums of squared differences between the 8-bit values of two RGB pictures in host memory
+extern "C" int hmr_gpu_rgb_ssd_host(const hmr_gpu_rgb_picture *a, const hmr_gpu_rgb_picture *b, int width, int height, uint64_t ssd[3])
+{
+	int rc;
+	if ((rc = hmr_gpu_rgb_picture_check(a, width, height)) || (rc = hmr_gpu_rgb_picture_check(b, width, height))) return rc;
+	if (!ssd) {
+		hmr_set_error("hmr_gpu_rgb_ssd_host: needs the three sums");
+		return HMR_GPU_ERR_ARG;
+	}
+	const hmr_gpu_rgb_picture *pics[2] = {a, b};
+	for (int c = 0; c < 3; c++) {
+		uint64_t sum = 0;
+		for (int py = 0; py < height; py++)
+			for (int px = 0; px < width; px++) {
+				int s[2];
+				for (int k = 0; k < 2; k++) {
+					const hmr_gpu_rgb_picture *p = pics[k];
+					const int plane = p->format == HMR_GPU_RGB_PACKED8 ? 0 : c;
+					s[k] = rgb_sample<const uint8_t *, const _Float16 *, const float *>((const uint8_t *)p->plane[plane], p->pitch[plane], p->format, p->pixel_bytes, p->offset[c], px, py);
+				}
+				sum += (uint64_t)((s[0] - s[1]) * (s[0] - s[1]));
+			}
+		ssd[c] = sum;
+	}
+	return HMR_GPU_OK;
+}
+
+// PSNR of R, G, B and of all three together from sums of squared differences: pure host
+extern "C" int hmr_gpu_psnr_rgb(const uint64_t ssd[3], int width, int height, double psnr[4])
+{
+	if (!ssd || !psnr || width <= 0 || height <= 0 || (width & 1) || (height & 1)) {
+		hmr_set_error("hmr_gpu_psnr_rgb: needs three sums, four results and a positive even width and height (%d x %d)", width, height);
+		return HMR_GPU_ERR_ARG;
+	}
+	const double samples = (double)width * height;
+	for (int c = 0; c < 3; c++) psnr[c] = ssd[c] ? 10.0 * log10(255.0 * 255.0 * samples / (double)ssd[c]) : 99.99;
+	const uint64_t all = ssd[0] + ssd[1] + ssd[2];
+	psnr[3] = all ? 10.0 * log10(255.0 * 255.0 * 3.0 * samples / (double)all) : 99.99;
 	return HMR_GPU_OK;
 }
 

@@ -14,9 +14,11 @@
     y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
     sums = enc.ssim()                           # the exact fixed-point SSIM sums between the reconstructed picture and `frame` as int64 [3], by one launch of k_ssim
     y, u, v = ssim(sums.tolist(), 1920, 1080)   # the mean SSIM of each plane, 1.0 for identical pictures
+    out, ssd = enc.export_rgb(dtype=torch.float16, reference=RGBFrame(rgb))     # the reconstructed picture as RGB [3, H, W], the sums of squared differences to `rgb` as int64 [3]
+    r, g, b, all3 = psnr_rgb(ssd.tolist(), 1920, 1080)                          # PSNR against the RGB frame that was supplied
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g and 12h).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), all
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h and 12i).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
@@ -78,8 +80,8 @@ class ScaledFrame:
     the integer arithmetic of include/homer_gpu.h section 12g (every sample can be reproduced from the formula there; hmr_gpu_scale_host is the same arithmetic on the host).
       frame: anything picture_of takes for a width x height picture (I420 tensor, (y, u, v) or (y, uv) views: a crop is just a view); width, height: ITS size.
     The same frame may be given to any number of sequences of a step - a resolution ladder - and the step makes ONE scaled load call for all of them.  Downscaling only, by
-    at most 8 per axis; equal sizes are legal and give what the plain frame gives.  source() returns the scaled picture of each rung, and export(ssd=True) gives the sums
-    against that SCALED picture, not against `frame`.
+    at most 8 per axis; equal sizes are legal and give what the plain frame gives.  source() returns the scaled picture of each rung, export(ssd=True) gives the sums
+    against that SCALED picture, not against `frame`, and export_rgb(source=True) shows the scaled picture as RGB.
     RGB sources are not taken here.  What works without a host round trip: encode the top rung from the RGBFrame, take its source(), and give that to the lower rungs as a
     ScaledFrame."""
 
@@ -103,7 +105,9 @@ class RGBFrame:
               or a [3, H, W] tensor of uint8, float16 or float32 (R, G, B planes; floats are clamped to 0 .. 1 and scaled by 255, NaN counts as 0) with unit stride along
               a row - views and channel slices of larger tensors are fine, `order` is ignored.
       matrix: "bt709" or "bt601"; full_range: False for 16 .. 235 / 16 .. 240, True for 0 .. 255.
-    The stream does NOT say which matrix or range was used (the parameter sets carry no colour description, as the reference's): tell the decoder's side by other means."""
+    The stream does NOT say which matrix or range was used (the parameter sets carry no colour description, as the reference's): tell the decoder's side by other means.
+    The same class describes what comes BACK: Encoder.export_rgb writes the reconstructed picture (or the encoded source) into an RGBFrame's tensor in its order, matrix
+    and range - the inverse arithmetic of section 12i - and takes the frame that was supplied as `reference` for the sums of squared differences in RGB."""
 
     def __init__(self, tensor, order="rgb", matrix="bt709", full_range=False):
         if matrix not in MATRICES:
@@ -164,6 +168,21 @@ def psnr(ssd, width, height):
     return tuple(out)
 
 
+def psnr_rgb(ssd, width, height):
+    """PSNR in dB of R, G, B and of the three together (99.99 for a zero sum) from three sums of squared differences - Python ints, e.g. export_rgb(reference=...)[1].tolist()
+    - of a width x height RGB picture, through hmr_gpu_psnr_rgb (include/homer_gpu.h section 12i).  Pure host arithmetic: needs neither torch nor a GPU."""
+    lib = _lib or _host_lib or C.CDLL(LIB_PATH)
+    lib.hmr_gpu_last_error.restype = C.c_char_p
+    lib.hmr_gpu_psnr_rgb.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    sums = [int(v) for v in ssd]
+    if len(sums) != 3 or min(sums) < 0:
+        raise ValueError(f"psnr_rgb: three non-negative sums, got {sums}")
+    out = (C.c_double * 4)()
+    if lib.hmr_gpu_psnr_rgb((C.c_uint64 * 3)(*sums), int(width), int(height), out) != 0:
+        raise ValueError((lib.hmr_gpu_last_error() or b"hmr_gpu_psnr_rgb").decode(errors="replace"))
+    return tuple(out)
+
+
 def ssim(sums, width, height):
     """The mean SSIM of each plane (Y, U, V; 1.0 for identical pictures, negative for inverted ones) from three SSIM sums - Python ints, e.g. Encoder.ssim().tolist() - of a
     width x height 4:2:0 picture, through hmr_gpu_ssim: sum / (2^30 x the plane's windows), include/homer_gpu.h section 12h.  Pure host arithmetic: needs neither torch
@@ -208,6 +227,7 @@ def load_library():
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
         lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
         lib.hmr_gpu_enc_ssim_device.argtypes = [C.POINTER(P), I, C.POINTER(I), P, P]
+        lib.hmr_gpu_enc_export_pictures_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), C.POINTER(RgbPicture), P, P]
         batch = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
         lib.hmr_gpu_enc_encode_batch.argtypes = batch
         lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = batch
@@ -346,6 +366,57 @@ def _export_sources(lib, device, encs, cfgs, slot, outs, nv12):
     return results
 
 
+def _rgb_output(cfg, out, order, dtype, matrix, full_range, device):
+    """the RGBFrame an RGB export writes: `out`, or one around a new packed [H, W, 3 or 4] uint8 tensor (`order` given) or a new planar [3, H, W] tensor of `dtype`"""
+    import torch
+    if out is not None:
+        if not isinstance(out, RGBFrame):
+            raise TypeError("export_rgb: out has to be an RGBFrame around the tensor to write")
+        return out
+    w, h = int(cfg.width), int(cfg.height)
+    if order is not None:
+        if order not in ORDERS:
+            raise ValueError(f"export_rgb: order has to be one of {sorted(ORDERS)}, got {order!r}")
+        if dtype not in (None, torch.uint8):
+            raise ValueError("export_rgb: a packed picture is uint8")
+        t = torch.empty((h, w, ORDERS[order][0]), dtype=torch.uint8, device=f"cuda:{device}")
+        return RGBFrame(t, order=order, matrix=matrix, full_range=full_range)
+    return RGBFrame(torch.empty((3, h, w), dtype=dtype or torch.uint8, device=f"cuda:{device}"), matrix=matrix, full_range=full_range)
+
+
+def _export_rgb(lib, device, encs, cfgs, which, outs, order, dtype, matrix, full_range, references):
+    """ONE hmr_gpu_enc_export_pictures_rgb_device for the encoders `encs`: (their tensors or None, an int64 tensor [len(encs), 3] or None).  outs: False (no pictures),
+    None, or a list of RGBFrame / None; references: None or a list of RGBFrame"""
+    import torch
+    n = len(encs)
+    picture = outs is not False
+    if not picture and references is None:
+        raise ValueError("export_rgb: neither the picture nor the sums asked for")
+    pics, refs, results, keep = None, None, None, []
+    if picture:
+        pics, results = (RgbPicture * n)(), []
+        for k, cfg in enumerate(cfgs):
+            target = _rgb_output(cfg, outs[k] if outs is not None else None, order, dtype, matrix, full_range, device)
+            pics[k], t = rgb_picture_of(target, cfg.width, cfg.height)
+            keep.append(t)
+            results.append(target.tensor)
+    if references is not None:
+        refs = (RgbPicture * n)()
+        for k, cfg in enumerate(cfgs):
+            if not isinstance(references[k], RGBFrame):
+                raise TypeError("export_rgb: reference has to be an RGBFrame")
+            # (sums alone: the reference's descriptor carries the matrix and range of the call)
+            frame = references[k] if picture else RGBFrame(references[k].tensor, order=references[k].order, matrix=matrix, full_range=full_range)
+            refs[k], t = rgb_picture_of(frame, cfg.width, cfg.height)
+            keep.append(t)
+    sums = torch.empty((n, 3), dtype=torch.int64, device=f"cuda:{device}") if refs is not None else None
+    if lib.hmr_gpu_enc_export_pictures_rgb_device((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([which] * n)), pics, refs, C.c_void_p(sums.data_ptr()) if sums is not None else None,
+                                                  _stream_of(device)) != 0:
+        _fail(lib, "hmr_gpu_enc_export_pictures_rgb_device")
+    del keep
+    return results, sums
+
+
 def _au_capacity(cfg):
     return max(1 << 20, int(cfg.width) * int(cfg.height) * 2)
 
@@ -403,6 +474,25 @@ class Encoder:
         if self.slot_used is None:
             raise RuntimeError("Encoder.ssim: nothing has been encoded yet")
         return _ssim(self.lib, self.device, [self.enc], self.slot_used)[0]
+
+    def export_rgb(self, out=None, order=None, dtype=None, matrix="bt709", full_range=False, reference=None, source=False):
+        """The reconstructed picture of the frame the last encode() encoded - with source=True: the picture that frame was encoded from, as it lies in the slot - as RGB,
+        converted by the egress kernel itself in the integer arithmetic of include/homer_gpu.h section 12i (bilinear chroma, every sample reproducible from the table there;
+        hmr_gpu_rgb_from_yuv_host is the same arithmetic on the host).
+          out: an RGBFrame around the tensor to write - its order, matrix and range are used, views and channel slices are fine, only the rows' bytes are written;
+               None: a new planar [3, H, W] tensor of `dtype` (torch.uint8 - the default -, float16 or float32: v / 255), or with `order` ("rgb", "bgra", ...: the alpha
+               byte is 255) a new packed [H, W, 3 or 4] uint8 tensor, in `matrix` and `full_range`; False (with a reference): no picture, the sums alone.
+          reference: an RGBFrame, normally the frame that was given to encode(): the call also returns the three exact sums of squared differences (R, G, B) between its
+               8-bit values and the 8-bit values of the conversion, as an int64 CUDA tensor [3]; psnr_rgb(sums.tolist(), W, H) gives dB.
+        Returns the tensor, (tensor, sums) with a reference, or the sums alone with out=False.  A float result fed back as an RGBFrame is the same 8-bit picture.  One launch
+        of k_egress_rgb, ordered on torch's current stream: what is queued there afterwards sees the results, nothing waits on the host."""
+        if self.slot_used is None:
+            raise RuntimeError("Encoder.export_rgb: nothing has been encoded yet")
+        pics, sums = _export_rgb(self.lib, self.device, [self.enc], [self.cfg], self.slot_used if source else -1, False if out is False else ([out] if out is not None else None),
+                                 order, dtype, matrix, full_range, [reference] if reference is not None else None)
+        if pics is None:
+            return sums[0]
+        return (pics[0], sums[0]) if sums is not None else pics[0]
 
     def source(self, out=None, nv12=False):
         """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a ScaledFrame the scaled picture.  `out` and nv12 as in
@@ -523,6 +613,33 @@ class BatchEncoder:
         table = torch.full((len(self.encs), 3), -(1 << 63), dtype=torch.int64, device=sums.device)
         table[torch.tensor(live, device=sums.device)] = sums
         return table
+
+    def export_rgb(self, out=None, order=None, dtype=None, matrix="bt709", full_range=False, reference=None, source=False):
+        """As Encoder.export_rgb, for every sequence that was given a picture in the last step(), with ONE launch - also with access units outstanding.  `out` and
+        `reference`, when given, are lists with one entry per sequence (the entries of idle sequences are ignored; out=False: the sums alone).  Returns a list of tensors
+        with one entry per sequence (None for a sequence without a picture in that step), (that list, sums) with references, or the sums alone with out=False; sums: an
+        int64 CUDA tensor [sequences, 3] whose rows of idle sequences are -1."""
+        import torch
+        live = self.last_live
+        if not live:
+            raise RuntimeError("BatchEncoder.export_rgb: the last step encoded nothing")
+        for name, given in (("outputs", out), ("references", reference)):
+            if given is not None and given is not False and len(given) != len(self.encs):
+                raise ValueError(f"BatchEncoder.export_rgb: {len(self.encs)} sequences, {len(given)} {name}")
+        pics, sums = _export_rgb(self.lib, self.device, [self.encs[i] for i in live], [self.cfgs[i] for i in live], self.slot_used if source else -1,
+                                 False if out is False else ([out[i] for i in live] if out is not None else None), order, dtype, matrix, full_range,
+                                 [reference[i] for i in live] if reference is not None else None)
+        pictures, table = None, None
+        if pics is not None:
+            pictures = [None] * len(self.encs)
+            for k, i in enumerate(live):
+                pictures[i] = pics[k]
+        if sums is not None:
+            table = torch.full((len(self.encs), 3), -1, dtype=torch.int64, device=sums.device)
+            table[torch.tensor(live, device=sums.device)] = sums
+        if pictures is None:
+            return table
+        return (pictures, table) if table is not None else pictures
 
     def source(self, out=None, nv12=False):
         """As Encoder.source, for every sequence that was given a picture in the last step(), with ONE launch: a list with one entry per sequence (None for a sequence

@@ -909,6 +909,62 @@ int hmr_gpu_ssim(const int64_t sums[3], int width, int height, double ssim[3]);
 int hmr_gpu_ssim_host(const hmr_gpu_picture *a, const hmr_gpu_picture *b, int width, int height, int64_t sums[3]);
 
 /* ------------------------------------------------------------------------------------------------
+ * 12i. Reconstructed pictures as RGB, left in device memory: colour conversion inside the egress (no counterpart in the reference)
+ *     The mirror image of 12f, as 12e mirrors 12d.  hmr_gpu_enc_export_pictures_rgb_device hands pictures of n encoders (1 .. 512; sizes, forms, matrices and ranges may
+ *     be mixed within a call) to the caller as RGB in DEVICE memory and / or leaves the exact sums of squared differences between each picture's 8-bit R, G, B values
+ *     and an RGB picture of the caller's - the frame that was actually supplied - with ONE launch of a bandwidth-bound kernel (k_egress_rgb, picture_io.hip) and no host
+ *     synchronisation.  Nothing on the encode path is touched: every stream stays byte-identical.
+ *     which[i]: -1: the encoder's final picture, exactly "the picture" of 12e (an encoder without an encoded picture is refused); >= 0: whatever picture slot which[i]
+ *     of encs[i] holds when the launch runs - the encoded source seen as RGB; this needs no prior encode.
+ *     outs (or NULL: no pictures): n descriptors of OUTPUT pictures - hmr_gpu_rgb_picture as in 12f, but the call WRITES through the plane pointers (the const of the
+ *     type describes the ingest).  matrix and full_range of outs[i] choose the row of the table below.  HMR_GPU_RGB_PACKED8 with 3 or 4 bytes a pixel and any offset[]
+ *     (the fourth byte is written as 255), _PLANAR8, _PLANAR_F32: x = (float)v / 255.0f, ONE correctly rounded binary32 division (np.float32(v) / np.float32(255)),
+ *     _PLANAR_F16: that binary32 value rounded to binary16, to nearest even.  For both float forms 12f's quantisation of x gives v back for all 256 values: an output
+ *     fed back through 12f is the same 8-bit picture.  Only the bytes of the rows are written - [plane + y * pitch, plane + y * pitch + row bytes).
+ *     refs with dev_ssd (both NULL or both given; dev_ssd: device memory, n x 3 values): refs[i] is the caller's original RGB picture in any form of 12f (its matrix and
+ *     range fields are checked but not used - except when outs is NULL: then THEY choose the row of the table); dev_ssd[3 * i + c] = the sum over width x height of
+ *     (q(ref) - v)^2 for c = R, G, B, exact, q being 12f's 8-bit quantisation of the reference's sample and v the 8-bit value of the arithmetic below (also when the
+ *     output form is float).  The values are overwritten, not accumulated.  hmr_gpu_psnr_rgb turns three sums into 10 * log10(255 * 255 * width * height / sum) for R,
+ *     G and B, and psnr[3]: the same expression over all 3 * width * height samples; 99.99 where the sum is 0, as hmr_gpu_psnr.  Pure host code.
+ *     The arithmetic is defined in integers, so that a caller can reproduce every sample (homerhevc_amd/csrc/yuv_rgb.h holds it once, for the kernel and the host):
+ *       inputs: 8-bit Y [H, W] and U, V [H / 2, W / 2]; chroma sample (cx, cy) sited at the centre of the luma block (2 cx .. 2 cx + 1, 2 cy .. 2 cy + 1) - what 12f makes.
+ *       chroma at luma position (x, y): bilinear, scaled by 16, not rounded.  Rows, with cy = y >> 1: an even y takes rows cy - 1 (weight 1) and cy (weight 3), an odd y
+ *         rows cy (weight 3) and cy + 1 (weight 1); columns: the same rule with x; indices are clamped to the plane, so an edge sample gets the full weight.
+ *         C16 = sum of wy wx C, 0 .. 4080; a flat plane gives exactly 16 C.
+ *       per pixel:  L = 16 Ky (Y - yoff), U' = U16 - 2048, V' = V16 - 2048
+ *                   R = clamp((L + Rv V' + 131072) >> 18, 0, 255)
+ *                   G = clamp((L + Gu U' + Gv V' + 131072) >> 18, 0, 255)
+ *                   B = clamp((L + Bu U' + 131072) >> 18, 0, 255);  >> is an arithmetic shift of a 32-bit signed value
+ *       matrix, range     Ky      Rv      Gu      Gv       Bu      yoff
+ *       BT.601 limited    19077   26149   -6419   -13320   33050   16
+ *       BT.601 full       16384   22970   -5638   -11700   29032   0
+ *       BT.709 limited    19077   29372   -3494   -8731    34610   16
+ *       BT.709 full       16384   25802   -3069   -7670    30402   0
+ *     Each coefficient is round(real x 2^14) of the inverse BT matrix (255 / 219 and 255 / 224 x 2 (1 - Kr), ... in limited range; 1 and 2 (1 - Kr), ... in full range).
+ *     Every output is within 0.52 of the real-valued formula applied to the same bilinear chroma; flat chroma 128 gives R = G = B, in full range R = G = B = Y at all 256
+ *     levels; a flat picture of any colour through 12f and back returns each channel within 1 (full range) or 2 (limited range).
+ *     consumer_stream: as in 12e, word for word.  The launch runs on the first encoder's stream behind an event recorded on consumer_stream and behind whatever the
+ *     encoders' streams and the streams that wrote the final pictures hold; consumer_stream and the encoders' streams go on behind the launch; the host waits for
+ *     nothing.  The producer of the reference pictures must be on consumer_stream, or ordered before it.
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is queued, every encoder left working: n outside 1 .. 512, NULL encs or which, a NULL
+ *     encoder, encoders on different devices, both outs and refs NULL, refs without dev_ssd or the reverse, which below -1 or a slot that does not exist, which = -1 on
+ *     an encoder without an encoded picture, whatever hmr_gpu_rgb_picture_check refuses for outs[i] or refs[i] at the encoder's picture size, sums for a picture wider
+ *     than 8192 samples, an output plane, a reference plane or dev_ssd that hipPointerGetAttributes does not report as device memory of the encoders' device.
+ *     hmr_gpu_rgb_from_yuv_host: the same arithmetic in a plain loop over HOST memory, from tightly packed I420 planes (y: width x height; u, v: width / 2 x height / 2)
+ *     into a descriptor whose planes are host pointers.  hmr_gpu_rgb_ssd_host: the same sums between two RGB pictures in host memory, in any two forms.  Both are pure
+ *     host code - no device, no context - and refuse what hmr_gpu_rgb_picture_check refuses and NULL arguments.  hmr_gpu_psnr_rgb refuses NULL arguments and an odd or
+ *     non-positive width or height.
+ *     Out of scope: other chroma sitings or upsampling filters, 10-bit or bfloat16 output, a colour description in the VUI (12f: the stream does not say which matrix
+ *     or range was used), SSIM in the RGB domain, scaled RGB export.
+ * ------------------------------------------------------------------------------------------------ */
+int hmr_gpu_enc_export_pictures_rgb_device(hmr_gpu_enc **encs, int n, const int *which, const hmr_gpu_rgb_picture *outs, const hmr_gpu_rgb_picture *refs, uint64_t *dev_ssd,
+					   void *consumer_stream);
+int hmr_gpu_enc_export_picture_rgb_device(hmr_gpu_enc *enc, int which, const hmr_gpu_rgb_picture *out, const hmr_gpu_rgb_picture *ref, uint64_t *dev_ssd, void *consumer_stream);
+int hmr_gpu_rgb_from_yuv_host(const uint8_t *y, const uint8_t *u, const uint8_t *v, int width, int height, const hmr_gpu_rgb_picture *out);
+int hmr_gpu_rgb_ssd_host(const hmr_gpu_rgb_picture *a, const hmr_gpu_rgb_picture *b, int width, int height, uint64_t ssd[3]);
+int hmr_gpu_psnr_rgb(const uint64_t ssd[3], int width, int height, double psnr[4]);
+
+/* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
  *     Replaces the per-block interpolation calls of the motion search and of motion compensation - the sixteen planes of
  *     hmr_half_pixel_estimation_luma_hm / hmr_quarter_pixel_estimation_luma_hm (hmr_motion_inter.c:395,442) and
