@@ -156,6 +156,7 @@ struct hmr_gpu_enc {
 	JobRing<EgressJob> egress;
 	JobRing<SsimJob> ssim;
 	JobRing<RgbEgressJob> egress_rgb;
+	JobRing<RgbScaleJob> scale_rgb;                       // (k_rgb_ladder)
 	// every encoder: whether d_pic[cur] holds an encoded frame's final picture, the stream whose work wrote it (its own, or the lead's of a batch or chain launch),
 	// events for that stream and its own (an export call waits behind both)
 	bool has_picture = false;
@@ -889,6 +890,7 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	e->egress.release();
 	e->ssim.release();
 	e->egress_rgb.release();
+	e->scale_rgb.release();
 	if (e->ev_pic_done) (void)hipEventDestroy(e->ev_pic_done);
 	if (e->ev_own_done) (void)hipEventDestroy(e->ev_own_done);
 	if (e->d_batch) (void)hipFree(e->d_batch);

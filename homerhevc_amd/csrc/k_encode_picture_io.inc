@@ -1,5 +1,5 @@
 // Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
-// (include/homer_gpu.h sections 12d, 12e, 12f, 12g, 12h and 12i).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim / k_egress_rgb (picture_io.hip)
+// (include/homer_gpu.h sections 12d, 12e, 12f, 12g, 12h, 12i and 12j).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_downscale / k_rgb_ladder / k_egress / k_ssim / k_egress_rgb (picture_io.hip)
 // on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
 //   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
 //   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
@@ -47,7 +47,7 @@ int check_planes(const char *fn, const hmr_gpu_picture *pics, int n, int device)
 }  // namespace
 
 namespace {
-// what the load calls of sections 12d, 12f and 12g refuse before they look at a picture
+// what the load calls of sections 12d, 12f, 12g and 12j refuse before they look at a picture
 int check_load(const char *fn, hmr_gpu_enc **encs, int n, const int *slots, const void *pics)
 {
 	static_assert(PICTURE_MAX_JOBS == BATCH_MAX, "a load call feeds a batch call, an export call follows one");
@@ -269,6 +269,38 @@ extern "C" int hmr_gpu_enc_load_sources_scaled_device(hmr_gpu_enc **encs, int n,
 extern "C" int hmr_gpu_enc_load_source_scaled_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_picture *pic, void *producer_stream)
 {
 	return hmr_gpu_enc_load_sources_scaled_device(&enc, 1, &slot, pic, producer_stream);
+}
+
+// ---- section 12j: larger RGB pictures in, converted and area-averaged down to the encoders' sizes ----
+extern "C" int hmr_gpu_enc_load_sources_scaled_rgb_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_scaled_rgb_picture *pics, void *producer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_load_sources_scaled_rgb_device";
+	int rc;
+	if ((rc = check_load(fn, encs, n, slots, pics))) return rc;
+	const int device = encs[0]->ctx->device;
+	for (int i = 0; i < n; i++)      // the descriptor against the SOURCE's size, then the pair of sizes
+		if (hmr_gpu_rgb_picture_check(&pics[i].pic, pics[i].width, pics[i].height) != HMR_GPU_OK ||
+		    hmr_gpu_scale_check(pics[i].width, pics[i].height, encs[i]->seq.width, encs[i]->seq.height) != HMR_GPU_OK) {
+			const std::string why = hmr_gpu_last_error();
+			return picture_refuse(fn, i, why.c_str());
+		}
+	HIP_TRY(hipSetDevice(device));
+	static const char *const names[3] = {"plane[0]", "plane[1]", "plane[2]"};
+	for (int i = 0; i < n; i++)
+		for (int c = 0; c < (pics[i].pic.format == HMR_GPU_RGB_PACKED8 ? 1 : 3); c++)
+			if (!on_device(pics[i].pic.plane[c], device)) return not_device(fn, i, names[c], device);
+	if ((rc = make_slots(encs, n, slots))) return rc;
+	std::vector<RgbScaleJob> jobs(n);
+	for (int i = 0; i < n; i++) {
+		const hmr_gpu_enc *e = encs[i];
+		jobs[i] = hmr_rgb_scale_job(pics[i].pic, pics[i].width, pics[i].height, e->src[slots[i]].p, e->seq.src_stride_y, e->seq.src_stride_c, e->seq.width, e->seq.height);
+	}
+	return run_load(encs[0]->scale_rgb, hmr_rgb_scale_launch, encs, n, jobs.data(), producer_stream);
+}
+
+extern "C" int hmr_gpu_enc_load_source_scaled_rgb_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_rgb_picture *pic, void *producer_stream)
+{
+	return hmr_gpu_enc_load_sources_scaled_rgb_device(&enc, 1, &slot, pic, producer_stream);
 }
 
 extern "C" int hmr_gpu_enc_export_sources_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_picture *outs, void *consumer_stream)

@@ -1,6 +1,6 @@
 // Picture conversion on the device (picture_io.hip): 8-bit 4:2:0 pictures in device memory <-> the int16 planes of the frame encoder, a batch of pictures per launch.
 // Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture); RGB pictures (8-bit packed or planar, binary16, binary32) -> the same planes, colour
-// converted in the same pass (rgb_yuv.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h).  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
+// converted in the same pass (rgb_yuv.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h); RGB pictures of a larger size -> the same planes, converted and area-averaged in the same pass.  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
 // squared differences against the int16 source planes of a picture slot; the final pictures or the slots' pictures -> RGB pictures in any of the ingest's forms, colour
 // converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  A launch reads its pictures from a job table; JobRing holds the tables of one encoder and
 // run_jobs queues one launch, ordered against the caller's stream by events (k_encode_picture_io.inc and the host-memory entries of k_encode_object.inc use it).
@@ -82,6 +82,23 @@ struct ScaleJob {
 };
 static_assert(sizeof(ScaleJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
+// one picture of a downscaling RGB ingest launch (k_rgb_ladder): the caller's src_w x src_h RGB picture, converted by rgb_yuv.h's arithmetic sample by sample in
+// registers and area-averaged by scale_area.h's into the dst_w x dst_h planes (section 12j: the composition of 12f and 12g without the picture in between)
+struct RgbScaleJob {
+	const uint8_t *src[3];       // HMR_GPU_RGB_PACKED8: src[0] alone; planar: R, G, B
+	int64_t pitch[3];            // bytes from row to row
+	int16_t *dst[3];             // the planes at sample (0, 0); 16-byte aligned
+	int32_t stride_y, stride_c;  // elements, multiples of 8
+	int32_t src_w, src_h, dst_w, dst_h;
+	int32_t format, pixel_bytes; // of the RGB picture
+	int32_t offset[3];           // PACKED8: byte of R, G, B inside a pixel
+	int32_t tile_rows;           // output rows of a tile, as ScaleJob's (hmr_rgb_scale_job)
+	RgbMatrix m;                 // the nine coefficients and yoff: a launch mixes matrices and ranges
+	ScaleAxis ax, ay;            // the reduced ratios (the same for luma and chroma) with the reciprocals of dx, dy
+	uint32_t den, mden;          // sx * sy and its reciprocal (hmr_scale_magic)
+};
+static_assert(sizeof(RgbScaleJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
+
 // one picture of an SSIM launch (k_ssim): the sums of ssim_window.h's window values between the int16 planes a and b
 struct SsimJob {
 	const int16_t *a[3];         // the slot's planes at sample (0, 0); 16-byte aligned, read-only
@@ -98,6 +115,14 @@ static inline double hmr_ssim_bytes(int width, int height) { return 6.0 * (doubl
 // Algorithmic bytes of one picture through k_downscale (tools/scale_ingest_bench.py restates it): every sample of the source is read once, the int16 Y, U, V
 // planes of the destination are written.
 static inline double hmr_scale_bytes(int src_w, int src_h, int dst_w, int dst_h) { return 1.5 * (double)src_w * src_h + 3.0 * (double)dst_w * dst_h; }
+
+// Algorithmic bytes of one picture through k_rgb_ladder (tools/rgb_scale_ingest_bench.py restates it): the luma tiles and the chroma tiles each read the RGB
+// source - twice its 3, 4, 3, 6 or 12 Ws Hs bytes - and the int16 Y, U, V planes of the destination are written.
+static inline double hmr_rgb_scale_bytes(int src_w, int src_h, int dst_w, int dst_h, int format, int pixel_bytes)
+{
+	const double per_pixel = format == HMR_GPU_RGB_PACKED8 ? pixel_bytes : format == HMR_GPU_RGB_PLANAR8 ? 3 : format == HMR_GPU_RGB_PLANAR_F16 ? 6 : 12;
+	return 2.0 * per_pixel * (double)src_w * src_h + 3.0 * (double)dst_w * dst_h;
+}
 
 // Algorithmic bytes of one width x height picture through k_ingest_rgb (tools/rgb_ingest_bench.py restates it): every sample of the source is read once -
 // 3 or 4 bytes per pixel packed, 3 planar 8-bit, 6 planar binary16, 12 planar binary32 - and the int16 Y, U, V planes are written: 4 W H in every case.
@@ -130,15 +155,18 @@ static inline double hmr_egress_rgb_bytes(int width, int height, int format, int
 }
 
 // The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of k_ingest /
-// k_ingest_rgb / k_downscale / k_egress / k_egress_rgb / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
+// k_ingest_rgb / k_downscale / k_rgb_ladder / k_egress / k_egress_rgb / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n);
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n);
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n);
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n);
+int hmr_rgb_scale_launch(hipStream_t stream, const RgbScaleJob *h_jobs, RgbScaleJob *d_jobs, int n);
 int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n);
 int hmr_egress_rgb_launch(hipStream_t stream, const RgbEgressJob *h_jobs, RgbEgressJob *d_jobs, int n);
 // the job of one picture: the sizes have passed hmr_gpu_scale_check; the ratios, their reciprocals and the tile height are derived here
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
+// the same for an RGB source: the descriptor has passed hmr_gpu_rgb_picture_check for the source's size
+RgbScaleJob hmr_rgb_scale_job(const hmr_gpu_rgb_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
 
 // The job tables of the calls one encoder leads, in one direction: a ring of tables in page-locked memory (a table is written again only when the launch that read it
 // is known to be over: ev_turn), their copy on the device, the events towards the outside stream (producer or consumer) and towards the streams that go on behind a launch.

@@ -18,6 +18,9 @@
 // k_downscale (section 12g): 8-bit pictures of a larger size into the same int16 planes, area-averaged by the integer arithmetic of scale_area.h in the same pass; its
 // mapping (tiles through LDS) is described at the kernel.
 //
+// k_rgb_ladder (section 12j): RGB pictures of a larger size into the same int16 planes, converted as k_ingest_rgb converts and area-averaged as k_downscale averages
+// in the same pass; described at the kernel.
+//
 // Mapping (struct Chunk): blockIdx.y = picture (a record of the job table), blockIdx.x = a chunk of CHUNK_ROWS rows of it - first the luma rows, then the chroma rows (a
 // chroma row is its U and its V part: as many 8-bit bytes as a luma row) - so that one grid covers the three planes of every picture; pictures smaller than the largest
 // of the launch leave their last chunks empty.  A lane takes a span of 16 samples.  Ingest: one 16-byte load, two 16-byte stores of int16; NV12 chroma: one 16-byte load
@@ -176,6 +179,11 @@ template <int V> struct RgbForm {
 	static constexpr int WORDS = V == RGB_PACKED3 ? 3 * PX / 4 : V == RGB_PACKED4 ? PX : 3 * PLANE;
 };
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+// which of the forms RGB_PACKED3 .. RGB_F32 a descriptor's format and pixel bytes are
+__host__ __device__ __forceinline__ int rgb_form(int format, int pixel_bytes)
+{
+	return format == HMR_GPU_RGB_PACKED8 ? (pixel_bytes == 3 ? RGB_PACKED3 : RGB_PACKED4) : format == HMR_GPU_RGB_PLANAR8 ? RGB_PLANAR8 : format == HMR_GPU_RGB_PLANAR_F16 ? RGB_F16 : RGB_F32;
+}
 
 template <int V, class Job>
 __device__ __forceinline__ void rgb_load_row(const Job &j, int x, int y, uint32_t *raw)
@@ -372,11 +380,14 @@ struct ScaleTile {
 };
 __host__ __device__ __forceinline__ int scale_tiles_x(int w, bool luma) { return luma ? (w + SCALE_TILE_W - 1) / SCALE_TILE_W : ((w >> 1) + SCALE_TILE_W / 2 - 1) / (SCALE_TILE_W / 2); }
 __host__ __device__ __forceinline__ int scale_tiles_y(int h, int rows, bool luma) { return ((luma ? h : h >> 1) + rows - 1) / rows; }
-__host__ __device__ __forceinline__ int scale_tiles(const ScaleJob &j)
+template <class Job>
+__host__ __device__ __forceinline__ int scale_tiles(const Job &j)
 {
 	return scale_tiles_x(j.dst_w, true) * scale_tiles_y(j.dst_h, j.tile_rows, true) + scale_tiles_x(j.dst_w, false) * scale_tiles_y(j.dst_h, j.tile_rows, false);
 }
-__host__ __device__ __forceinline__ ScaleTile scale_tile(const ScaleJob &j, int b)
+// (Job: ScaleJob, or RgbScaleJob - whose source is never in pairs, and whose chroma tile's columns are columns of the converted chroma planes)
+template <class Job>
+__host__ __device__ __forceinline__ ScaleTile scale_tile(const Job &j, int b, bool nv12)
 {
 	ScaleTile t;
 	const int luma_tiles = scale_tiles_x(j.dst_w, true) * scale_tiles_y(j.dst_h, j.tile_rows, true);
@@ -388,7 +399,7 @@ __host__ __device__ __forceinline__ ScaleTile scale_tile(const ScaleJob &j, int 
 	const int pw = t.luma ? j.dst_w : j.dst_w >> 1, ph = t.luma ? j.dst_h : j.dst_h >> 1, sw = t.luma ? j.src_w : j.src_w >> 1;
 	t.x0 = tx * per; t.nx = pw - t.x0 < per ? pw - t.x0 : per;
 	t.y0 = ty * j.tile_rows; t.ny = ph - t.y0 < j.tile_rows ? ph - t.y0 : j.tile_rows;
-	t.pairs = !t.luma && j.format == HMR_GPU_PIC_NV12;
+	t.pairs = !t.luma && nv12;
 	t.c0 = t.empty ? 0 : (int)hmr_scale_first(j.ax, (uint32_t)t.x0);
 	const int c1 = t.empty ? 0 : (int)hmr_scale_end(j.ax, (uint32_t)(t.x0 + t.nx - 1));
 	t.streams = t.luma || t.pairs ? 1 : 2;
@@ -401,14 +412,50 @@ __host__ __device__ __forceinline__ ScaleTile scale_tile(const ScaleJob &j, int 
 // the word of LDS (inside a tile row) that holds the column sum of byte `b` of a stream's window
 __device__ __forceinline__ int scale_word(int b) { return (b >> 4) * SCALE_SPAN_WORDS + (b & 15); }
 
+// The horizontal pass and the store pass of a tile whose column sums lie in `sums` (every lane of the workgroup comes here, behind the barrier that follows the
+// vertical pass): k_downscale and k_rgb_ladder share them.
+__device__ __forceinline__ void scale_finish(const ScaleTile &k, const ScaleAxis &ax, uint32_t den, uint32_t mden, const uint32_t *sums, u32x4 *outs4, int row_words, int16_t *dst_y, int16_t *dst_u,
+					     int16_t *dst_v, int stride_y, int stride_c)
+{
+	int16_t *outs = (int16_t *)outs4;
+	const int t = (int)threadIdx.x;
+	// horizontal: an output sample per lane; a chroma tile row: SCALE_TILE_W / 2 of U, then as many of V
+	const int half_w = SCALE_TILE_W / 2;
+	for (int i = t; i < k.ny * SCALE_TILE_W; i += HMR_BLOCK) {
+		const int r = i / SCALE_TILE_W, q = i - r * SCALE_TILE_W;
+		const int second = k.luma ? 0 : q / half_w, xx = k.luma ? q : q - second * half_w;
+		if (xx >= k.nx) continue;
+		const uint32_t x = (uint32_t)(k.x0 + xx), hi = (x + 1) * ax.s;
+		const uint32_t *line = sums + r * row_words + (second && !k.pairs ? k.spans * SCALE_SPAN_WORDS : 0);
+		uint32_t sum = den >> 1;
+		for (uint32_t c = hmr_scale_first(ax, x); c * ax.d < hi; c++) {
+			const int rel = (int)c - k.c0;
+			sum += hmr_scale_weight(ax, x, c) * line[scale_word(k.pairs ? 2 * rel + second : rel)];
+		}
+		outs[i] = (int16_t)hmr_scale_div(sum, den, mden);
+	}
+	__syncthreads();
+
+	// eight samples per lane to the planes
+	const int stride = k.luma ? stride_y : stride_c;
+	for (int i = t; i < k.ny * (SCALE_TILE_W / 8); i += HMR_BLOCK) {
+		const int r = i / (SCALE_TILE_W / 8), q = i - r * (SCALE_TILE_W / 8);
+		const int second = k.luma ? 0 : q / (half_w / 8), xx = (k.luma ? q : q - second * (half_w / 8)) << 3;
+		if (xx >= k.nx) continue;
+		const samples_out d = (samples_out)(k.luma ? dst_y : second ? dst_v : dst_u) + (size_t)(k.y0 + r) * stride + k.x0 + xx;
+		if (k.nx - xx >= 8) *(GLOBAL_AS u32x4 *)d = outs4[i];
+		else
+			for (int m = 0; m < k.nx - xx; m++) d[m] = outs[8 * i + m];      // (a row's tail)
+	}
+}
+
 __global__ __launch_bounds__(HMR_BLOCK) void k_downscale(const ScaleJob *jobs)
 {
 	__shared__ u32x4 sums4[SCALE_LDS_WORDS / 4];
 	__shared__ u32x4 outs4[SCALE_MAX_ROWS * SCALE_TILE_W / 8];
 	uint32_t *sums = (uint32_t *)sums4;
-	int16_t *outs = (int16_t *)outs4;
 	const ScaleJob j = jobs[blockIdx.y];
-	const ScaleTile k = scale_tile(j, (int)blockIdx.x);
+	const ScaleTile k = scale_tile(j, (int)blockIdx.x, j.format == HMR_GPU_PIC_NV12);
 	if (k.empty) return;
 	const int t = (int)threadIdx.x, total = k.total(), row_words = total * SCALE_SPAN_WORDS;
 	const ScaleAxis ax = j.ax, ay = j.ay;
@@ -444,34 +491,175 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_downscale(const ScaleJob *jobs)
 	}
 	__syncthreads();
 
-	// horizontal: an output sample per lane; a chroma tile row: SCALE_TILE_W / 2 of U, then as many of V
-	const int half_w = SCALE_TILE_W / 2;
-	for (int i = t; i < k.ny * SCALE_TILE_W; i += HMR_BLOCK) {
-		const int r = i / SCALE_TILE_W, q = i - r * SCALE_TILE_W;
-		const int second = k.luma ? 0 : q / half_w, xx = k.luma ? q : q - second * half_w;
-		if (xx >= k.nx) continue;
-		const uint32_t x = (uint32_t)(k.x0 + xx), hi = (x + 1) * ax.s;
-		const uint32_t *line = sums + r * row_words + (second && !k.pairs ? k.spans * SCALE_SPAN_WORDS : 0);
-		uint32_t sum = j.den >> 1;
-		for (uint32_t c = hmr_scale_first(ax, x); c * ax.d < hi; c++) {
-			const int rel = (int)c - k.c0;
-			sum += hmr_scale_weight(ax, x, c) * line[scale_word(k.pairs ? 2 * rel + second : rel)];
+	scale_finish(k, ax, j.den, j.mden, sums, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
+}
+
+// ---- downscaling RGB ingest (section 12j) ----
+// k_rgb_ladder: RGB pictures of one size, in any of k_ingest_rgb's forms, into the int16 planes of a smaller - or equal - size: every slot sample is section 12g's
+// area average of the 8-bit 4:2:0 picture section 12f makes of the source, and that picture never exists in memory.  12f's luma is a function of one pixel and its
+// chroma of one 2 x 2 block, so a lane converts what it has loaded in registers (rgb_load_row, rgb_pixel, hmr_rgb_luma, hmr_rgb_chroma) and accumulates the weighted
+// 8-bit results: the column sums are k_downscale's, bit for bit, and so are the tiles, the LDS layout, the horizontal pass and the stores (scale_tile, scale_finish).
+// Luma tile: a lane takes ONE output row and a span of 16 source pixels, and walks the row's source rows (at most nine); per source row the loads of k_ingest_rgb's
+// form (binary32: two halves of eight pixels), sixteen luma samples, sixteen multiply-adds.  Chroma tile: a lane takes ONE chroma output row and a span of EIGHT
+// source chroma columns - sixteen pixels, so a source chroma row costs the loads of a luma lane twice (the two pixel rows under it) - forms the eight 2 x 2 sums and
+// accumulates U and V apart; its sixteen sums are half a span of the U stream and half a span of the V stream (two 16-byte LDS stores each: eight lanes of such a
+// store hit six different quads of banks, two of them twice).  Sixteen chroma columns a lane would hold 32 sums beside two rows of 32 pixels: eight keeps every form
+// free of spills.  A span that reaches past the end of a row goes sample by sample (rgb_sample), every sample checked against the width.
+// Luma and chroma tiles each read the RGB source: 2 x (3, 4, 3, 6 or 12) Ws Hs bytes read, 3 Wd Hd written per picture (hmr_rgb_scale_bytes in picture_io.h).  No lane
+// reads a byte outside [plane + y * pitch, plane + y * pitch + row bytes) or writes outside dst_w x dst_h.  The weighted sums fit 32 bits as section 12g's do: the
+// converted samples are 8-bit.  LDS: k_downscale's.
+template <int FMT>
+__device__ __forceinline__ void ladder_sample(const RgbScaleJob &j, int px, int py, int &r, int &g, int &b)
+{
+	constexpr bool packed = FMT == HMR_GPU_RGB_PACKED8;
+	r = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[0], j.pitch[0], FMT, j.pixel_bytes, j.offset[0], px, py);
+	g = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[packed ? 0 : 1], j.pitch[packed ? 0 : 1], FMT, j.pixel_bytes, j.offset[1], px, py);
+	b = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[packed ? 0 : 2], j.pitch[packed ? 0 : 2], FMT, j.pixel_bytes, j.offset[2], px, py);
+}
+
+// the weighted column sums of a luma tile: (output row, span of 16 source pixels) per lane
+template <int V, int FMT>
+__device__ __forceinline__ void ladder_luma(const RgbScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
+{
+	typedef RgbForm<V> F;
+	const int sh[3] = {8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]};
+	const ScaleAxis ay = j.ay;
+	for (int i = (int)threadIdx.x; i < k.spans * k.ny; i += HMR_BLOCK) {
+		const int r = i / k.spans, p = i - r * k.spans, x = k.c0 + (p << 4);
+		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
+		uint32_t acc[16];
+#pragma unroll
+		for (int m = 0; m < 16; m++) acc[m] = 0;
+		const bool whole = x + 16 <= j.src_w;
+		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
+			const uint32_t w = hmr_scale_weight(ay, y, sy);
+			if (whole) {
+#pragma unroll
+				for (int h = 0; h < 16 / F::PX; h++) {
+					uint32_t raw[F::WORDS];
+					rgb_load_row<V>(j, x + F::PX * h, (int)sy, raw);
+#pragma unroll
+					for (int m = 0; m < F::PX; m++) {
+						int cr, cg, cb;
+						rgb_pixel<V>(raw, m, sh, cr, cg, cb);
+						acc[F::PX * h + m] += w * (uint32_t)hmr_rgb_luma(j.m, cr, cg, cb);
+					}
+				}
+			} else {
+#pragma unroll
+				for (int m = 0; m < 16; m++) {      // (the row's last pixels: sample by sample)
+					if (x + m >= j.src_w) continue;
+					int cr, cg, cb;
+					ladder_sample<FMT>(j, x + m, (int)sy, cr, cg, cb);
+					acc[m] += w * (uint32_t)hmr_rgb_luma(j.m, cr, cg, cb);
+				}
+			}
 		}
-		outs[i] = (int16_t)hmr_scale_div(sum, j.den, j.mden);
+		u32x4 *o = &sums4[(r * row_words + p * SCALE_SPAN_WORDS) >> 2];
+#pragma unroll
+		for (int m = 0; m < 4; m++) o[m] = u32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
+	}
+}
+
+// four chroma columns from pixels i0 .. i0 + 7 of the two pixel rows a, b, weighted into au, av
+template <int V>
+__device__ __forceinline__ void ladder_chroma4(const uint32_t *a, const uint32_t *b, int i0, const RgbMatrix &m, const int sh[3], uint32_t w, uint32_t *au, uint32_t *av)
+{
+#pragma unroll
+	for (int p = 0; p < 4; p++) {
+		int r0, g0, b0, r1, g1, b1, r2, g2, b2, r3, g3, b3;
+		rgb_pixel<V>(a, i0 + 2 * p, sh, r0, g0, b0);
+		rgb_pixel<V>(a, i0 + 2 * p + 1, sh, r1, g1, b1);
+		rgb_pixel<V>(b, i0 + 2 * p, sh, r2, g2, b2);
+		rgb_pixel<V>(b, i0 + 2 * p + 1, sh, r3, g3, b3);
+		const int sr = r0 + r1 + r2 + r3, sg = g0 + g1 + g2 + g3, sb = b0 + b1 + b2 + b3;
+		au[p] += w * (uint32_t)hmr_rgb_chroma(m.u, sr, sg, sb);
+		av[p] += w * (uint32_t)hmr_rgb_chroma(m.v, sr, sg, sb);
+	}
+}
+
+// the weighted column sums of a chroma tile: (chroma output row, span of 8 source chroma columns) per lane; the U sums to the first stream, the V sums to the second
+template <int V, int FMT>
+__device__ __forceinline__ void ladder_chroma(const RgbScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
+{
+	typedef RgbForm<V> F;
+	const int sh[3] = {8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]};
+	const ScaleAxis ay = j.ay;
+	const int halves = 2 * k.spans, cw = k.row_bytes;      // (the source's chroma width)
+	for (int i = (int)threadIdx.x; i < halves * k.ny; i += HMR_BLOCK) {
+		const int r = i / halves, q = i - r * halves, cx = k.c0 + (q << 3);
+		if (cx >= cw) continue;      // (the second half of the last span may lie beyond the plane: no tap reads its sums)
+		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
+		uint32_t au[8], av[8];
+#pragma unroll
+		for (int m = 0; m < 8; m++) au[m] = av[m] = 0;
+		const bool whole = cx + 8 <= cw;
+		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
+			const uint32_t w = hmr_scale_weight(ay, y, sy);
+			const int py = 2 * (int)sy;
+			if (whole) {
+				if (F::PX == 8) {
+#pragma unroll
+					for (int h = 0; h < 2; h++) {
+						uint32_t a[F::WORDS], b[F::WORDS];
+						rgb_load_row<V>(j, 2 * cx + 8 * h, py, a);
+						rgb_load_row<V>(j, 2 * cx + 8 * h, py + 1, b);
+						ladder_chroma4<V>(a, b, 0, j.m, sh, w, au + 4 * h, av + 4 * h);
+					}
+				} else {
+					uint32_t a[F::WORDS], b[F::WORDS];
+					rgb_load_row<V>(j, 2 * cx, py, a);
+					rgb_load_row<V>(j, 2 * cx, py + 1, b);
+#pragma unroll
+					for (int h = 0; h < 2; h++) ladder_chroma4<V>(a, b, 8 * h, j.m, sh, w, au + 4 * h, av + 4 * h);
+				}
+			} else {
+#pragma unroll
+				for (int m = 0; m < 8; m++) {      // (the row's last blocks: sample by sample)
+					if (cx + m >= cw) continue;
+					int sr = 0, sg = 0, sb = 0;
+#pragma unroll
+					for (int c = 0; c < 4; c++) {
+						int cr, cg, cb;
+						ladder_sample<FMT>(j, 2 * (cx + m) + (c & 1), py + (c >> 1), cr, cg, cb);
+						sr += cr; sg += cg; sb += cb;
+					}
+					au[m] += w * (uint32_t)hmr_rgb_chroma(j.m.u, sr, sg, sb);
+					av[m] += w * (uint32_t)hmr_rgb_chroma(j.m.v, sr, sg, sb);
+				}
+			}
+		}
+		u32x4 *o = &sums4[(r * row_words + scale_word(q << 3)) >> 2];
+		o[0] = u32x4{au[0], au[1], au[2], au[3]}; o[1] = u32x4{au[4], au[5], au[6], au[7]};
+		o += (k.spans * SCALE_SPAN_WORDS) >> 2;
+		o[0] = u32x4{av[0], av[1], av[2], av[3]}; o[1] = u32x4{av[4], av[5], av[6], av[7]};
+	}
+}
+
+template <int V, int FMT>
+__device__ __forceinline__ void ladder_vertical(const RgbScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
+{
+	if (k.luma) ladder_luma<V, FMT>(j, k, sums4, row_words);
+	else ladder_chroma<V, FMT>(j, k, sums4, row_words);
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_rgb_ladder(const RgbScaleJob *jobs)
+{
+	__shared__ u32x4 sums4[SCALE_LDS_WORDS / 4];
+	__shared__ u32x4 outs4[SCALE_MAX_ROWS * SCALE_TILE_W / 8];
+	const RgbScaleJob &j = jobs[blockIdx.y];      // (read where it lies: a copy of its 192 bytes in scalar registers leaves too few for the five forms)
+	const ScaleTile k = scale_tile(j, (int)blockIdx.x, false);
+	if (k.empty) return;
+	const int row_words = k.total() * SCALE_SPAN_WORDS;
+	switch (rgb_form(j.format, j.pixel_bytes)) {
+	case RGB_PACKED3: ladder_vertical<RGB_PACKED3, HMR_GPU_RGB_PACKED8>(j, k, sums4, row_words); break;
+	case RGB_PACKED4: ladder_vertical<RGB_PACKED4, HMR_GPU_RGB_PACKED8>(j, k, sums4, row_words); break;
+	case RGB_PLANAR8: ladder_vertical<RGB_PLANAR8, HMR_GPU_RGB_PLANAR8>(j, k, sums4, row_words); break;
+	case RGB_F16: ladder_vertical<RGB_F16, HMR_GPU_RGB_PLANAR_F16>(j, k, sums4, row_words); break;
+	default: ladder_vertical<RGB_F32, HMR_GPU_RGB_PLANAR_F32>(j, k, sums4, row_words); break;
 	}
 	__syncthreads();
-
-	// eight samples per lane to the planes
-	const int stride = k.luma ? j.stride_y : j.stride_c;
-	for (int i = t; i < k.ny * (SCALE_TILE_W / 8); i += HMR_BLOCK) {
-		const int r = i / (SCALE_TILE_W / 8), q = i - r * (SCALE_TILE_W / 8);
-		const int second = k.luma ? 0 : q / (half_w / 8), xx = (k.luma ? q : q - second * (half_w / 8)) << 3;
-		if (xx >= k.nx) continue;
-		const samples_out d = (samples_out)(k.luma ? j.dst[0] : second ? j.dst[2] : j.dst[1]) + (size_t)(k.y0 + r) * stride + k.x0 + xx;
-		if (k.nx - xx >= 8) *(GLOBAL_AS u32x4 *)d = outs4[i];
-		else
-			for (int m = 0; m < k.nx - xx; m++) d[m] = outs[8 * i + m];      // (a row's tail)
-	}
+	scale_finish(k, j.ax, j.den, j.mden, (const uint32_t *)sums4, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
 }
 
 // ---- egress ----
@@ -768,12 +956,6 @@ __device__ __forceinline__ void rgb_store_row(const RgbEgressJob &j, int form, i
 	}
 }
 
-// which of the forms RGB_PACKED3 .. RGB_F32 a descriptor's format and pixel bytes are
-__host__ __device__ __forceinline__ int rgb_form(int format, int pixel_bytes)
-{
-	return format == HMR_GPU_RGB_PACKED8 ? (pixel_bytes == 3 ? RGB_PACKED3 : RGB_PACKED4) : format == HMR_GPU_RGB_PLANAR8 ? RGB_PLANAR8 : format == HMR_GPU_RGB_PLANAR_F16 ? RGB_F16 : RGB_F32;
-}
-
 __global__ __launch_bounds__(HMR_BLOCK) void k_egress_rgb(const RgbEgressJob *jobs)
 {
 	const RgbEgressJob j = jobs[blockIdx.y];
@@ -966,6 +1148,7 @@ inline int chunks_of(const IngestJob &j) { return Chunk{0, j.width, j.height}.ch
 inline int chunks_of(const EgressJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
 inline int chunks_of(const RgbIngestJob &j) { return rgb_chunks(j.height); }
 inline int chunks_of(const ScaleJob &j) { return scale_tiles(j); }
+inline int chunks_of(const RgbScaleJob &j) { return scale_tiles(j); }
 inline int chunks_of(const SsimJob &j) { return ssim_tiles(j.width, j.height); }
 inline int chunks_of(const RgbEgressJob &j) { return rgb_egress_chunks(j.height); }
 
@@ -987,8 +1170,22 @@ int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n) { return launch(k_egress, stream, h_jobs, d_jobs, n); }
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n) { return launch(k_ingest_rgb, stream, h_jobs, d_jobs, n); }
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n) { return launch(k_downscale, stream, h_jobs, d_jobs, n); }
+int hmr_rgb_scale_launch(hipStream_t stream, const RgbScaleJob *h_jobs, RgbScaleJob *d_jobs, int n) { return launch(k_rgb_ladder, stream, h_jobs, d_jobs, n); }
 int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n) { return launch(k_ssim, stream, h_jobs, d_jobs, n); }
 int hmr_egress_rgb_launch(hipStream_t stream, const RgbEgressJob *h_jobs, RgbEgressJob *d_jobs, int n) { return launch(k_egress_rgb, stream, h_jobs, d_jobs, n); }
+
+// The output rows of a job's tiles: the widest tile row of the picture, in spans (it does not depend on the tile's rows; at most SCALE_MAX_SPANS at the ratios
+// hmr_gpu_scale_check lets through), and the rows the LDS then holds.  The job's sizes and ratios are set.
+template <class Job>
+static int scale_tile_rows(Job &j, bool nv12)
+{
+	j.tile_rows = SCALE_MIN_ROWS;
+	int widest = 1;
+	for (int luma = 0; luma < 2; luma++)
+		for (int tx = 0; tx < scale_tiles_x(j.dst_w, luma != 0); tx++)
+			widest = std::max(widest, scale_tile(j, (luma ? 0 : scale_tiles_x(j.dst_w, true) * scale_tiles_y(j.dst_h, j.tile_rows, true)) + tx, nv12).total());
+	return std::min(SCALE_MAX_ROWS, std::max(SCALE_MIN_ROWS, SCALE_LDS_WORDS / (widest * SCALE_SPAN_WORDS)));
+}
 
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h)
 {
@@ -1004,14 +1201,27 @@ ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t
 	j.format = pic.format;
 	j.ax = hmr_scale_axis(src_w, dst_w); j.ay = hmr_scale_axis(src_h, dst_h);
 	j.den = j.ax.s * j.ay.s; j.mden = hmr_scale_magic(j.den);
-	// the widest tile row of this picture, in spans (it does not depend on the tile's rows; at most SCALE_MAX_SPANS at the ratios hmr_gpu_scale_check lets through), and
-	// the rows the LDS then holds
-	j.tile_rows = SCALE_MIN_ROWS;
-	int widest = 1;
-	for (int luma = 0; luma < 2; luma++)
-		for (int tx = 0; tx < scale_tiles_x(dst_w, luma != 0); tx++)
-			widest = std::max(widest, scale_tile(j, (luma ? 0 : scale_tiles_x(dst_w, true) * scale_tiles_y(dst_h, j.tile_rows, true)) + tx).total());
-	j.tile_rows = std::min(SCALE_MAX_ROWS, std::max(SCALE_MIN_ROWS, SCALE_LDS_WORDS / (widest * SCALE_SPAN_WORDS)));
+	j.tile_rows = scale_tile_rows(j, pic.format == HMR_GPU_PIC_NV12);
+	return j;
+}
+
+RgbScaleJob hmr_rgb_scale_job(const hmr_gpu_rgb_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h)
+{
+	RgbScaleJob j;
+	memset(&j, 0, sizeof j);
+	for (int c = 0; c < 3; c++) {
+		j.src[c] = (const uint8_t *)pic.plane[c];
+		j.pitch[c] = pic.pitch[c];
+		j.dst[c] = dst[c];
+		j.offset[c] = pic.offset[c];
+	}
+	j.stride_y = stride_y; j.stride_c = stride_c;
+	j.src_w = src_w; j.src_h = src_h; j.dst_w = dst_w; j.dst_h = dst_h;
+	j.format = pic.format; j.pixel_bytes = pic.pixel_bytes;
+	j.m = hmr_rgb_matrix(pic.matrix, pic.full_range);
+	j.ax = hmr_scale_axis(src_w, dst_w); j.ay = hmr_scale_axis(src_h, dst_h);
+	j.den = j.ax.s * j.ay.s; j.mden = hmr_scale_magic(j.den);
+	j.tile_rows = scale_tile_rows(j, false);
 	return j;
 }
 
@@ -1161,6 +1371,61 @@ extern "C" int hmr_gpu_scale_host(const hmr_gpu_scaled_picture *pic, int dst_w, 
 		hmr_scale_plane_host(p.plane[1], p.pitch[1], 1, ws / 2, hs / 2, dst_w / 2, dst_h / 2, u);
 		hmr_scale_plane_host(p.plane[2], p.pitch[2], 1, ws / 2, hs / 2, dst_w / 2, dst_h / 2, v);
 	}
+	return HMR_GPU_OK;
+}
+
+// ---- section 12j: the host side of the downscaling RGB ingest ----
+// rgb_yuv.h's and scale_area.h's arithmetic over host memory, the loop a caller would write from section 12j: every output sums its taps, and each tap converts the
+// pixel (luma) or the 2 x 2 block (chroma) it stands on; no converted picture in between
+extern "C" int hmr_gpu_scale_rgb_host(const hmr_gpu_scaled_rgb_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v)
+{
+	if (!pic) {
+		hmr_set_error("hmr_gpu_scale_rgb_host: the descriptor is NULL");
+		return HMR_GPU_ERR_ARG;
+	}
+	const int rc = hmr_gpu_rgb_picture_check(&pic->pic, pic->width, pic->height);
+	if (rc) return rc;
+	if (const char *why = hmr_scale_refusal(pic->width, pic->height, dst_w, dst_h, true)) {      // (any ratio: the bound of 8 is the kernel's)
+		hmr_set_error("hmr_gpu_scale_rgb_host: %d x %d -> %d x %d: %s", pic->width, pic->height, dst_w, dst_h, why);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!y || !u || !v) {
+		hmr_set_error("hmr_gpu_scale_rgb_host: needs the three output planes");
+		return HMR_GPU_ERR_ARG;
+	}
+	const hmr_gpu_rgb_picture &p = pic->pic;
+	const RgbMatrix m = hmr_rgb_matrix(p.matrix, p.full_range);
+	const bool packed = p.format == HMR_GPU_RGB_PACKED8;
+	const ScaleAxis ax = hmr_scale_axis(pic->width, dst_w), ay = hmr_scale_axis(pic->height, dst_h);      // (a chroma axis has the same reduced ratio)
+	const uint32_t den = ax.s * ay.s;
+	auto sample = [&](int c, int px, int py) {
+		return rgb_sample<const uint8_t *, const _Float16 *, const float *>((const uint8_t *)p.plane[packed ? 0 : c], p.pitch[packed ? 0 : c], p.format, p.pixel_bytes, p.offset[c], px, py);
+	};
+	for (int oy = 0; oy < dst_h; oy++)
+		for (int ox = 0; ox < dst_w; ox++) {
+			uint32_t sum = den >> 1;
+			for (uint32_t sj = (uint32_t)oy * ay.s / ay.d; sj * ay.d < ((uint32_t)oy + 1) * ay.s; sj++)
+				for (uint32_t si = (uint32_t)ox * ax.s / ax.d; si * ax.d < ((uint32_t)ox + 1) * ax.s; si++)
+					sum += hmr_scale_weight(ay, (uint32_t)oy, sj) * hmr_scale_weight(ax, (uint32_t)ox, si) *
+					       (uint32_t)hmr_rgb_luma(m, sample(0, (int)si, (int)sj), sample(1, (int)si, (int)sj), sample(2, (int)si, (int)sj));
+			y[(size_t)oy * dst_w + ox] = (uint8_t)(sum / den);
+		}
+	for (int oy = 0; oy < dst_h / 2; oy++)
+		for (int ox = 0; ox < dst_w / 2; ox++) {
+			uint32_t sum_u = den >> 1, sum_v = den >> 1;
+			for (uint32_t sj = (uint32_t)oy * ay.s / ay.d; sj * ay.d < ((uint32_t)oy + 1) * ay.s; sj++)
+				for (uint32_t si = (uint32_t)ox * ax.s / ax.d; si * ax.d < ((uint32_t)ox + 1) * ax.s; si++) {
+					int s[3] = {0, 0, 0};      // the sums of the 2 x 2 block under source chroma sample (si, sj)
+					for (int k = 0; k < 4; k++)
+						for (int c = 0; c < 3; c++) s[c] += sample(c, 2 * (int)si + (k & 1), 2 * (int)sj + (k >> 1));
+					const uint32_t w = hmr_scale_weight(ay, (uint32_t)oy, sj) * hmr_scale_weight(ax, (uint32_t)ox, si);
+					sum_u += w * (uint32_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
+					sum_v += w * (uint32_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
+				}
+			const size_t oc = (size_t)oy * (dst_w / 2) + ox;
+			u[oc] = (uint8_t)(sum_u / den);
+			v[oc] = (uint8_t)(sum_v / den);
+		}
 	return HMR_GPU_OK;
 }
 

@@ -9,6 +9,8 @@
 
     ladder = BatchEncoder([EncoderConfig(1920, 1080, ...), EncoderConfig(1280, 720, ...), EncoderConfig(960, 544, ...)])
     ladder.step([frame, ScaledFrame(frame, 1920, 1080), ScaledFrame(frame, 1920, 1080)])      # one 1080p picture, area-averaged down to each rung by ONE launch
+    ladder.step([RGBFrame(rgb)] + [ScaledRGBFrame(RGBFrame(rgb), 1920, 1080)] * 2)            # the same from an RGB frame: converted and averaged by ONE launch (and one for the top rung)
+    small.encode(ScaledRGBFrame(RGBFrame(render[:, 60:2100, 120:3720]), 3600, 2040))          # a crop of a 2160p render into a smaller encoder: no encoder of the source's size
 
     rec, ssd = enc.export(ssd=True)             # the reconstructed picture as a uint8 CUDA tensor, the sums of squared differences to `frame` as int64 [3]
     y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
@@ -17,8 +19,8 @@
     out, ssd = enc.export_rgb(dtype=torch.float16, reference=RGBFrame(rgb))     # the reconstructed picture as RGB [3, H, W], the sums of squared differences to `rgb` as int64 [3]
     r, g, b, all3 = psnr_rgb(ssd.tolist(), 1920, 1080)                          # PSNR against the RGB frame that was supplied
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h and 12i).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h, 12i and 12j).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass; scaled RGB frames: k_rgb_ladder, which does both) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
@@ -75,6 +77,11 @@ class ScaledPicture(C.Structure):
     _fields_ = [("pic", Picture), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class ScaledRgbPicture(C.Structure):
+    """hmr_gpu_scaled_rgb_picture"""
+    _fields_ = [("pic", RgbPicture), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class ScaledFrame:
     """A 4:2:0 picture that is LARGER than the encoder's, for Encoder.encode / BatchEncoder.step: area-averaged down to the encoder's size by the ingest kernel itself, in
     the integer arithmetic of include/homer_gpu.h section 12g (every sample can be reproduced from the formula there; hmr_gpu_scale_host is the same arithmetic on the host).
@@ -82,8 +89,7 @@ class ScaledFrame:
     The same frame may be given to any number of sequences of a step - a resolution ladder - and the step makes ONE scaled load call for all of them.  Downscaling only, by
     at most 8 per axis; equal sizes are legal and give what the plain frame gives.  source() returns the scaled picture of each rung, export(ssd=True) gives the sums
     against that SCALED picture, not against `frame`, and export_rgb(source=True) shows the scaled picture as RGB.
-    RGB sources are not taken here.  What works without a host round trip: encode the top rung from the RGBFrame, take its source(), and give that to the lower rungs as a
-    ScaledFrame."""
+    RGB sources are not taken here: ScaledRGBFrame takes them, and fills the slot with exactly what this class makes of the RGBFrame's source()."""
 
     def __init__(self, frame, width, height):
         if isinstance(frame, (RGBFrame, ScaledFrame)):
@@ -144,6 +150,29 @@ def rgb_picture_of(frame, width, height):
     for c in range(3):
         pic.plane[c], pic.pitch[c] = t.data_ptr() + c * t.stride(0) * t.element_size(), t.stride(1) * t.element_size()
     return pic, (t,)
+
+
+class ScaledRGBFrame:
+    """An RGB picture that is LARGER than the encoder's, for Encoder.encode / BatchEncoder.step: converted to 8-bit 4:2:0 and area-averaged down to the encoder's size by
+    ONE launch of the ingest kernel k_rgb_ladder (include/homer_gpu.h section 12j).  No new arithmetic: the slot holds section 12g's average of the picture section 12f
+    makes of the frame - what encoding the RGBFrame at its own size, taking source() and giving that to a ScaledFrame would put there, bit for bit - but no encoder of
+    the source's size is needed and the picture in between never exists (hmr_gpu_scale_rgb_host is the same arithmetic on the host).
+      frame: an RGBFrame of width x height pixels - any of its tensor forms, orders, matrices and ranges; a crop is just a view; width, height: ITS size.
+    The same frame may be given to any number of sequences of a step and the step makes ONE load call for all its ScaledRGBFrames.  Downscaling only, by at most 8 per
+    axis; equal sizes are legal and give what the RGBFrame itself gives.  source() returns the scaled 4:2:0 picture, export(ssd=True) and ssim() measure against that
+    picture, and export_rgb(source=True) shows it as RGB."""
+
+    def __init__(self, frame, width, height):
+        if not isinstance(frame, RGBFrame):
+            raise TypeError("ScaledRGBFrame: the frame has to be an RGBFrame (a 4:2:0 picture goes into a ScaledFrame)")
+        self.frame, self.width, self.height = frame, int(width), int(height)
+
+
+def scaled_rgb_picture_of(frame):
+    """The descriptor (hmr_gpu_scaled_rgb_picture) of a ScaledRGBFrame; nothing is copied.  Returns (ScaledRgbPicture, tensors): keep the tensors until the load call has
+    returned."""
+    pic, keep = rgb_picture_of(frame.frame, frame.width, frame.height)
+    return ScaledRgbPicture(pic=pic, width=frame.width, height=frame.height), keep
 
 
 _lib = None
@@ -223,6 +252,8 @@ def load_library():
         lib.hmr_gpu_enc_load_sources_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), P]
         lib.hmr_gpu_enc_load_source_scaled_device.argtypes = [P, I, C.POINTER(ScaledPicture), P]
         lib.hmr_gpu_enc_load_sources_scaled_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledPicture), P]
+        lib.hmr_gpu_enc_load_source_scaled_rgb_device.argtypes = [P, I, C.POINTER(ScaledRgbPicture), P]
+        lib.hmr_gpu_enc_load_sources_scaled_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledRgbPicture), P]
         lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
         lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
@@ -328,11 +359,12 @@ def _ssim(lib, device, encs, slot):
 
 
 def _load(lib, device, encs, cfgs, slot, frames):
-    """the frames (what picture_of takes, RGBFrame or ScaledFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
-    kinds = {"yuv": [], "rgb": [], "scaled": []}
+    """the frames (what picture_of takes, RGBFrame, ScaledFrame or ScaledRGBFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
+    kinds = {"yuv": [], "rgb": [], "scaled": [], "scaled_rgb": []}
     for k, f in enumerate(frames):
-        kinds["rgb" if isinstance(f, RGBFrame) else "scaled" if isinstance(f, ScaledFrame) else "yuv"].append(k)
-    calls = {"yuv": (Picture, "hmr_gpu_enc_load_sources_device"), "rgb": (RgbPicture, "hmr_gpu_enc_load_sources_rgb_device"), "scaled": (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device")}
+        kinds["rgb" if isinstance(f, RGBFrame) else "scaled" if isinstance(f, ScaledFrame) else "scaled_rgb" if isinstance(f, ScaledRGBFrame) else "yuv"].append(k)
+    calls = {"yuv": (Picture, "hmr_gpu_enc_load_sources_device"), "rgb": (RgbPicture, "hmr_gpu_enc_load_sources_rgb_device"), "scaled": (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device"),
+             "scaled_rgb": (ScaledRgbPicture, "hmr_gpu_enc_load_sources_scaled_rgb_device")}
     keep = []
     for kind, members in kinds.items():
         n = len(members)
@@ -343,6 +375,8 @@ def _load(lib, device, encs, cfgs, slot, frames):
         for j, k in enumerate(members):
             if kind == "scaled":
                 pics[j], t = scaled_picture_of(frames[k])
+            elif kind == "scaled_rgb":
+                pics[j], t = scaled_rgb_picture_of(frames[k])
             else:
                 pics[j], t = (rgb_picture_of if kind == "rgb" else picture_of)(frames[k], cfgs[k].width, cfgs[k].height)
             keep.append(t)
@@ -442,7 +476,7 @@ class Encoder:
         self.slot_used = None            # the slot of the last encoded frame (export)
 
     def encode(self, frame, image_type=IMAGE_AUTO):
-        """frame: what picture_of takes, an RGBFrame or a ScaledFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
+        """frame: what picture_of takes, an RGBFrame, a ScaledFrame or a ScaledRGBFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
         2 for I)."""
         lib = self.lib
         keep = _load(lib, self.device, [self.enc], [self.cfg], self.slot, [frame])
@@ -457,7 +491,7 @@ class Encoder:
 
     def export(self, picture=True, ssd=False, out=None, nv12=False):
         """The reconstructed picture of the frame the last encode() encoded (the final picture: after deblocking and SAO, what a decoder makes of the access unit) and / or
-        the three exact sums of squared differences between it and the picture that frame was encoded from (for a ScaledFrame: the SCALED picture in the slot, what source() returns).  Returns (picture, ssd); whichever was not asked for is None.
+        the three exact sums of squared differences between it and the picture that frame was encoded from (for a ScaledFrame or ScaledRGBFrame: the SCALED picture in the slot, what source() returns).  Returns (picture, ssd); whichever was not asked for is None.
         picture: `out` written in place (anything picture_of takes: views into larger tensors are fine, only the rows' bytes are written), else a new contiguous uint8
         tensor [H * 3 // 2, W] (I420), with nv12=True a (y, uv) pair [H, W], [H / 2, W / 2, 2].  ssd: an int64 CUDA tensor [3] (Y, U, V); psnr(ssd.tolist(), W, H) gives dB.
         One launch of the egress kernel, ordered on torch's current stream: what is queued there afterwards sees the results, nothing waits on the host."""
@@ -495,7 +529,7 @@ class Encoder:
         return (pics[0], sums[0]) if sums is not None else pics[0]
 
     def source(self, out=None, nv12=False):
-        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a ScaledFrame the scaled picture.  `out` and nv12 as in
+        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a ScaledFrame or a ScaledRGBFrame the scaled 4:2:0 picture.  `out` and nv12 as in
         export(); one launch of the egress kernel, ordered on torch's current stream."""
         if self.slot_used is None:
             raise RuntimeError("Encoder.source: nothing has been encoded yet")
@@ -520,7 +554,7 @@ class BatchEncoder:
     """Several sequences (configurations with wfpp_num_threads > 1: the batch schedule), one picture of each per step(): ONE ingest launch for all their pictures and ONE
     launch for all their CTU stages.  Every sequence has a context - a stream - of its own.
 
-    step(frames): frames[i] is sequence i's next picture (what picture_of takes, an RGBFrame or a ScaledFrame; a step that has several kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
+    step(frames): frames[i] is sequence i's next picture (what picture_of takes, an RGBFrame, a ScaledFrame or a ScaledRGBFrame; a step that has several kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
     Not pipelined: entry i is the access unit of frames[i] (b"" for None).
     Pipelined (the default): access units are delivered ONE STEP LATE, as by hmr_gpu_enc_encode_batch_pipelined - entry i is the access unit of the picture sequence i was
     given in the previous step (b"" if it was given none), whose download and entropy coding ran beside this step's launch; flush() returns those of the last step.  When

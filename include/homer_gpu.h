@@ -848,8 +848,7 @@ int hmr_gpu_enc_export_sources_device(hmr_gpu_enc **encs, int n, const int *slot
  *     hmr_gpu_scale_host: the same arithmetic in a plain loop over HOST memory - the descriptor's planes are host pointers here - into tightly packed I420 planes
  *     (y: dst_w x dst_h; u, v: dst_w / 2 x dst_h / 2).  No device, no context.  A utility in the spirit of hmr_gpu_rgb_convert_host; it is not a fallback for encoding.
  *     It refuses what hmr_gpu_picture_check and hmr_gpu_scale_check refuse, except that it takes any ratio: the bound of 8 is the kernel's, not the arithmetic's.
- *     RGB sources are out of scope here; the composition that works without a host round trip: load the top rung with 12f, export its slot
- *     (hmr_gpu_enc_export_sources_device), and give that picture to the lower rungs through this call.
+ *     RGB sources: section 12j, which fills a slot with exactly this section's average of the picture 12f makes, in one launch and without that picture in memory.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct hmr_gpu_scaled_picture {
 	hmr_gpu_picture pic;           /* the SOURCE picture, as in 12d */
@@ -963,6 +962,44 @@ int hmr_gpu_enc_export_picture_rgb_device(hmr_gpu_enc *enc, int which, const hmr
 int hmr_gpu_rgb_from_yuv_host(const uint8_t *y, const uint8_t *u, const uint8_t *v, int width, int height, const hmr_gpu_rgb_picture *out);
 int hmr_gpu_rgb_ssd_host(const hmr_gpu_rgb_picture *a, const hmr_gpu_rgb_picture *b, int width, int height, uint64_t ssd[3]);
 int hmr_gpu_psnr_rgb(const uint64_t ssd[3], int width, int height, double psnr[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * 12j. A resolution ladder from RGB pictures in device memory: colour conversion and downscaling inside the ingest (no counterpart in the reference)
+ *     A renderer or a tensor library holds a float [3, H, W] or packed RGBA frame that is wanted at several smaller sizes - or at one smaller size only, or as a crop.
+ *     hmr_gpu_enc_load_sources_scaled_rgb_device fills picture slots of n encoders (1 .. 512) from RGB pictures that are LARGER than (or as large as) the encoders'
+ *     pictures with ONE launch of a kernel (k_rgb_ladder, picture_io.hip).  No new formula: the slot is the composition of two sections above, bit for bit,
+ *       out = 12g's area average (source size -> encoder size, every plane on its own, one rounding) of the 8-bit 4:2:0 picture that 12f's conversion makes of the RGB
+ *             source at the source's size
+ *     so that for every entry  slot == hmr_gpu_scale_host(hmr_gpu_rgb_convert_host(rgb)) : what loading a source-sized encoder with 12f, exporting its slot and loading
+ *     that picture with 12g gives, and a ladder whose top rung is encoded from the RGB picture itself (12f) stays consistent with its lower rungs.  The 8-bit picture
+ *     in between never exists in memory: 12f's luma is a function of one pixel and its chroma of one 2 x 2 block, so the kernel converts each source sample in
+ *     registers and accumulates 12g's weighted sums directly.  Luma and chroma are produced by different workgroups, each of which reads the RGB source: it is read
+ *     twice per entry.
+ *     Every output is within 1.01 of the real-valued area average of the real-valued BT formula: 0.51 from 12f for every converted sample, which an average with
+ *     weights that sum to 1 cannot enlarge, plus 0.5 from 12g's single rounding.
+ *     Formats, channel orders, matrices, ranges, sizes and ratios may be mixed within a call, and the same source may appear in any number of entries.  An entry whose
+ *     source has the encoder's size is legal and gives exactly what hmr_gpu_enc_load_sources_rgb_device gives.  The source is any of 12f's forms at any base address
+ *     and pitch (float planes aligned to their element), so a crop is just a view.
+ *     It carries the contract of 12d word for word: the launch runs on the first encoder's stream behind what producer_stream holds now, producer_stream and the
+ *     other encoders' streams go on behind it, the host waits for nothing (but for a slot that has to be allocated first); only the bytes of the source's rows are
+ *     read, nothing outside width x height of the slot is written; a slot filled this way is indistinguishable, to every encode call, from one filled by
+ *     hmr_gpu_enc_load_sources_device with the host-made I420 picture.  hmr_gpu_enc_export_sources_device (12f) returns what the slot holds.
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is queued, every encoder left working: what 12d refuses; what
+ *     hmr_gpu_rgb_picture_check refuses for the SOURCE's size (hmr_gpu_scaled_rgb_picture.width, .height); what hmr_gpu_scale_check refuses for (source size ->
+ *     encoder size); a plane that hipPointerGetAttributes does not report as device memory of the encoders' device.
+ *     hmr_gpu_scale_rgb_host: the same arithmetic in a plain loop over HOST memory - the descriptor's planes are host pointers here - into tightly packed I420 planes
+ *     (y: dst_w x dst_h; u, v: dst_w / 2 x dst_h / 2): every output sums its taps and converts the pixel or the 2 x 2 block under each tap, no picture in between.  No
+ *     device, no context.  It refuses what hmr_gpu_rgb_picture_check and hmr_gpu_scale_check refuse and NULL arguments, except that it takes any ratio, as
+ *     hmr_gpu_scale_host does.  A utility; it is not a fallback for encoding.
+ *     Out of scope: averaging in RGB before converting (a different, new arithmetic), upscaling, one read of a source shared by several entries, other chroma sitings.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct hmr_gpu_scaled_rgb_picture {
+	hmr_gpu_rgb_picture pic;       /* the SOURCE picture, as in 12f */
+	int32_t width, height;         /* the SOURCE's size */
+} hmr_gpu_scaled_rgb_picture;      /* 88 bytes */
+int hmr_gpu_enc_load_sources_scaled_rgb_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_scaled_rgb_picture *pics, void *producer_stream);
+int hmr_gpu_enc_load_source_scaled_rgb_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_rgb_picture *pic, void *producer_stream);
+int hmr_gpu_scale_rgb_host(const hmr_gpu_scaled_rgb_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v);
 
 /* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
