@@ -427,45 +427,35 @@ HENC_HD void sync_reference_buffs(const G g, Enc &__restrict__ e, int ni, int sr
 	g.sync();
 	PRIM_END(PP_SYNC);
 }
-// the same samples into the windows first_dst .. last_dst: read once (the windows live in HBM: every copy is a trip there and back), written to each
+// the same samples of all three planes after a CU (sub)tree is final: luma into the windows first_dst .. last_dst, both chroma components into chroma_dst.  The windows
+// live in HBM, every copy is a trip there and back: the samples of all three planes are read before any is written, and the stores are waited for once
 template <class G>
-HENC_HD void sync_reference_buffs_range(const G g, Enc &__restrict__ e, int ni, int src_wnd, int first_dst, int last_dst)
+HENC_HD void sync_reference_buffs_planes(const G g, Enc &__restrict__ e, int ni, int src_wnd, int first_dst, int last_dst, int chroma_dst)
 {
 	HENC_ENC_IN_LDS(e);
 	PRIM_T0();
 	const Geo &q = e.geo[ni];
-	const int16_t *s = dec_ptr(*e.w, src_wnd, COMP_Y) + q.y * DEC_STRIDE_Y + q.x;
-	const int n = q.size, base = q.y * DEC_STRIDE_Y + q.x;
-	for (int i0 = g.tid; i0 < 2 * n - 1; i0 += 2 * g.n) {      // (2 n - 1 <= 127: two samples per lane of a wavefront)
+	const int n = q.size, base = q.y * DEC_STRIDE_Y + q.x, nc = q.size_chroma, cbase = q.yc * DEC_STRIDE_C + q.xc;
+	const int16_t *s = dec_ptr(*e.w, src_wnd, COMP_Y) + base;
+	const int16_t *su = dec_ptr(*e.w, src_wnd, COMP_U) + cbase, *sv = dec_ptr(*e.w, src_wnd, COMP_V) + cbase;
+	int16_t *du = dec_ptr(*e.w, chroma_dst, COMP_U) + cbase, *dv = dec_ptr(*e.w, chroma_dst, COMP_V) + cbase;
+	for (int i0 = g.tid; i0 < 2 * n - 1; i0 += 2 * g.n) {      // (2 n - 1 <= 127: two luma samples per lane of a wavefront; 2 nc - 1 <= 63: one chroma sample of each plane)
 		const int i1 = i0 + g.n;
 		const int off0 = i0 < n ? (n - 1) * DEC_STRIDE_Y + i0 : (i0 - n) * DEC_STRIDE_Y + n - 1;
 		const int off1 = i1 < n ? (n - 1) * DEC_STRIDE_Y + i1 : (i1 - n) * DEC_STRIDE_Y + n - 1;
-		const bool two = i1 < 2 * n - 1;
+		const int offc0 = i0 < nc ? (nc - 1) * DEC_STRIDE_C + i0 : (i0 - nc) * DEC_STRIDE_C + nc - 1;
+		const int offc1 = i1 < nc ? (nc - 1) * DEC_STRIDE_C + i1 : (i1 - nc) * DEC_STRIDE_C + nc - 1;
+		const bool two = i1 < 2 * n - 1, c0 = i0 < 2 * nc - 1, c1 = G::n < 64 && i1 < 2 * nc - 1;      // (a wavefront's second index is past the chroma samples)
 		const int16_t v0 = s[off0], v1 = two ? s[off1] : (int16_t)0;
+		const int16_t a0 = c0 ? su[offc0] : (int16_t)0, b0 = c0 ? sv[offc0] : (int16_t)0;
+		const int16_t a1 = c1 ? su[offc1] : (int16_t)0, b1 = c1 ? sv[offc1] : (int16_t)0;
 		for (int wnd = first_dst; wnd <= last_dst; wnd++) {
 			int16_t *d = dec_ptr(*e.w, wnd, COMP_Y) + base;
 			d[off0] = v0;
 			if (two) d[off1] = v1;
 		}
-	}
-	g.sync();
-	PRIM_END(PP_SYNC);
-}
-template <class G>
-HENC_HD void sync_reference_buffs_chroma(const G g, Enc &__restrict__ e, int ni, int src_wnd, int dst_wnd)
-{
-	HENC_ENC_IN_LDS(e);
-	PRIM_T0();
-	const Geo &q = e.geo[ni];
-	const int n = q.size_chroma;
-	// (both components' samples are read before either is written: one trip to the windows, not two)
-	const int16_t *su = dec_ptr(*e.w, src_wnd, COMP_U) + q.yc * DEC_STRIDE_C + q.xc, *sv = dec_ptr(*e.w, src_wnd, COMP_V) + q.yc * DEC_STRIDE_C + q.xc;
-	int16_t *du = dec_ptr(*e.w, dst_wnd, COMP_U) + q.yc * DEC_STRIDE_C + q.xc, *dv = dec_ptr(*e.w, dst_wnd, COMP_V) + q.yc * DEC_STRIDE_C + q.xc;
-	for (int i = g.tid; i < 2 * n - 1; i += g.n) {
-		const int off = i < n ? (n - 1) * DEC_STRIDE_C + i : (i - n) * DEC_STRIDE_C + n - 1;
-		const int16_t a = su[off], b = sv[off];
-		du[off] = a;
-		dv[off] = b;
+		if (c0) { du[offc0] = a0; dv[offc0] = b0; }
+		if (c1) { du[offc1] = a1; dv[offc1] = b1; }
 	}
 	g.sync();
 	PRIM_END(PP_SYNC);

@@ -44,9 +44,34 @@ HENC_HD void info_buffs_copy(const G g, Enc &__restrict__ e, int depth, int abs_
 	PRIM_END(PP_INFO);
 }
 
-// SET_INTER_INFO_BUFFS :3309
+// the CTU's arrays into the worker's buffers of the depths first_depth .. last_depth: read once (one trip to the record), written to each
 template <class G>
-HENC_HD void set_inter_info_buffs(const G g, Enc &__restrict__ e, int ni)
+HENC_HD void info_buffs_fan_out(const G g, Enc &__restrict__ e, int first_depth, int last_depth, int abs_idx, int num)
+{
+	HENC_ENC_IN_LDS(e);
+	PRIM_T0();
+	Work &w = *e.w;
+	CtuPublic &c = *e.ctu;
+	for (int i = g.tid; i < num; i += g.n) {
+		const int k = abs_idx + i;
+		const uint8_t v0 = c.cbf[0][k], v1 = c.cbf[1][k], v2 = c.cbf[2][k], v3 = c.tr_idx[k], v4 = c.intra_mode[0][k], v5 = c.intra_mode[1][k];
+		for (int depth = first_depth; depth <= last_depth; depth++) {
+			w.cbf_buffs[0][depth][k] = v0;
+			w.cbf_buffs[1][depth][k] = v1;
+			w.cbf_buffs[2][depth][k] = v2;
+			w.tr_idx_buffs[depth][k] = v3;
+			w.intra_mode_buffs[0][depth][k] = v4;
+			w.intra_mode_buffs[1][depth][k] = v5;
+		}
+	}
+	g.sync();
+	PRIM_END(PP_INFO);
+}
+
+// SET_INTER_INFO_BUFFS :3309.  pred_depth >= 0: the CU's qp, prediction depth and partition type with it (what consolidate_prediction_info writes next to it for a
+// parent that wins) - all of it stores into the record, issued together and waited for once.
+template <class G>
+HENC_HD void set_inter_info_buffs(const G g, Enc &__restrict__ e, int ni, int pred_depth = -1, int part_size_type = 0)
 {
 	HENC_ENC_IN_LDS(e);
 	PRIM_T0();
@@ -75,18 +100,28 @@ HENC_HD void set_inter_info_buffs(const G g, Enc &__restrict__ e, int ni)
 		}
 	}
 	for (int i = g.tid; i < n; i += g.n) c.pred_mode[a + i] = (uint8_t)nd.prediction_mode;
+	if (pred_depth >= 0) {
+		const uint8_t qp = (uint8_t)nd.qp;
+		for (int i = g.tid; i < n; i += g.n) {
+			c.qp[a + i] = qp;
+			c.pred_depth[a + i] = (uint8_t)pred_depth;
+			c.part_size_type[a + i] = (uint8_t)part_size_type;
+		}
+	}
 	g.sync();
 	PRIM_END(PP_INFO);
 }
 
 // get_back_consolidated_info :3456 / put_consolidated_info :3472
+// (luma_only: the caller knows that the depth's chroma windows still hold what window 0 holds - the chroma planes are not copied, no helper is asked)
 template <class G>
-HENC_HD void get_back_consolidated_info(const G g, Enc &__restrict__ e, int ni, int depth)
-{	ni = uni(ni); depth = uni(depth);
+HENC_HD void get_back_consolidated_info(const G g, Enc &__restrict__ e, int ni, int depth, int luma_only = 0)
+{	ni = uni(ni); depth = uni(depth); luma_only = uni(luma_only);
 
 	HENC_ENC_IN_LDS(e);
 	info_buffs_copy(g, e, depth, e.geo[ni].abs_index, e.geo[ni].num_part, 0);
-	sync_motion_buffers(g, e, ni, 0, depth + 1, 0, depth + 1);
+	if (luma_only) sync_motion_buffers_luma(g, e, ni, 0, depth + 1, 0, depth + 1);
+	else sync_motion_buffers(g, e, ni, 0, depth + 1, 0, depth + 1);
 }
 template <class G>
 HENC_HD void put_consolidated_info(const G g, Enc &__restrict__ e, int ni, int depth)
@@ -99,9 +134,12 @@ HENC_HD void put_consolidated_info(const G g, Enc &__restrict__ e, int ni, int d
 
 // consolidate_prediction_info :3372.  Returns true when the children were taken (the caller's running cost of the parent's depth then changes by
 // children_cost - parent_cost, as the reference does inside).
+// parent_is_consolidated: the caller knows that window 0 and the record's side-info arrays already hold, for this CU, byte for byte what its depth's windows and
+// buffers hold (get_back_consolidated_info has just copied the one into the other and nothing has written either since): where the parent wins, the copy of
+// the three planes into window 0 and of the six arrays into the record would move these bytes onto themselves and is left out.
 template <class G>
-HENC_HD bool consolidate_prediction_info(const G g, Enc &__restrict__ e, int pi, uint32_t parent_cost, uint32_t children_cost, int is_max_depth)
-{	pi = uni(pi); parent_cost = uni(parent_cost); children_cost = uni(children_cost); is_max_depth = uni(is_max_depth);
+HENC_HD bool consolidate_prediction_info(const G g, Enc &__restrict__ e, int pi, uint32_t parent_cost, uint32_t children_cost, int is_max_depth, int parent_is_consolidated = 0)
+{	pi = uni(pi); parent_cost = uni(parent_cost); children_cost = uni(children_cost); is_max_depth = uni(is_max_depth); parent_is_consolidated = uni(parent_is_consolidated);
 
 	HENC_ENC_IN_LDS(e);
 	const Geo &pq = e.geo[pi];
@@ -136,16 +174,11 @@ HENC_HD bool consolidate_prediction_info(const G g, Enc &__restrict__ e, int pi,
 	} else {
 		const int part2 = pq.depth < CFG_MAX_PRED_DEPTH ? PART_2Nx2N : PART_NxN;
 		const int parent_depth = pq.depth;
-		sync_motion_buffers(g, e, pi, parent_depth + 1, 0, parent_depth + 1, 0);
-		info_buffs_copy(g, e, parent_depth, abs_index, num, 1);
-		set_inter_info_buffs(g, e, pi);
-		const uint8_t qp = (uint8_t)pn.qp;
-		for (int i = g.tid; i < num; i += g.n) {
-			c.qp[abs_index + i] = qp;
-			c.pred_depth[abs_index + i] = (uint8_t)(pq.depth - (part2 == PART_NxN));
-			c.part_size_type[abs_index + i] = (uint8_t)part2;
+		if (!parent_is_consolidated) {
+			sync_motion_buffers(g, e, pi, parent_depth + 1, 0, parent_depth + 1, 0);
+			info_buffs_copy(g, e, parent_depth, abs_index, num, 1);
 		}
-		g.sync();
+		set_inter_info_buffs(g, e, pi, pq.depth - (part2 == PART_NxN), part2);
 	}
 	return false;
 }
@@ -160,11 +193,10 @@ HENC_HD void refresh_deeper_windows(const G g, Enc &__restrict__ e, int aux_ni, 
 	const int max_processing_depth = hmin(CFG_MAX_PRED_DEPTH + e.seq->max_intra_tr_depth - 1, NDEPTH - 1);
 	if (from_depth > max_processing_depth) return;
 	const Geo &q = e.geo[aux_ni];
-	// (the reference copies window by window, each followed by the depth's side-info copy; source and destinations are distinct buffers, so the order is free)
-	sync_reference_buffs_range(g, e, aux_ni, 0, from_depth + 1, max_processing_depth + 1);
-	if (with_info && e.seq->rd_mode != RDM_DIST_ONLY)
-		for (int aux_depth = from_depth; aux_depth <= max_processing_depth; aux_depth++) info_buffs_copy(g, e, aux_depth, q.abs_index, q.num_part, 0);
-	sync_reference_buffs_chroma(g, e, aux_ni, 0, NWND - 1);
+	// (the reference copies window by window, each followed by the depth's side-info copy; source and destinations are distinct buffers, so the order is free,
+	// and the samples of the three planes, and the record's arrays for all depths, are each read in one trip)
+	sync_reference_buffs_planes(g, e, aux_ni, 0, from_depth + 1, max_processing_depth + 1, NWND - 1);
+	if (with_info && e.seq->rd_mode != RDM_DIST_ONLY) info_buffs_fan_out(g, e, from_depth, max_processing_depth, q.abs_index, q.num_part);
 }
 
 // encode_intra, hmr_motion_intra.c:1731
@@ -218,7 +250,9 @@ HENC_WALK_FN HENC_HD uint32_t check_rd_cost_merge(const G g, Enc &__restrict__ e
 		if (slots >= 0) {
 			const uint32_t best = q.size == 8 ? quad_merge_loop<8>(g, e, ni, slots, mc, inter_modes HENC_QPROF_PASS) : quad_merge_loop<16>(g, e, ni, slots, mc, inter_modes HENC_QPROF_PASS);
 			HENC_QPROF_MARK(e, 7);      // (the node's fields)
-			if (g.tid == 0 && e.prof) e.prof[8] += 1;      // (CUs taken this way)
+#if defined(HENC_QPROF)
+			if (g.tid == 0 && e.prof) e.prof[8] += 1;      // (CUs taken this way: slot 8 is lent to this count in the experiment build only - it is PF_INTRA_CHROMA otherwise)
+#endif
 			return best;
 		}
 	}
@@ -382,6 +416,12 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 	int curr_depth = 0, parent = -1, curr = 0;
 	double dist = 0, best_cost;
 	const int root = 0;
+	// The CU for which window 0 and the record's side-info arrays are known to hold, byte for byte, what the windows and buffers of the CU's own depth hold (-1: none).
+	// get_back_consolidated_info makes it so (it copies the one into the other, all three planes or - luma_only - the one plane that differed); the evaluation of
+	// the next CU ends it, and so does everything that writes either side: an intra evaluation that wins, a motion search that wins without a put, any consolidation.
+	// Nothing between a CU's get_back and the consolidation that follows it (directly, or through the dummy NxN level below an 8 x 8 CU) writes a window, a
+	// per-depth buffer or the record, so that consolidation's copy into window 0 is left out (consolidate_prediction_info, parent_is_consolidated).
+	int consolidated_cu = -1;
 	while (curr_depth != 0 || depth_state.get(curr_depth) != 1) {
 		double cost = 0, intra_cost = 0;
 		int stop_recursion = 0, is_skipped = 0;
@@ -402,6 +442,7 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 				int merge_ref_idx = 0, merge_inter_mode = 0;
 				const int action = S.me_precision * 2 - 1;
 				nd.prediction_mode = PM_INTER;
+				consolidated_cu = -1;
 				if (curr_depth >= perf_min_depth) {
 					{ HENC_PROF_T0(); merge_dist = check_rd_cost_merge(g, e, curr_depth, position); HENC_PROF_ADD(e, PF_MERGE); }
 					merge_mv = nd.inter_mv;
@@ -463,12 +504,14 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 						       (nd.sum == 0 && dist < avg_distortion * num_part_in_cu))) {
 					if (nd.merge_flag) get_back_consolidated_info(g, e, curr, curr_depth);
 					stop_recursion = 1;
-					(void)consolidate_prediction_info(g, e, curr, nd.cost, MAX_COST, 0);
+					(void)consolidate_prediction_info(g, e, curr, nd.cost, MAX_COST, 0, nd.merge_flag);      // (after a get_back the copy would move the same bytes back)
 					refresh_deeper_windows(g, e, curr, curr_depth, 1);
 				}
 				if (perf_fast_skip && (curr_depth >= perf_min_depth && !stop_recursion && !is_skipped && (q.size < 32 || sad > 400u * num_part_in_cu))) {
 					const uint32_t inter_sum = nd.sum;
-					if (!nd.merge_flag) put_consolidated_info(g, e, curr, curr_depth);
+					const int put_here = !nd.merge_flag;
+					int chroma_untouched = 0;      // window 0 got its chroma planes from the depth's windows just now (put_here) and nothing has written those since
+					if (put_here) put_consolidated_info(g, e, curr, curr_depth);
 					e.last_slog = -1;
 					// encode_intra (:1731): luma, then chroma.  The comparison below only grows with what chroma adds - its distortion, and its levels through cost_rd - so when
 					// luma alone already loses against the inter cost for every value the intra ratio can take (it is clipped to 0 .. 0.15, and enc_sched.h re-evaluates
@@ -482,7 +525,7 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 						{ HENC_PROF_T0(); cl = encode_intra_luma(g, e, curr_depth, position, PART_2Nx2N); HENC_PROF_ADD(e, PF_INTRA_TU); } HENC_TRACE_PW(e, "iluma");
 						const double add_lb = hclip(avg_distortion - 400, 40., avg_distortion) / 1.75 * curr_depth;
 						const double lb = intra_cost_with_ratio((double)cl, .15, add_lb, cost_rd(e.f->avg_dist, nd.sum));
-						if (!rd_full(g, S) && e.f->lockstep && lb > cost + 1.) intra_dist = cl;
+						if (!rd_full(g, S) && e.f->lockstep && lb > cost + 1.) { intra_dist = cl; chroma_untouched = put_here; }      // (the luma evaluation writes luma windows and luma buffers only)
 						else {
 							uint32_t cc;
 							{ HENC_PROF_T0(); cc = encode_intra_chroma(g, e, curr_depth, position, PART_2Nx2N); HENC_PROF_ADD(e, PF_INTRA_CHROMA); } HENC_TRACE_PW(e, "ichroma");
@@ -513,14 +556,15 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 						nd.merge_flag = 0;
 						nd.skipped = 0;
 					} else {
-						get_back_consolidated_info(g, e, curr, curr_depth);
+						get_back_consolidated_info(g, e, curr, curr_depth, chroma_untouched);
+						consolidated_cu = curr;
 						nd.cost = (uint32_t)cost;
 						nd.distortion = (uint32_t)dist;
 						nd.sum = inter_sum;
 						nd.prediction_mode = PM_INTER;
 					}
 				} else if (curr_depth >= perf_min_depth && !stop_recursion) {
-					if (nd.merge_flag) get_back_consolidated_info(g, e, curr, curr_depth);
+					if (nd.merge_flag) { get_back_consolidated_info(g, e, curr, curr_depth); consolidated_cu = curr; }
 				}
 			} else {
 				// NxN level.  Inter NxN needs a parent larger than 8x8 (:4061), which the 8x8 minimum CU of the built configurations excludes.
@@ -543,7 +587,8 @@ HENC_HD uint32_t motion_inter_ctu(const G g, Enc &__restrict__ e)
 				cost = ccost;
 				depth_state.set(curr_depth, 0);
 				best_cost = node_of(e, parent).cost;
-				if (consolidate_prediction_info(g, e, parent, (uint32_t)best_cost, (uint32_t)cost, is_max_depth)) cost_sum.add(e.geo[parent].depth, (uint32_t)cost - (uint32_t)best_cost);
+				if (consolidate_prediction_info(g, e, parent, (uint32_t)best_cost, (uint32_t)cost, is_max_depth, consolidated_cu == parent)) cost_sum.add(e.geo[parent].depth, (uint32_t)cost - (uint32_t)best_cost);
+				consolidated_cu = -1;
 				cost_sum.set(curr_depth, 0);
 				curr_depth--;
 				parent = e.geo[parent].parent;
