@@ -157,6 +157,7 @@ struct hmr_gpu_enc {
 	JobRing<SsimJob> ssim;
 	JobRing<RgbEgressJob> egress_rgb;
 	JobRing<RgbScaleJob> scale_rgb;                       // (k_rgb_ladder)
+	JobRing<YuvIngestJob> ingest_yuv;                     // (k_ingest_yuv)
 	// every encoder: whether d_pic[cur] holds an encoded frame's final picture, the stream whose work wrote it (its own, or the lead's of a batch or chain launch),
 	// events for that stream and its own (an export call waits behind both)
 	bool has_picture = false;
@@ -886,6 +887,7 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	if (e->h_offs) (void)hipHostFree(e->h_offs);
 	e->ingest.release();
 	e->ingest_rgb.release();
+	e->ingest_yuv.release();
 	e->scale.release();
 	e->egress.release();
 	e->ssim.release();

@@ -1,5 +1,5 @@
 // Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
-// (include/homer_gpu.h sections 12d, 12e, 12f, 12g, 12h, 12i and 12j).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_downscale / k_rgb_ladder / k_egress / k_ssim / k_egress_rgb (picture_io.hip)
+// (include/homer_gpu.h sections 12d, 12e, 12f, 12g, 12h, 12i, 12j and 12k).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of k_ingest / k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_egress / k_ssim / k_egress_rgb (picture_io.hip)
 // on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
 //   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
 //   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
@@ -47,7 +47,7 @@ int check_planes(const char *fn, const hmr_gpu_picture *pics, int n, int device)
 }  // namespace
 
 namespace {
-// what the load calls of sections 12d, 12f, 12g and 12j refuse before they look at a picture
+// what the load calls of sections 12d, 12f, 12g, 12j and 12k refuse before they look at a picture
 int check_load(const char *fn, hmr_gpu_enc **encs, int n, const int *slots, const void *pics)
 {
 	static_assert(PICTURE_MAX_JOBS == BATCH_MAX, "a load call feeds a batch call, an export call follows one");
@@ -237,6 +237,47 @@ extern "C" int hmr_gpu_enc_load_sources_rgb_device(hmr_gpu_enc **encs, int n, co
 extern "C" int hmr_gpu_enc_load_source_rgb_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_rgb_picture *pic, void *producer_stream)
 {
 	return hmr_gpu_enc_load_sources_rgb_device(&enc, 1, &slot, pic, producer_stream);
+}
+
+// ---- section 12k: Y'CbCr pictures of 8 .. 16 bits, 4:2:0 / 4:2:2 / 4:4:4, planar, semi-planar or packed, rounded to 8-bit 4:2:0 ----
+extern "C" int hmr_gpu_enc_load_sources_yuv_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_yuv_picture *pics, void *producer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_load_sources_yuv_device";
+	int rc;
+	if ((rc = check_load(fn, encs, n, slots, pics))) return rc;
+	const int device = encs[0]->ctx->device;
+	for (int i = 0; i < n; i++)
+		if (hmr_gpu_yuv_picture_check(&pics[i], encs[i]->seq.width, encs[i]->seq.height) != HMR_GPU_OK) {
+			const std::string why = hmr_gpu_last_error();
+			return picture_refuse(fn, i, why.c_str());
+		}
+	HIP_TRY(hipSetDevice(device));
+	static const char *const names[3] = {"plane[0]", "plane[1]", "plane[2]"};
+	for (int i = 0; i < n; i++)
+		for (int c = 0; c < (pics[i].format == HMR_GPU_YUV_PLANAR ? 3 : pics[i].format == HMR_GPU_YUV_SEMIPLANAR ? 2 : 1); c++)
+			if (!on_device(pics[i].plane[c], device)) return not_device(fn, i, names[c], device);
+	if ((rc = make_slots(encs, n, slots))) return rc;
+	std::vector<YuvIngestJob> jobs(n);
+	for (int i = 0; i < n; i++) {
+		const hmr_gpu_enc *e = encs[i];
+		const hmr_gpu_yuv_picture &pic = pics[i];
+		YuvIngestJob &j = jobs[i];
+		memset(&j, 0, sizeof j);
+		for (int c = 0; c < 3; c++) {
+			j.src[c] = (const uint8_t *)pic.plane[c];
+			j.pitch[c] = pic.pitch[c];
+			j.dst[c] = e->src[slots[i]].p[c];
+		}
+		j.stride_y = e->seq.src_stride_y; j.stride_c = e->seq.src_stride_c;
+		j.width = e->seq.width; j.height = e->seq.height;
+		j.f = hmr_yuv_form(pic.format, pic.chroma, pic.bits, pic.msb_aligned, pic.offset);
+	}
+	return run_load(encs[0]->ingest_yuv, hmr_ingest_yuv_launch, encs, n, jobs.data(), producer_stream);
+}
+
+extern "C" int hmr_gpu_enc_load_source_yuv_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_yuv_picture *pic, void *producer_stream)
+{
+	return hmr_gpu_enc_load_sources_yuv_device(&enc, 1, &slot, pic, producer_stream);
 }
 
 // ---- section 12g: larger pictures in, area-averaged down to the encoders' sizes ----

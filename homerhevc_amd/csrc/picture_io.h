@@ -1,6 +1,6 @@
 // Picture conversion on the device (picture_io.hip): 8-bit 4:2:0 pictures in device memory <-> the int16 planes of the frame encoder, a batch of pictures per launch.
 // Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture); RGB pictures (8-bit packed or planar, binary16, binary32) -> the same planes, colour
-// converted in the same pass (rgb_yuv.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h); RGB pictures of a larger size -> the same planes, converted and area-averaged in the same pass.  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
+// converted in the same pass (rgb_yuv.h); Y'CbCr pictures of 8 .. 16 bits in 4:2:0, 4:2:2 or 4:4:4, planar, semi-planar or packed -> the same planes, rounded to 8-bit 4:2:0 in the same pass (yuv_depth.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h); RGB pictures of a larger size -> the same planes, converted and area-averaged in the same pass.  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
 // squared differences against the int16 source planes of a picture slot; the final pictures or the slots' pictures -> RGB pictures in any of the ingest's forms, colour
 // converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  A launch reads its pictures from a job table; JobRing holds the tables of one encoder and
 // run_jobs queues one launch, ordered against the caller's stream by events (k_encode_picture_io.inc and the host-memory entries of k_encode_object.inc use it).
@@ -10,6 +10,7 @@
 #include <vector>
 #include "common.h"
 #include "rgb_yuv.h"
+#include "yuv_depth.h"
 #include "yuv_rgb.h"
 #include "scale_area.h"
 #include "ssim_window.h"
@@ -51,6 +52,17 @@ struct RgbIngestJob {
 	int32_t reserved[3];
 };
 static_assert(sizeof(RgbIngestJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
+
+// one picture of a deep / 4:2:2 / 4:4:4 ingest launch (k_ingest_yuv): the caller's Y'CbCr picture into the int16 planes, rounded to 8-bit 4:2:0 by yuv_depth.h's arithmetic
+struct YuvIngestJob {
+	const uint8_t *src[3];       // PLANAR: Y, U, V; SEMIPLANAR: Y, interleaved pairs, unused; PACKED422: src[0] alone
+	int64_t pitch[3];            // bytes from row to row
+	int16_t *dst[3];             // the planes at sample (0, 0); 16-byte aligned
+	int32_t stride_y, stride_c;  // elements, multiples of 8
+	int32_t width, height;
+	YuvForm f;                   // layout, taps, container, shifts and offsets: a launch mixes forms
+};
+static_assert(sizeof(YuvIngestJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
 // one picture of an RGB egress launch (k_egress_rgb): int16 planes (a final picture, a picture slot) into the caller's RGB picture by yuv_rgb.h's arithmetic, and / or
 // the sums of squared differences between the 8-bit RGB values and the caller's reference RGB picture
@@ -133,6 +145,14 @@ static inline double hmr_ingest_rgb_bytes(int width, int height, int format, int
 	return (read + 4.0) * wh;
 }
 
+// Algorithmic bytes of one width x height picture through k_ingest_yuv (tools/yuv_ingest_bench.py restates it): every sample of the source is read once - sb
+// bytes each, W H luma and 2 Wc Hc chroma samples (chroma: HMR_GPU_CHROMA_420 / _422 / _444 = 0 / 1 / 2) - and the int16 Y, U, V planes are written: 3 W H.
+static inline double hmr_ingest_yuv_bytes(int width, int height, int chroma, int bits)
+{
+	const double wh = (double)width * height, sb = bits > 8 ? 2.0 : 1.0;
+	return sb * wh * (chroma == 0 ? 1.5 : chroma == 1 ? 2.0 : 3.0) + 3.0 * wh;
+}
+
 // Algorithmic bytes of one width x height picture through k_egress (tools/egress_bench.py restates it): the final picture is read, the slot's picture is read
 // when sums are asked for, the 8-bit picture is written when one is asked for.
 static inline double hmr_egress_bytes(int width, int height, int picture, int sums)
@@ -155,10 +175,11 @@ static inline double hmr_egress_rgb_bytes(int width, int height, int format, int
 }
 
 // The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of k_ingest /
-// k_ingest_rgb / k_downscale / k_rgb_ladder / k_egress / k_egress_rgb / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
+// k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_egress / k_egress_rgb / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n);
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n);
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n);
+int hmr_ingest_yuv_launch(hipStream_t stream, const YuvIngestJob *h_jobs, YuvIngestJob *d_jobs, int n);
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n);
 int hmr_rgb_scale_launch(hipStream_t stream, const RgbScaleJob *h_jobs, RgbScaleJob *d_jobs, int n);
 int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n);

@@ -351,6 +351,190 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ingest_rgb(const RgbIngestJob *jo
 	}
 }
 
+// ---- deep / 4:2:2 / 4:4:4 ingest (section 12k) ----
+// k_ingest_yuv: Y'CbCr pictures of 8 .. 16 bits - 4:2:0, 4:2:2 or 4:4:4; planar, semi-planar in either order, or packed 4:2:2 in any of its four orders - into the int16
+// planes of a slot, rounded to 8-bit 4:2:0 by the integer arithmetic of yuv_depth.h in the same pass.  sb (W H + 2 Wc Hc) bytes read, 3 W H written per picture
+// (hmr_ingest_yuv_bytes in picture_io.h).  The mapping is k_ingest_rgb's: blockIdx.y = picture, blockIdx.x = a chunk of CHUNK_ROWS luma rows; a lane takes a span of 16
+// pixels of TWO adjacent luma rows and every chroma sample that lies over them, so the 1, 2 or 4 taps of a chroma output never leave the lane and a packed picture's
+// bytes are read once for luma and chroma.  Per lane: the luma rows' bytes by 16-byte loads at whatever address the pitch gives (one a row for 8-bit planes, two for
+// 16-bit planes or 8-bit packed, four for 16-bit packed); the chroma rows' (one row for 4:2:0, two otherwise; 8 columns, 16 for 4:4:4; ONE 8-byte load where a row's
+// part is 8 bytes: 8-bit planar 4:2:0 / 4:2:2); four 16-byte stores of int16 luma and one each of eight U and eight V samples.  The kernel is specialised on the layout,
+// the container's width and the tap count (14 instantiations, picked per job: a launch mixes forms); the shifts, the clamp and the offsets inside a pair or a group are
+// the job's and uniform over a workgroup.  Samples are picked from the loaded dwords at indices fixed at compile time (v_bfe_u32 / v_perm_b32; a 16-bit group of four by a
+// 64-bit shift, v_lshrrev_b64).  A row's tail of fewer than 16 pixels goes sample by sample, a lane per 2 x 2 block, through yuv_depth.h's own sample functions - the
+// ones the host twin runs.  No LDS, no atomics.  No lane reads a byte outside [plane + y * pitch, plane + y * pitch + row bytes): whole spans lie inside the width.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x2 u32x2_unaligned __attribute__((aligned(1)));
+__device__ __forceinline__ u32x2 load8(bytes_in s) { return *(GLOBAL_AS const u32x2_unaligned *)s; }
+
+// BYTES (8, or a multiple of 16) bytes at s as dwords
+template <int BYTES>
+__device__ __forceinline__ void yuv_load(bytes_in s, uint32_t *w)
+{
+	if (BYTES == 8) {
+		const u32x2 v = load8(s);
+		w[0] = v.x; w[1] = v.y;
+		return;
+	}
+#pragma unroll
+	for (int k = 0; k < BYTES / 16; k++) {
+		const u32x4 v = load16(s + 16 * k);
+		w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+	}
+}
+
+// The container `shift` bits into group g (a compile-time index) of a row's dwords; a group is G containers of SB bytes: a sample of a plane (G = 1), a pair of a
+// semi-planar chroma plane or of a packed row's luma (G = 2), two pixels of a packed row (G = 4).
+template <int SB, int G>
+__device__ __forceinline__ uint32_t yuv_pick(const uint32_t *w, int g, int shift)
+{
+	constexpr int GROUP_BITS = 8 * SB * G;
+	constexpr uint32_t mask = SB == 1 ? 255u : 65535u;
+	if (GROUP_BITS == 64) return (uint32_t)((((uint64_t)w[2 * g + 1] << 32) | w[2 * g]) >> shift) & mask;
+	if (GROUP_BITS == 32) return (w[g] >> shift) & mask;
+	if (GROUP_BITS == 16) return (w[g >> 1] >> (16 * (g & 1) + shift)) & mask;
+	return (w[g >> 2] >> (8 * (g & 3))) & mask;
+}
+
+enum { YUV_PLANAR = HMR_YUV_PLANAR, YUV_SEMI = HMR_YUV_SEMIPLANAR, YUV_PACKED = HMR_YUV_PACKED422 };
+// what a lane reads of a row: L the layout, SB the container's bytes, K log2 of the chroma taps
+template <int L, int SB, int K> struct YuvSpan {
+	static constexpr int LUMA_BYTES = (L == YUV_PACKED ? 32 : 16) * SB;             // 16 pixels of a luma (or packed) row
+	static constexpr int COLS = K == 2 ? 16 : 8;                                     // chroma columns under 16 pixels
+	static constexpr int ROWS = K == 0 ? 1 : 2;                                      // chroma rows under two luma rows
+	static constexpr int CHROMA_BYTES = COLS * SB * (L == YUV_SEMI ? 2 : 1);         // of one row of one chroma plane (planar) or of the pairs' plane
+	static constexpr int TAPS = K == 2 ? 2 : 1;                                      // per row
+};
+
+// 16 pixels at (x, y) of rows y and y + 1 (x a multiple of 16, y even): 32 luma samples, 8 U and 8 V samples
+template <int L, int SB, int K>
+__device__ __forceinline__ void yuv_span(const YuvIngestJob &j, int x, int y)
+{
+	typedef YuvSpan<L, SB, K> F;
+	const YuvForm &f = j.f;
+	const int bits0 = 8 * SB * f.offset[0], bits1 = 8 * SB * f.offset[1], bits2 = 8 * SB * f.offset[2];
+	uint32_t la[2][F::LUMA_BYTES / 4];
+#pragma unroll
+	for (int r = 0; r < 2; r++) yuv_load<F::LUMA_BYTES>((bytes_in)j.src[0] + (int64_t)(y + r) * j.pitch[0] + (int64_t)x * (L == YUV_PACKED ? 2 : 1) * SB, la[r]);
+#pragma unroll
+	for (int r = 0; r < 2; r++) {
+		uint32_t o[8];
+#pragma unroll
+		for (int q = 0; q < 8; q++) {
+			if (SB == 1 && L != YUV_PACKED) {      // 8 bits: the sample itself
+				o[q] = (q & 1) ? high_bytes(la[r][q >> 1]) : low_bytes(la[r][q >> 1]);
+				continue;
+			}
+			const uint32_t a = L == YUV_PACKED ? yuv_pick<SB, 2>(la[r], 2 * q, bits0) : yuv_pick<SB, 1>(la[r], 2 * q, 0);
+			const uint32_t b = L == YUV_PACKED ? yuv_pick<SB, 2>(la[r], 2 * q + 1, bits0) : yuv_pick<SB, 1>(la[r], 2 * q + 1, 0);
+			o[q] = SB == 1 ? a | b << 16 : hmr_yuv_round(hmr_yuv_value(f, a), f.s) | hmr_yuv_round(hmr_yuv_value(f, b), f.s) << 16;
+		}
+		GLOBAL_AS u32x4 *d = (GLOBAL_AS u32x4 *)((samples_out)j.dst[0] + (size_t)(y + r) * j.stride_y + x);
+		d[0] = u32x4{o[0], o[1], o[2], o[3]};
+		d[1] = u32x4{o[4], o[5], o[6], o[7]};
+	}
+	uint32_t su[8], sv[8];
+#pragma unroll
+	for (int c = 0; c < 8; c++) su[c] = sv[c] = 0;
+	if (L == YUV_PACKED) {      // the rows are here already: group c holds chroma column c
+#pragma unroll
+		for (int r = 0; r < 2; r++)
+#pragma unroll
+			for (int c = 0; c < 8; c++) {
+				const uint32_t u = yuv_pick<SB, 4>(la[r], c, bits1), v = yuv_pick<SB, 4>(la[r], c, bits2);
+				su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
+				sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
+			}
+	} else {
+		const int row0 = K == 0 ? y >> 1 : y, col0 = K == 2 ? x : x >> 1;
+#pragma unroll
+		for (int r = 0; r < F::ROWS; r++) {
+			uint32_t cu[F::CHROMA_BYTES / 4], cv[F::CHROMA_BYTES / 4];
+			yuv_load<F::CHROMA_BYTES>((bytes_in)j.src[1] + (int64_t)(row0 + r) * j.pitch[1] + (int64_t)col0 * SB * (L == YUV_SEMI ? 2 : 1), cu);
+			if (L == YUV_PLANAR) yuv_load<F::CHROMA_BYTES>((bytes_in)j.src[2] + (int64_t)(row0 + r) * j.pitch[2] + (int64_t)col0 * SB, cv);
+#pragma unroll
+			for (int c = 0; c < 8; c++)
+#pragma unroll
+				for (int t = 0; t < F::TAPS; t++) {
+					const int i = c * F::TAPS + t;
+					const uint32_t u = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, i, bits1) : yuv_pick<SB, 1>(cu, i, 0);
+					const uint32_t v = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, i, bits2) : yuv_pick<SB, 1>(cv, i, 0);
+					su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
+					sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
+				}
+		}
+	}
+	const int t = f.s + K;      // (8 bits: s = 0, maxv = 255, rs = 0 - hmr_yuv_value is the identity and was left out above)
+	uint32_t ou[4], ov[4];
+#pragma unroll
+	for (int q = 0; q < 4; q++) {
+		ou[q] = hmr_yuv_round(su[2 * q], t) | hmr_yuv_round(su[2 * q + 1], t) << 16;
+		ov[q] = hmr_yuv_round(sv[2 * q], t) | hmr_yuv_round(sv[2 * q + 1], t) << 16;
+	}
+	const size_t oc = (size_t)(y >> 1) * j.stride_c + (x >> 1);
+	*(GLOBAL_AS u32x4 *)((samples_out)j.dst[1] + oc) = u32x4{ou[0], ou[1], ou[2], ou[3]};
+	*(GLOBAL_AS u32x4 *)((samples_out)j.dst[2] + oc) = u32x4{ov[0], ov[1], ov[2], ov[3]};
+}
+
+// the 2 x 2 block at (bx, y), sample by sample (a row's tail): yuv_depth.h's functions on global pointers
+__device__ __forceinline__ void yuv_block(const YuvIngestJob &j, int bx, int y)
+{
+	const samples_out dy = (samples_out)j.dst[0];
+#pragma unroll
+	for (int k = 0; k < 4; k++) {
+		const int px = bx + (k & 1), py = y + (k >> 1);
+		dy[(size_t)py * j.stride_y + px] = (int16_t)hmr_yuv_luma<bytes_in>(j.src, j.pitch, j.f, px, py);
+	}
+	const size_t oc = (size_t)(y >> 1) * j.stride_c + (bx >> 1);
+	((samples_out)j.dst[1])[oc] = (int16_t)hmr_yuv_chroma<bytes_in>(j.src, j.pitch, j.f, 1, bx >> 1, y >> 1);
+	((samples_out)j.dst[2])[oc] = (int16_t)hmr_yuv_chroma<bytes_in>(j.src, j.pitch, j.f, 2, bx >> 1, y >> 1);
+}
+
+// the rows y0 .. of a picture in layout L with containers of SB bytes and 2^K chroma taps: whole spans, then the row's tail of fewer than 16 pixels
+template <int L, int SB, int K>
+__device__ __forceinline__ void yuv_chunk(const YuvIngestJob &j, int y0)
+{
+	const int left = j.height - y0, pairs = (left < CHUNK_ROWS ? left : CHUNK_ROWS) >> 1, per_row = j.width >> 4;      // (whole spans)
+	for (int i = (int)threadIdx.x; i < pairs * per_row; i += HMR_BLOCK) {
+		const int r = i / per_row, x = (i - r * per_row) << 4, y = y0 + 2 * r;
+		yuv_span<L, SB, K>(j, x, y);
+	}
+	const int tail = (j.width & 15) >> 1;
+	for (int i = (int)threadIdx.x; i < pairs * tail; i += HMR_BLOCK) {
+		const int r = i / tail;
+		yuv_block(j, (j.width & ~15) + 2 * (i - r * tail), y0 + 2 * r);
+	}
+}
+template <int L, int SB>
+__device__ __forceinline__ void yuv_chunk_k(const YuvIngestJob &j, int y0)
+{
+	if (j.f.k == 0) yuv_chunk<L, SB, 0>(j, y0);
+	else if (j.f.k == 1) yuv_chunk<L, SB, 1>(j, y0);
+	else yuv_chunk<L, SB, 2>(j, y0);
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_ingest_yuv(const YuvIngestJob *jobs)
+{
+	const YuvIngestJob j = jobs[blockIdx.y];
+	const int y0 = (int)blockIdx.x * CHUNK_ROWS;
+	if (y0 >= j.height) return;
+	const bool wide = j.f.sb == 2;
+	switch (j.f.format) {
+	case HMR_YUV_PLANAR:
+		if (wide) yuv_chunk_k<YUV_PLANAR, 2>(j, y0);
+		else yuv_chunk_k<YUV_PLANAR, 1>(j, y0);
+		break;
+	case HMR_YUV_SEMIPLANAR:
+		if (wide) yuv_chunk_k<YUV_SEMI, 2>(j, y0);
+		else yuv_chunk_k<YUV_SEMI, 1>(j, y0);
+		break;
+	default:
+		if (wide) yuv_chunk<YUV_PACKED, 2, 1>(j, y0);
+		else yuv_chunk<YUV_PACKED, 1, 1>(j, y0);
+		break;
+	}
+}
+
 // ---- downscaling ingest (section 12g) ----
 // k_downscale: 8-bit pictures of one size, area-averaged (scale_area.h) into the int16 planes of a smaller - or equal - size.  1.5 Ws Hs bytes read, 3 Wd Hd written per
 // picture (hmr_scale_bytes in picture_io.h).  blockIdx.y = picture; blockIdx.x = a tile of tile_rows output rows x SCALE_TILE_W output columns of one plane class - the
@@ -1147,6 +1331,7 @@ __global__ __launch_bounds__(64) void k_picture_jobs(const uint32_t *h_jobs, uin
 inline int chunks_of(const IngestJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
 inline int chunks_of(const EgressJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
 inline int chunks_of(const RgbIngestJob &j) { return rgb_chunks(j.height); }
+inline int chunks_of(const YuvIngestJob &j) { return rgb_chunks(j.height); }
 inline int chunks_of(const ScaleJob &j) { return scale_tiles(j); }
 inline int chunks_of(const RgbScaleJob &j) { return scale_tiles(j); }
 inline int chunks_of(const SsimJob &j) { return ssim_tiles(j.width, j.height); }
@@ -1169,6 +1354,7 @@ int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, J
 int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n) { return launch(k_ingest, stream, h_jobs, d_jobs, n); }
 int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n) { return launch(k_egress, stream, h_jobs, d_jobs, n); }
 int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n) { return launch(k_ingest_rgb, stream, h_jobs, d_jobs, n); }
+int hmr_ingest_yuv_launch(hipStream_t stream, const YuvIngestJob *h_jobs, YuvIngestJob *d_jobs, int n) { return launch(k_ingest_yuv, stream, h_jobs, d_jobs, n); }
 int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n) { return launch(k_downscale, stream, h_jobs, d_jobs, n); }
 int hmr_rgb_scale_launch(hipStream_t stream, const RgbScaleJob *h_jobs, RgbScaleJob *d_jobs, int n) { return launch(k_rgb_ladder, stream, h_jobs, d_jobs, n); }
 int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n) { return launch(k_ssim, stream, h_jobs, d_jobs, n); }
@@ -1331,6 +1517,87 @@ extern "C" int hmr_gpu_rgb_convert_host(const hmr_gpu_rgb_picture *pic, int widt
 			const size_t oc = (size_t)(by >> 1) * (width >> 1) + (bx >> 1);
 			u[oc] = (uint8_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
 			v[oc] = (uint8_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
+		}
+	return HMR_GPU_OK;
+}
+
+// ---- section 12k: the host side of the deep / 4:2:2 / 4:4:4 ingest ----
+static_assert(HMR_YUV_PLANAR == HMR_GPU_YUV_PLANAR && HMR_YUV_SEMIPLANAR == HMR_GPU_YUV_SEMIPLANAR && HMR_YUV_PACKED422 == HMR_GPU_YUV_PACKED422, "yuv_depth.h restates the header's formats");
+static int refuse_yuv(const char *what)
+{
+	hmr_set_error("hmr_gpu_yuv_picture: %s", what);
+	return HMR_GPU_ERR_ARG;
+}
+// a Y'CbCr descriptor against a picture size, on the host alone
+extern "C" int hmr_gpu_yuv_picture_check(const hmr_gpu_yuv_picture *pic, int width, int height)
+{
+	if (!pic) return refuse_yuv("the descriptor is NULL");
+	if (pic->format < HMR_GPU_YUV_PLANAR || pic->format > HMR_GPU_YUV_PACKED422) return refuse_yuv("format: not one of HMR_GPU_YUV_PLANAR, _SEMIPLANAR, _PACKED422");
+	if (pic->chroma < HMR_GPU_CHROMA_420 || pic->chroma > HMR_GPU_CHROMA_444) return refuse_yuv("chroma: not one of HMR_GPU_CHROMA_420, _422, _444");
+	if (pic->bits < 8 || pic->bits > 16) return refuse_yuv("bits: outside 8 .. 16");
+	if (pic->msb_aligned != 0 && pic->msb_aligned != 1) return refuse_yuv("msb_aligned: must be 0 or 1");
+	if (pic->msb_aligned && (pic->bits == 8 || pic->bits == 16)) return refuse_yuv("msb_aligned: must be 0 with bits 8 or 16 (the sample fills its container)");
+	if (pic->reserved != 0) return refuse_yuv("reserved: must be 0");
+	if (width <= 0 || (width & 1)) return refuse_yuv("width: must be positive and even");
+	if (height <= 0 || (height & 1)) return refuse_yuv("height: must be positive and even");
+	if (pic->format == HMR_GPU_YUV_PACKED422 && pic->chroma != HMR_GPU_CHROMA_422) return refuse_yuv("chroma: must be HMR_GPU_CHROMA_422 for HMR_GPU_YUV_PACKED422");
+	static const char *const offset_zero[3] = {"offset[0]: must be 0 for this format", "offset[1]: must be 0 for HMR_GPU_YUV_PLANAR", "offset[2]: must be 0 for HMR_GPU_YUV_PLANAR"};
+	if (pic->format == HMR_GPU_YUV_PLANAR) {
+		for (int c = 0; c < 3; c++)
+			if (pic->offset[c] != 0) return refuse_yuv(offset_zero[c]);
+	} else if (pic->format == HMR_GPU_YUV_SEMIPLANAR) {
+		if (pic->offset[0] != 0) return refuse_yuv(offset_zero[0]);
+		if (pic->offset[1] < 0 || pic->offset[1] > 1) return refuse_yuv("offset[1]: outside 0 .. 1 (U's place in a pair)");
+		if (pic->offset[2] < 0 || pic->offset[2] > 1) return refuse_yuv("offset[2]: outside 0 .. 1 (V's place in a pair)");
+		if (pic->offset[2] == pic->offset[1]) return refuse_yuv("offset[2]: the same sample of a pair as offset[1]");
+	} else {
+		if (pic->offset[0] < 0 || pic->offset[0] > 1) return refuse_yuv("offset[0]: outside 0 .. 1 (the first luma sample of a group of four)");
+		if (pic->offset[1] < 0 || pic->offset[1] > 3) return refuse_yuv("offset[1]: outside 0 .. 3");
+		if (pic->offset[2] < 0 || pic->offset[2] > 3) return refuse_yuv("offset[2]: outside 0 .. 3");
+		if (((pic->offset[1] ^ pic->offset[0]) & 1) == 0) return refuse_yuv("offset[1]: a luma sample's place (offset[0] and offset[0] + 2)");
+		if (((pic->offset[2] ^ pic->offset[0]) & 1) == 0) return refuse_yuv("offset[2]: a luma sample's place (offset[0] and offset[0] + 2)");
+		if (pic->offset[2] == pic->offset[1]) return refuse_yuv("offset[2]: the same sample of a group as offset[1]");
+	}
+	const int planes = pic->format == HMR_GPU_YUV_PLANAR ? 3 : pic->format == HMR_GPU_YUV_SEMIPLANAR ? 2 : 1;
+	const int sb = pic->bits > 8 ? 2 : 1;
+	const int64_t wc = pic->chroma == HMR_GPU_CHROMA_444 ? width : width / 2;
+	const int64_t row_bytes[3] = {(pic->format == HMR_GPU_YUV_PACKED422 ? 2 : 1) * (int64_t)width * sb, (pic->format == HMR_GPU_YUV_SEMIPLANAR ? 2 : 1) * wc * sb, wc * sb};
+	static const char *const missing[3] = {"plane[0]: NULL", "plane[1]: NULL", "plane[2]: NULL"};
+	static const char *const extra[3] = {"", "plane[1]: must be NULL for HMR_GPU_YUV_PACKED422 (plane[0] holds the samples)", "plane[2]: must be NULL for this format (it has no third plane)"};
+	static const char *const negative[3] = {"pitch[0]: negative", "pitch[1]: negative", "pitch[2]: negative"};
+	static const char *const narrow[3] = {"pitch[0]: less than a row's bytes (W sb; PACKED422: 2 W sb)", "pitch[1]: less than a row's bytes (Wc sb; SEMIPLANAR: 2 Wc sb)", "pitch[2]: less than a row's bytes (Wc sb)"};
+	static const char *const plane_align[3] = {"plane[0]: not a multiple of 2 (16-bit containers)", "plane[1]: not a multiple of 2 (16-bit containers)", "plane[2]: not a multiple of 2 (16-bit containers)"};
+	static const char *const pitch_align[3] = {"pitch[0]: not a multiple of 2 (16-bit containers)", "pitch[1]: not a multiple of 2 (16-bit containers)", "pitch[2]: not a multiple of 2 (16-bit containers)"};
+	for (int c = 0; c < 3; c++) {
+		if (c >= planes) {
+			if (pic->plane[c]) return refuse_yuv(extra[c]);
+			continue;
+		}
+		if (!pic->plane[c]) return refuse_yuv(missing[c]);
+		if (pic->pitch[c] < 0) return refuse_yuv(negative[c]);
+		if (pic->pitch[c] < row_bytes[c]) return refuse_yuv(narrow[c]);
+		if ((uintptr_t)pic->plane[c] % sb) return refuse_yuv(plane_align[c]);
+		if (pic->pitch[c] % sb) return refuse_yuv(pitch_align[c]);
+	}
+	return HMR_GPU_OK;
+}
+
+// yuv_depth.h's arithmetic over host memory: the loop a caller would write from the header's formulas
+extern "C" int hmr_gpu_yuv_convert_host(const hmr_gpu_yuv_picture *pic, int width, int height, uint8_t *y, uint8_t *u, uint8_t *v)
+{
+	const int rc = hmr_gpu_yuv_picture_check(pic, width, height);
+	if (rc) return rc;
+	if (!y || !u || !v) {
+		hmr_set_error("hmr_gpu_yuv_convert_host: needs the three output planes");
+		return HMR_GPU_ERR_ARG;
+	}
+	const YuvForm f = hmr_yuv_form(pic->format, pic->chroma, pic->bits, pic->msb_aligned, pic->offset);
+	for (int py = 0; py < height; py++)
+		for (int px = 0; px < width; px++) y[(size_t)py * width + px] = (uint8_t)hmr_yuv_luma<const uint8_t *>(pic->plane, pic->pitch, f, px, py);
+	for (int cy = 0; cy < height / 2; cy++)
+		for (int cx = 0; cx < width / 2; cx++) {
+			u[(size_t)cy * (width / 2) + cx] = (uint8_t)hmr_yuv_chroma<const uint8_t *>(pic->plane, pic->pitch, f, 1, cx, cy);
+			v[(size_t)cy * (width / 2) + cx] = (uint8_t)hmr_yuv_chroma<const uint8_t *>(pic->plane, pic->pitch, f, 2, cx, cy);
 		}
 	return HMR_GPU_OK;
 }

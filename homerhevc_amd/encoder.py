@@ -6,6 +6,8 @@
 
     au, slice_type = enc.encode(RGBFrame(rgb))  # rgb: a [3, H, W] tensor (uint8, or float16 / float32 in 0 .. 1) or packed uint8 [H, W, 3 or 4]; BT.709 limited range
     yuv = enc.source()                          # the 4:2:0 picture that frame was encoded from, as a uint8 CUDA tensor
+    au, slice_type = enc.encode(YUVFrame((y16, uv16), bits=10, msb_aligned=True))      # P010 from a decoder: int16 / uint16 tensors [H, W], [H / 2, W / 2, 2]; rounded to 8 bits by the ingest
+    au, slice_type = enc.encode(YUVFrame((y, u, v), chroma="444"))                     # planar 4:4:4 (a JPEG decoder): chroma averaged 2 x 2;  YUVFrame(yuyv, order="yuyv"): packed 4:2:2
 
     ladder = BatchEncoder([EncoderConfig(1920, 1080, ...), EncoderConfig(1280, 720, ...), EncoderConfig(960, 544, ...)])
     ladder.step([frame, ScaledFrame(frame, 1920, 1080), ScaledFrame(frame, 1920, 1080)])      # one 1080p picture, area-averaged down to each rung by ONE launch
@@ -19,8 +21,8 @@
     out, ssd = enc.export_rgb(dtype=torch.float16, reference=RGBFrame(rgb))     # the reconstructed picture as RGB [3, H, W], the sums of squared differences to `rgb` as int64 [3]
     r, g, b, all3 = psnr_rgb(ssd.tolist(), 1920, 1080)                          # PSNR against the RGB frame that was supplied
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h, 12i and 12j).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; scaled frames: k_downscale, which area-averages in the same pass; scaled RGB frames: k_rgb_ladder, which does both) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h, 12i, 12j and 12k).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; YUVFrame - more than 8 bits, 4:2:2, 4:4:4, packed -: k_ingest_yuv, which rounds to 8-bit 4:2:0 in the same pass; scaled frames: k_downscale, which area-averages in the same pass; scaled RGB frames: k_rgb_ladder, which does both) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
@@ -30,6 +32,10 @@ from .build import LIB_PATH
 
 PIC_I420, PIC_NV12 = 0, 1
 RGB_PACKED8, RGB_PLANAR8, RGB_PLANAR_F16, RGB_PLANAR_F32 = 0, 1, 2, 3
+YUV_PLANAR, YUV_SEMIPLANAR, YUV_PACKED422 = 0, 1, 2
+CHROMAS = {"420": 0, "422": 1, "444": 2}
+PAIR_ORDERS = {"uv": (0, 0, 1), "vu": (0, 1, 0)}                                                               # offset[] of a semi-planar picture
+PACKED_ORDERS = {"yuyv": (0, 1, 3), "uyvy": (1, 0, 2), "yvyu": (0, 3, 1), "vyuy": (1, 2, 0)}                   # offset[] of a packed 4:2:2 picture
 MATRICES = {"bt601": 0, "bt709": 1}
 ORDERS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0)), "argb": (4, (1, 2, 3)), "abgr": (4, (3, 2, 1))}      # pixel bytes, byte of R, G, B
 SLICE_P, SLICE_I = 1, 2
@@ -72,6 +78,12 @@ class RgbPicture(C.Structure):
                 ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3)]
 
 
+class YuvPicture(C.Structure):
+    """hmr_gpu_yuv_picture"""
+    _fields_ = [("format", C.c_int32), ("chroma", C.c_int32), ("bits", C.c_int32), ("msb_aligned", C.c_int32), ("offset", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("plane", C.c_void_p * 3), ("pitch", C.c_int64 * 3)]
+
+
 class ScaledPicture(C.Structure):
     """hmr_gpu_scaled_picture"""
     _fields_ = [("pic", Picture), ("width", C.c_int32), ("height", C.c_int32)]
@@ -92,8 +104,8 @@ class ScaledFrame:
     RGB sources are not taken here: ScaledRGBFrame takes them, and fills the slot with exactly what this class makes of the RGBFrame's source()."""
 
     def __init__(self, frame, width, height):
-        if isinstance(frame, (RGBFrame, ScaledFrame)):
-            raise TypeError("ScaledFrame: the frame has to be a 4:2:0 picture (what picture_of takes), not an RGBFrame or a ScaledFrame")
+        if isinstance(frame, (RGBFrame, ScaledFrame, YUVFrame)):
+            raise TypeError("ScaledFrame: the frame has to be an 8-bit 4:2:0 picture (what picture_of takes), not an RGBFrame, a YUVFrame or a ScaledFrame")
         self.frame, self.width, self.height = frame, int(width), int(height)
 
 
@@ -150,6 +162,76 @@ def rgb_picture_of(frame, width, height):
     for c in range(3):
         pic.plane[c], pic.pitch[c] = t.data_ptr() + c * t.stride(0) * t.element_size(), t.stride(1) * t.element_size()
     return pic, (t,)
+
+
+class YUVFrame:
+    """A Y'CbCr picture that is not 8-bit 4:2:0 I420 / NV12, for Encoder.encode / BatchEncoder.step: more than 8 bits, 4:2:2 or 4:4:4, NV21, packed.  Rounded to 8-bit 4:2:0
+    by the ingest kernel itself (k_ingest_yuv), in the integer arithmetic of include/homer_gpu.h section 12k: ONE rounding per sample, chroma averaged over its 1, 2 or 4
+    taps, no range, matrix or transfer conversion, no dithering (hmr_gpu_yuv_convert_host is the same arithmetic on the host).
+      planes: (y, u, v)  planar: [H, W] and two [Hc, Wc] tensors;
+              (y, uv)    semi-planar: uv [Hc, Wc, 2] or [Hc, 2 Wc]; order "uv" (NV12, P010: the default) or "vu" (NV21);
+              one tensor [H, W, 2] or [H, 2 W]: packed 4:2:2; order "yuyv" (the default), "uyvy", "yvyu" or "vyuy"; chroma has to be "422";
+              Wc = W / 2 for chroma "420" and "422", W for "444"; Hc = H / 2 for "420", H otherwise.
+      bits: 8 .. 16.  uint8 tensors for 8 bits; int16 - or uint16 where torch has it - for more (the 16 bits are read as unsigned either way).
+      msb_aligned: the sample lies in the container's high bits (P010, P016's 12-bit form, Y210) rather than in its low bits (yuv420p10le).
+    The tensors need unit stride along a row; views and crops of larger tensors are fine.  source(), export(ssd=True), ssim() and export_rgb(source=True) then see the
+    8-bit picture that was encoded.  A ScaledFrame does not take one."""
+
+    def __init__(self, planes, chroma="420", bits=8, msb_aligned=False, order=None):
+        chroma = str(chroma)
+        if chroma not in CHROMAS:
+            raise ValueError(f"YUVFrame: chroma has to be one of {sorted(CHROMAS)}, got {chroma!r}")
+        if not 8 <= int(bits) <= 16:
+            raise ValueError(f"YUVFrame: bits has to be 8 .. 16, got {bits!r}")
+        planes = tuple(planes) if isinstance(planes, (tuple, list)) else (planes,)
+        if len(planes) not in (1, 2, 3):
+            raise ValueError("YUVFrame: (y, u, v), (y, uv) or one packed tensor")
+        orders = {1: PACKED_ORDERS, 2: PAIR_ORDERS, 3: {None: (0, 0, 0)}}[len(planes)]
+        if order is None:
+            order = {1: "yuyv", 2: "uv", 3: None}[len(planes)]
+        if order not in orders:
+            raise ValueError(f"YUVFrame: order has to be one of {sorted(k for k in orders if k)} for {len(planes)} tensor(s), got {order!r}")
+        if len(planes) == 1 and chroma != "422":
+            raise ValueError("YUVFrame: a packed picture is 4:2:2")
+        self.planes, self.chroma, self.bits, self.msb_aligned, self.order = planes, chroma, int(bits), bool(msb_aligned), order
+        self.offsets = orders[order]
+
+
+def yuv_picture_of(frame, width, height):
+    """The descriptor (hmr_gpu_yuv_picture) of a width x height YUVFrame; nothing is copied, the tensors' strides become the pitches.  Returns (YuvPicture, tensors): keep
+    the tensors until the load call that takes the descriptor has returned."""
+    import torch
+    w, h = int(width), int(height)
+    wide = frame.bits > 8
+    dtypes = (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ()) if wide else (torch.uint8,)
+    sb = 2 if wide else 1
+    planes = list(frame.planes)
+    for i, t in enumerate(planes):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dtypes:
+            raise TypeError(f"yuv_picture_of: plane {i} has to be a CUDA tensor of {' or '.join(str(d) for d in dtypes)} for {frame.bits} bits")
+    wc, hc = (w if frame.chroma == "444" else w // 2), (h // 2 if frame.chroma == "420" else h)
+    pic = YuvPicture(format=(YUV_PACKED422, YUV_SEMIPLANAR, YUV_PLANAR)[len(planes) - 1], chroma=CHROMAS[frame.chroma], bits=frame.bits, msb_aligned=int(frame.msb_aligned), reserved=0)
+    pic.offset[0], pic.offset[1], pic.offset[2] = frame.offsets
+
+    def rows_of(t, rows, cols, group, what):
+        """t as [rows, cols * group] with unit stride along a row: [rows, cols, group] tensors have their groups next to each other"""
+        if t.dim() == 3 and group > 1:
+            if tuple(t.shape) != (rows, cols, group) or t.stride(2) != 1 or t.stride(1) != group:
+                raise ValueError(f"yuv_picture_of: {what} has to be [{rows}, {cols}, {group}] with the samples of a group next to each other, got {tuple(t.shape)} with strides {t.stride()}")
+            return t.as_strided((rows, cols * group), (t.stride(0), 1))
+        if t.dim() != 2 or tuple(t.shape) != (rows, cols * group) or t.stride(1) != 1:
+            raise ValueError(f"yuv_picture_of: {what} has to be [{rows}, {cols * group}] with unit stride along a row, got {tuple(t.shape)} with strides {t.stride()}")
+        return t
+
+    if len(planes) == 1:
+        planes = [rows_of(planes[0], h, w, 2, "the packed picture")]
+    elif len(planes) == 2:
+        planes = [rows_of(planes[0], h, w, 1, "the luma plane"), rows_of(planes[1], hc, wc, 2, "the plane of pairs")]
+    else:
+        planes = [rows_of(planes[0], h, w, 1, "the luma plane"), rows_of(planes[1], hc, wc, 1, "the U plane"), rows_of(planes[2], hc, wc, 1, "the V plane")]
+    for c, t in enumerate(planes):
+        pic.plane[c], pic.pitch[c] = t.data_ptr(), t.stride(0) * sb
+    return pic, tuple(planes)
 
 
 class ScaledRGBFrame:
@@ -250,6 +332,8 @@ def load_library():
         lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_load_source_rgb_device.argtypes = [P, I, C.POINTER(RgbPicture), P]
         lib.hmr_gpu_enc_load_sources_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), P]
+        lib.hmr_gpu_enc_load_source_yuv_device.argtypes = [P, I, C.POINTER(YuvPicture), P]
+        lib.hmr_gpu_enc_load_sources_yuv_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(YuvPicture), P]
         lib.hmr_gpu_enc_load_source_scaled_device.argtypes = [P, I, C.POINTER(ScaledPicture), P]
         lib.hmr_gpu_enc_load_sources_scaled_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledPicture), P]
         lib.hmr_gpu_enc_load_source_scaled_rgb_device.argtypes = [P, I, C.POINTER(ScaledRgbPicture), P]
@@ -359,12 +443,12 @@ def _ssim(lib, device, encs, slot):
 
 
 def _load(lib, device, encs, cfgs, slot, frames):
-    """the frames (what picture_of takes, RGBFrame, ScaledFrame or ScaledRGBFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
-    kinds = {"yuv": [], "rgb": [], "scaled": [], "scaled_rgb": []}
+    """the frames (what picture_of takes, RGBFrame, YUVFrame, ScaledFrame or ScaledRGBFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
+    kinds = {"yuv": [], "rgb": [], "deep": [], "scaled": [], "scaled_rgb": []}
     for k, f in enumerate(frames):
-        kinds["rgb" if isinstance(f, RGBFrame) else "scaled" if isinstance(f, ScaledFrame) else "scaled_rgb" if isinstance(f, ScaledRGBFrame) else "yuv"].append(k)
-    calls = {"yuv": (Picture, "hmr_gpu_enc_load_sources_device"), "rgb": (RgbPicture, "hmr_gpu_enc_load_sources_rgb_device"), "scaled": (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device"),
-             "scaled_rgb": (ScaledRgbPicture, "hmr_gpu_enc_load_sources_scaled_rgb_device")}
+        kinds["rgb" if isinstance(f, RGBFrame) else "deep" if isinstance(f, YUVFrame) else "scaled" if isinstance(f, ScaledFrame) else "scaled_rgb" if isinstance(f, ScaledRGBFrame) else "yuv"].append(k)
+    calls = {"yuv": (Picture, "hmr_gpu_enc_load_sources_device"), "rgb": (RgbPicture, "hmr_gpu_enc_load_sources_rgb_device"), "deep": (YuvPicture, "hmr_gpu_enc_load_sources_yuv_device"),
+             "scaled": (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device"), "scaled_rgb": (ScaledRgbPicture, "hmr_gpu_enc_load_sources_scaled_rgb_device")}
     keep = []
     for kind, members in kinds.items():
         n = len(members)
@@ -378,7 +462,7 @@ def _load(lib, device, encs, cfgs, slot, frames):
             elif kind == "scaled_rgb":
                 pics[j], t = scaled_rgb_picture_of(frames[k])
             else:
-                pics[j], t = (rgb_picture_of if kind == "rgb" else picture_of)(frames[k], cfgs[k].width, cfgs[k].height)
+                pics[j], t = (rgb_picture_of if kind == "rgb" else yuv_picture_of if kind == "deep" else picture_of)(frames[k], cfgs[k].width, cfgs[k].height)
             keep.append(t)
         if getattr(lib, name)((C.c_void_p * n)(*[encs[k] for k in members]), n, (C.c_int * n)(*([slot] * n)), pics, _stream_of(device)) != 0:
             _fail(lib, name)
@@ -476,7 +560,7 @@ class Encoder:
         self.slot_used = None            # the slot of the last encoded frame (export)
 
     def encode(self, frame, image_type=IMAGE_AUTO):
-        """frame: what picture_of takes, an RGBFrame, a ScaledFrame or a ScaledRGBFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
+        """frame: what picture_of takes, an RGBFrame, a YUVFrame, a ScaledFrame or a ScaledRGBFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
         2 for I)."""
         lib = self.lib
         keep = _load(lib, self.device, [self.enc], [self.cfg], self.slot, [frame])
@@ -529,7 +613,7 @@ class Encoder:
         return (pics[0], sums[0]) if sums is not None else pics[0]
 
     def source(self, out=None, nv12=False):
-        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a ScaledFrame or a ScaledRGBFrame the scaled 4:2:0 picture.  `out` and nv12 as in
+        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a YUVFrame the 8-bit 4:2:0 picture the rounding made, for a ScaledFrame or a ScaledRGBFrame the scaled 4:2:0 picture.  `out` and nv12 as in
         export(); one launch of the egress kernel, ordered on torch's current stream."""
         if self.slot_used is None:
             raise RuntimeError("Encoder.source: nothing has been encoded yet")
@@ -554,7 +638,7 @@ class BatchEncoder:
     """Several sequences (configurations with wfpp_num_threads > 1: the batch schedule), one picture of each per step(): ONE ingest launch for all their pictures and ONE
     launch for all their CTU stages.  Every sequence has a context - a stream - of its own.
 
-    step(frames): frames[i] is sequence i's next picture (what picture_of takes, an RGBFrame, a ScaledFrame or a ScaledRGBFrame; a step that has several kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
+    step(frames): frames[i] is sequence i's next picture (what picture_of takes, an RGBFrame, a YUVFrame, a ScaledFrame or a ScaledRGBFrame; a step that has several kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
     Not pipelined: entry i is the access unit of frames[i] (b"" for None).
     Pipelined (the default): access units are delivered ONE STEP LATE, as by hmr_gpu_enc_encode_batch_pipelined - entry i is the access unit of the picture sequence i was
     given in the previous step (b"" if it was given none), whose download and entropy coding ran beside this step's launch; flush() returns those of the last step.  When

@@ -788,7 +788,7 @@ int hmr_gpu_psnr(const uint64_t ssd[3], int width, int height, double psnr[3]);
  *       BT.709 full       13933, 46871, 4732    -7509, -25259, 32768     32768, -29763, -3005    0
  *     Every output is within 0.51 of the real-valued BT formula; grey gives U = V = 128 at every level; limited-range luma stays in 16 .. 235 and chroma in 16 .. 240.
  *     The stream does NOT say which matrix or range was used: the parameter sets stay byte-identical to the reference's, which writes no colour description into the VUI.
- *     Whoever decodes the stream has to be told by other means.  (Out of scope as well: other chroma sitings, 10-bit, bfloat16, alpha - a fourth byte is ignored.)
+ *     Whoever decodes the stream has to be told by other means.  (Out of scope as well: other chroma sitings, 10-bit RGB - 10-bit Y'CbCr: section 12k -, bfloat16, alpha - a fourth byte is ignored.)
  *     hmr_gpu_rgb_picture_check: pure host, like hmr_gpu_picture_check; names the field.  Refused: NULL descriptor, unknown format, matrix, full_range outside 0 / 1,
  *     non-zero reserved, odd or non-positive width / height; PACKED8: pixel_bytes not 3 or 4, an offset outside 0 .. pixel_bytes - 1 or repeated, plane[0] NULL,
  *     plane[1] or plane[2] given; planar: pixel_bytes or an offset not 0, a NULL plane; a negative pitch or one below a row's bytes (width x pixel_bytes, width x
@@ -953,7 +953,7 @@ int hmr_gpu_ssim_host(const hmr_gpu_picture *a, const hmr_gpu_picture *b, int wi
  *     into a descriptor whose planes are host pointers.  hmr_gpu_rgb_ssd_host: the same sums between two RGB pictures in host memory, in any two forms.  Both are pure
  *     host code - no device, no context - and refuse what hmr_gpu_rgb_picture_check refuses and NULL arguments.  hmr_gpu_psnr_rgb refuses NULL arguments and an odd or
  *     non-positive width or height.
- *     Out of scope: other chroma sitings or upsampling filters, 10-bit or bfloat16 output, a colour description in the VUI (12f: the stream does not say which matrix
+ *     Out of scope: other chroma sitings or upsampling filters, 10-bit or bfloat16 output (12k brings deeper pictures IN; what comes out stays 8-bit), a colour description in the VUI (12f: the stream does not say which matrix
  *     or range was used), SSIM in the RGB domain, scaled RGB export.
  * ------------------------------------------------------------------------------------------------ */
 int hmr_gpu_enc_export_pictures_rgb_device(hmr_gpu_enc **encs, int n, const int *which, const hmr_gpu_rgb_picture *outs, const hmr_gpu_rgb_picture *refs, uint64_t *dev_ssd,
@@ -1000,6 +1000,70 @@ typedef struct hmr_gpu_scaled_rgb_picture {
 int hmr_gpu_enc_load_sources_scaled_rgb_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_scaled_rgb_picture *pics, void *producer_stream);
 int hmr_gpu_enc_load_source_scaled_rgb_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_rgb_picture *pic, void *producer_stream);
 int hmr_gpu_scale_rgb_host(const hmr_gpu_scaled_rgb_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v);
+
+/* ------------------------------------------------------------------------------------------------
+ * 12k. Y'CbCr pictures of more than 8 bits, 4:2:2 and 4:4:4 in device memory: rounding to 8-bit 4:2:0 inside the ingest (no counterpart in the reference)
+ *     12d takes 8-bit 4:2:0 as I420 or NV12.  A decoder leaves more than that on the GPU: P010 / P016 (16-bit containers, the sample in the high bits) and
+ *     yuv420p10le-style planes (the sample in the low bits) from every 10-bit source; planar or semi-planar 4:2:2 and 4:4:4 from JPEG and mezzanine decoders; packed
+ *     YUYV / UYVY (and Y210 / Y216) from capture.  hmr_gpu_enc_load_sources_yuv_device brings n such pictures (1 .. 512; forms may be mixed within a call) to 8-bit
+ *     4:2:0 and into picture slots of their encoders with ONE launch of a bandwidth-bound kernel (k_ingest_yuv, picture_io.hip): every source sample is read once,
+ *     nothing is written but the slot.  What the encoder encodes does not change: it stays 8-bit 4:2:0.
+ *     The arithmetic is defined in integers, so that a caller can reproduce every sample (homerhevc_amd/csrc/yuv_depth.h holds it once, for the kernel and the host).
+ *     A source sample is an unsigned integer in a container of 1 byte (bits == 8) or 2 bytes (bits 9 .. 16, little endian).
+ *       raw    = the container's value
+ *       v      = msb_aligned ? raw >> (16 - bits) : min(raw, 2^bits - 1)
+ *       s      = bits - 8
+ *       luma:    Y(x, y) = min(255, (v + r(s)) >> s)                          r(t) = t ? 1 << (t - 1) : 0
+ *       chroma:  n = 2^k taps, S = their sum of v
+ *                C(cx, cy) = min(255, (S + r(s + k)) >> (s + k))
+ *         4:2:0  k = 0: the sample (cx, cy)
+ *         4:2:2  k = 1: column cx of chroma rows 2 cy and 2 cy + 1           (vertical average; horizontal siting untouched)
+ *         4:4:4  k = 2: the 2 x 2 block (2 cx .., 2 cy ..)                    (the block's average, sited at its centre: what 12f makes)
+ *     ONE rounding and nothing in between, in unsigned 32-bit arithmetic: 4 x 65535 + 2^9 < 2^32.  So:
+ *       - every output is within 0.5 of the real-valued average of v / 2^s; where that average is >= 255.5 the result is 255 (10-bit 1023 -> 255, four 16-bit
+ *         65535 -> 255);
+ *       - 8-bit 4:2:0 is the identity: the slot is bit for bit what hmr_gpu_enc_load_sources_device gives for the same planes;
+ *       - an 8-bit picture widened to any depth (v << s, in either alignment) comes back unchanged, for every chroma format when the widened chroma is constant over
+ *         its taps;
+ *       - 10-bit limited range stays limited range: 64 -> 16, 940 -> 235, 960 -> 240.
+ *     There is NO range conversion, no tone mapping, no dithering and no change of the transfer function: a PQ or HLG source stays PQ or HLG in 8 bits.  The stream
+ *     carries no colour description (12f): whoever decodes it has to be told by other means.
+ *     Layouts.  sb: the container's bytes; chroma width Wc = W / 2 for 4:2:0 and 4:2:2, W for 4:4:4; chroma rows Hc = H / 2 for 4:2:0, H otherwise.
+ *       PLANAR       planes Y, U, V; pitches at least W sb, Wc sb, Wc sb; offset[] all 0.
+ *       SEMIPLANAR   planes Y and one plane of interleaved pairs, plane[2] NULL; pitches at least W sb, 2 Wc sb; offset[0] = 0, offset[1] and offset[2] in {0, 1},
+ *                    distinct: which sample of a pair is U and which is V (NV12 / P010: 0, 1; NV21: 1, 0).
+ *       PACKED422    plane[0] only, groups of four samples per two pixels; pitch at least 2 W sb; chroma = HMR_GPU_CHROMA_422 only.  offset[0] in {0, 1} is the
+ *                    group's first luma sample, the second is at offset[0] + 2; offset[1] and offset[2] are the two remaining positions (YUYV: 0, 1, 3; UYVY: 1, 0, 2;
+ *                    YVYU: 0, 3, 1; VYUY: 1, 2, 0).  Y210 / Y216 are PACKED422 with 16-bit containers.
+ *     16-bit containers need planes and pitches that are multiples of 2.  Any base address and pitch otherwise, so a crop is just a view.
+ *     hmr_gpu_yuv_picture_check: pure host, like hmr_gpu_picture_check; names the field.  Refused: a NULL descriptor; an unknown format or chroma; bits outside
+ *     8 .. 16; msb_aligned outside 0 / 1, or 1 with bits 8 or 16 (there is nothing to align); non-zero reserved; an odd or non-positive width or height; PACKED422
+ *     with another chroma; an offset outside what its format allows, or repeated; a missing plane, or a plane the format does not have; a negative pitch, or one
+ *     below a row's bytes; a 16-bit plane or pitch that is not a multiple of 2.
+ *     hmr_gpu_yuv_convert_host: the same arithmetic in plain loops over HOST memory - the descriptor's planes are host pointers here - into tightly packed I420 planes
+ *     (y: width x height, u, v: width / 2 x height / 2).  No device, no context.  It refuses what the check refuses, before a pointer is followed, and NULL outputs.
+ *     A utility in the spirit of hmr_gpu_rgb_convert_host; it is not a fallback for encoding.
+ *     The load calls carry the contract of 12d word for word: the launch runs on the first encoder's stream behind what producer_stream holds now, producer_stream
+ *     and the other encoders' streams go on behind it, the host waits for nothing (but for a slot that has to be allocated first); only the bytes of the rows are
+ *     read - [plane + y * pitch, plane + y * pitch + row bytes) -, nothing outside width x height of the slot is written; a slot filled this way is indistinguishable,
+ *     to every encode call, from one filled by hmr_gpu_enc_load_sources_device with the converted I420 picture.  hmr_gpu_enc_export_sources_device (12f) returns
+ *     what the slot holds.  Refused as in 12d, plus whatever hmr_gpu_yuv_picture_check refuses for the encoder's picture size.
+ *     Out of scope: upsampling chroma; other sitings or filters; dithering; range, matrix or transfer conversion; big-endian samples; the 10:10:10:2 packings (v210,
+ *     Y410); float Y'CbCr; high-depth or 4:2:2 / 4:4:4 OUTPUT (12e writes 8-bit 4:2:0); scaled deep sources (12g takes 8-bit 4:2:0); anything that changes what the
+ *     encoder itself encodes.
+ * ------------------------------------------------------------------------------------------------ */
+enum { HMR_GPU_YUV_PLANAR = 0, HMR_GPU_YUV_SEMIPLANAR = 1, HMR_GPU_YUV_PACKED422 = 2 };
+enum { HMR_GPU_CHROMA_420 = 0, HMR_GPU_CHROMA_422 = 1, HMR_GPU_CHROMA_444 = 2 };
+typedef struct hmr_gpu_yuv_picture {
+	int32_t format, chroma, bits, msb_aligned;   /* HMR_GPU_YUV_*; HMR_GPU_CHROMA_*; 8 .. 16; 1: the sample is in the container's high bits (P010), 0: in its low bits */
+	int32_t offset[3], reserved;                 /* see the layouts above; 0 */
+	const void *plane[3];                        /* device pointers (hmr_gpu_yuv_convert_host: host pointers); planes the format does not have are NULL */
+	int64_t pitch[3];                            /* bytes from row to row */
+} hmr_gpu_yuv_picture;                           /* 80 bytes */
+int hmr_gpu_yuv_picture_check(const hmr_gpu_yuv_picture *pic, int width, int height);
+int hmr_gpu_yuv_convert_host(const hmr_gpu_yuv_picture *pic, int width, int height, uint8_t *y, uint8_t *u, uint8_t *v);
+int hmr_gpu_enc_load_source_yuv_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_yuv_picture *pic, void *producer_stream);
+int hmr_gpu_enc_load_sources_yuv_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_yuv_picture *pics, void *producer_stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
