@@ -148,16 +148,9 @@ struct hmr_gpu_enc {
 	WorkSlow *d_pool_slow = nullptr;                     // the pool workers' transform / decoded windows
 	int pool_workers = 0;
 	int last_pool_kernel = -1;                           // (lead) which kernel the last pool launch ran - 0: k_encode_pool_lat, 1: k_encode_pool, 2: k_encode_full; -1: none yet
-	// picture conversion (picture_io.h, k_encode_picture_io.inc): the job tables and events of the k_ingest / k_ingest_rgb / k_downscale / k_egress / k_ssim / k_egress_rgb launches this encoder leads - as the first
+	// picture conversion (picture_io.h, k_encode_picture_io.inc): the job tables and events, one ring per job type, of the picture launches this encoder leads - as the first
 	// encoder of a load / export call, and alone in the host-memory entries (widen_packed, narrow_packed)
-	JobRing<IngestJob> ingest;
-	JobRing<RgbIngestJob> ingest_rgb;
-	JobRing<ScaleJob> scale;
-	JobRing<EgressJob> egress;
-	JobRing<SsimJob> ssim;
-	JobRing<RgbEgressJob> egress_rgb;
-	JobRing<RgbScaleJob> scale_rgb;                       // (k_rgb_ladder)
-	JobRing<YuvIngestJob> ingest_yuv;                     // (k_ingest_yuv)
+	PictureRings rings;
 	// every encoder: whether d_pic[cur] holds an encoded frame's final picture, the stream whose work wrote it (its own, or the lead's of a batch or chain launch),
 	// events for that stream and its own (an export call waits behind both)
 	bool has_picture = false;
@@ -203,38 +196,8 @@ int dev_alloc(T **p, size_t n, hipStream_t st)
 		if (rc_) return rc_;              \
 	} while (0)
 
-// Jobs of k_ingest / k_egress (picture_io.h).  Ingest: the 8-bit picture `pic` of e's size into the int16 planes `dst` (at sample (0, 0)) with the given strides.
-// Egress: e's final picture into `pic` (NULL: no picture), the sums of its squared differences against the int16 planes `src` of a picture slot (NULL: none) into ssd.
-IngestJob ingest_job(const hmr_gpu_enc *e, const hmr_gpu_picture &pic, int16_t *const dst[3], int stride_y, int stride_c)
-{
-	IngestJob j;
-	for (int c = 0; c < 3; c++) {
-		j.src[c] = pic.plane[c];
-		j.pitch[c] = pic.pitch[c];
-		j.dst[c] = dst[c];
-	}
-	j.stride_y = stride_y; j.stride_c = stride_c;
-	j.width = e->seq.width; j.height = e->seq.height;
-	j.format = pic.format; j.reserved = 0;
-	return j;
-}
-EgressJob egress_job(hmr_gpu_enc *e, const hmr_gpu_picture *pic, int16_t *const src[3], uint64_t *ssd)
-{
-	const Seq &s = e->seq;
-	EgressJob j;
-	for (int c = 0; c < 3; c++) {
-		j.rec[c] = plane0(e, e->cur, c);
-		j.src[c] = src ? src[c] : nullptr;
-		j.dst[c] = pic ? const_cast<uint8_t *>(pic->plane[c]) : nullptr;      // (as the output descriptor: the call writes through the plane pointers)
-		j.pitch[c] = pic ? pic->pitch[c] : 0;
-	}
-	j.ssd = ssd;
-	j.stride_y = s.stride_y; j.stride_c = s.stride_c;
-	j.src_stride_y = s.src_stride_y; j.src_stride_c = s.src_stride_c;
-	j.width = s.width; j.height = s.height;
-	j.format = pic ? pic->format : HMR_GPU_PIC_I420; j.reserved = 0;
-	return j;
-}
+// e's final picture as picture_io.h's job builders take it, and as a picture slot is held: the planes at sample (0, 0); their strides are e->seq.stride_y / stride_c
+SrcSlot final_planes(hmr_gpu_enc *e) { return SrcSlot{{plane0(e, e->cur, 0), plane0(e, e->cur, 1), plane0(e, e->cur, 2)}}; }
 // a tightly packed I420 picture of e's size at `bytes` (luma pitch width, chroma pitch width / 2): the staging buffer d_bytes, a picture as it travels between GPUs
 hmr_gpu_picture packed_picture(const hmr_gpu_enc *e, const uint8_t *bytes)
 {
@@ -244,14 +207,15 @@ hmr_gpu_picture packed_picture(const hmr_gpu_enc *e, const uint8_t *bytes)
 // Queued on the encoder's own stream, nothing waited for: the packed picture at `bytes` (device memory) into the planes `dst` / e's final picture into one at `bytes`.
 int widen_packed(hmr_gpu_enc *e, const uint8_t *bytes, int16_t *const dst[3], int stride_y, int stride_c)
 {
-	const IngestJob j = ingest_job(e, packed_picture(e, bytes), dst, stride_y, stride_c);
-	return run_jobs(e->ingest, hmr_ingest_launch, e->ctx->stream, &j, 1, e->ctx->stream);
+	const IngestJob j = hmr_ingest_job(packed_picture(e, bytes), dst, stride_y, stride_c, e->seq.width, e->seq.height);
+	return run_jobs(e->rings, e->ctx->stream, &j, 1, e->ctx->stream);
 }
 int narrow_packed(hmr_gpu_enc *e, uint8_t *bytes)
 {
+	const Seq &s = e->seq;
 	const hmr_gpu_picture pic = packed_picture(e, bytes);
-	const EgressJob j = egress_job(e, &pic, nullptr, nullptr);
-	return run_jobs(e->egress, hmr_egress_launch, e->ctx->stream, &j, 1, e->ctx->stream);
+	const EgressJob j = hmr_egress_job(final_planes(e).p, s.stride_y, s.stride_c, &pic, nullptr, s.src_stride_y, s.src_stride_c, nullptr, s.width, s.height);
+	return run_jobs(e->rings, e->ctx->stream, &j, 1, e->ctx->stream);
 }
 
 // a picture in host memory into the planes `dst`: the device path (k_ingest) plus the copy into the staging buffer and a synchronise
@@ -885,14 +849,7 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	if (e->d_gather) (void)hipFree(e->d_gather);
 	if (e->h_gather) (void)hipHostFree(e->h_gather);
 	if (e->h_offs) (void)hipHostFree(e->h_offs);
-	e->ingest.release();
-	e->ingest_rgb.release();
-	e->ingest_yuv.release();
-	e->scale.release();
-	e->egress.release();
-	e->ssim.release();
-	e->egress_rgb.release();
-	e->scale_rgb.release();
+	e->rings.release();
 	if (e->ev_pic_done) (void)hipEventDestroy(e->ev_pic_done);
 	if (e->ev_own_done) (void)hipEventDestroy(e->ev_own_done);
 	if (e->d_batch) (void)hipFree(e->d_batch);

@@ -2,11 +2,15 @@
 // Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture); RGB pictures (8-bit packed or planar, binary16, binary32) -> the same planes, colour
 // converted in the same pass (rgb_yuv.h); Y'CbCr pictures of 8 .. 16 bits in 4:2:0, 4:2:2 or 4:4:4, planar, semi-planar or packed -> the same planes, rounded to 8-bit 4:2:0 in the same pass (yuv_depth.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h); RGB pictures of a larger size -> the same planes, converted and area-averaged in the same pass.  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
 // squared differences against the int16 source planes of a picture slot; the final pictures or the slots' pictures -> RGB pictures in any of the ingest's forms, colour
-// converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  A launch reads its pictures from a job table; JobRing holds the tables of one encoder and
-// run_jobs queues one launch, ordered against the caller's stream by events (k_encode_picture_io.inc and the host-memory entries of k_encode_object.inc use it).
+// converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  SSIM: the exact window sums between a final picture and a slot (ssim_window.h).
+// What the file holds, in its order: the eight job structs (one picture of a launch each; the kernels read a table of them); hmr_picture_launch, which finds kernel and
+// grid size by the job type; one builder per job type (descriptors, planes, strides and sizes in, a job out - no encoder); JobRing, the tables of one job type that one
+// encoder has in flight, and PictureRings, its eight rings; run_jobs, which queues one launch ordered against the caller's stream by events (k_encode_picture_io.inc and
+// the host-memory entries of k_encode_object.inc use it).  The host-only part of the module - builders, descriptor checks, host twins, metrics - is picture_host.cpp.
 #pragma once
 #include <algorithm>
 #include <functional>
+#include <tuple>
 #include <vector>
 #include "common.h"
 #include "rgb_yuv.h"
@@ -121,73 +125,51 @@ struct SsimJob {
 };
 static_assert(sizeof(SsimJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
-// Algorithmic bytes of one width x height picture through k_ssim (tools/ssim_bench.py restates it): the int16 planes of both pictures are read once.
-static inline double hmr_ssim_bytes(int width, int height) { return 6.0 * (double)width * height; }
+// The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of the job
+// type's kernel - k_ingest / k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_egress / k_egress_rgb / k_ssim - handles all n pictures; both on `stream`,
+// nothing is waited for.  Instantiated in picture_io.hip for the eight job types (PictureKernel there names each type's kernel and grid size).
+template <class Job>
+int hmr_picture_launch(hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n);
 
-// Algorithmic bytes of one picture through k_downscale (tools/scale_ingest_bench.py restates it): every sample of the source is read once, the int16 Y, U, V
-// planes of the destination are written.
-static inline double hmr_scale_bytes(int src_w, int src_h, int dst_w, int dst_h) { return 1.5 * (double)src_w * src_h + 3.0 * (double)dst_w * dst_h; }
-
-// Algorithmic bytes of one picture through k_rgb_ladder (tools/rgb_scale_ingest_bench.py restates it): the luma tiles and the chroma tiles each read the RGB
-// source - twice its 3, 4, 3, 6 or 12 Ws Hs bytes - and the int16 Y, U, V planes of the destination are written.
-static inline double hmr_rgb_scale_bytes(int src_w, int src_h, int dst_w, int dst_h, int format, int pixel_bytes)
+// ---- the job of one picture, one builder per job type (picture_host.cpp; the two scale jobs next to scale_tile in picture_io.hip) ----
+// The descriptors have passed their checks.  `dst` and every other int16 plane pointer is the plane at sample (0, 0), with its strides in elements.
+// what the five ingest-side jobs begin with: the caller's planes and pitches, the int16 planes and their strides
+template <class Job, class Picture>
+void hmr_job_planes(Job &j, const Picture &pic, int16_t *const dst[3], int stride_y, int stride_c)
 {
-	const double per_pixel = format == HMR_GPU_RGB_PACKED8 ? pixel_bytes : format == HMR_GPU_RGB_PLANAR8 ? 3 : format == HMR_GPU_RGB_PLANAR_F16 ? 6 : 12;
-	return 2.0 * per_pixel * (double)src_w * src_h + 3.0 * (double)dst_w * dst_h;
+	for (int c = 0; c < 3; c++) {
+		j.src[c] = (const uint8_t *)pic.plane[c];
+		j.pitch[c] = pic.pitch[c];
+		j.dst[c] = dst[c];
+	}
+	j.stride_y = stride_y; j.stride_c = stride_c;
 }
-
-// Algorithmic bytes of one width x height picture through k_ingest_rgb (tools/rgb_ingest_bench.py restates it): every sample of the source is read once -
-// 3 or 4 bytes per pixel packed, 3 planar 8-bit, 6 planar binary16, 12 planar binary32 - and the int16 Y, U, V planes are written: 4 W H in every case.
-static inline double hmr_ingest_rgb_bytes(int width, int height, int format, int pixel_bytes)
+// an RGB source (RgbIngestJob, RgbScaleJob): the planes, and how a pixel is read and converted
+template <class Job>
+void hmr_rgb_source(Job &j, const hmr_gpu_rgb_picture &pic, int16_t *const dst[3], int stride_y, int stride_c)
 {
-	const double wh = (double)width * height;
-	const double read = format == HMR_GPU_RGB_PACKED8 ? pixel_bytes : format == HMR_GPU_RGB_PLANAR8 ? 3 : format == HMR_GPU_RGB_PLANAR_F16 ? 6 : 12;
-	return (read + 4.0) * wh;
+	hmr_job_planes(j, pic, dst, stride_y, stride_c);
+	for (int c = 0; c < 3; c++) j.offset[c] = pic.offset[c];
+	j.format = pic.format; j.pixel_bytes = pic.pixel_bytes;
+	j.m = hmr_rgb_matrix(pic.matrix, pic.full_range);
 }
-
-// Algorithmic bytes of one width x height picture through k_ingest_yuv (tools/yuv_ingest_bench.py restates it): every sample of the source is read once - sb
-// bytes each, W H luma and 2 Wc Hc chroma samples (chroma: HMR_GPU_CHROMA_420 / _422 / _444 = 0 / 1 / 2) - and the int16 Y, U, V planes are written: 3 W H.
-static inline double hmr_ingest_yuv_bytes(int width, int height, int chroma, int bits)
-{
-	const double wh = (double)width * height, sb = bits > 8 ? 2.0 : 1.0;
-	return sb * wh * (chroma == 0 ? 1.5 : chroma == 1 ? 2.0 : 3.0) + 3.0 * wh;
-}
-
-// Algorithmic bytes of one width x height picture through k_egress (tools/egress_bench.py restates it): the final picture is read, the slot's picture is read
-// when sums are asked for, the 8-bit picture is written when one is asked for.
-static inline double hmr_egress_bytes(int width, int height, int picture, int sums)
-{
-	const double wh = (double)width * height;
-	return 3.0 * wh + (sums ? 3.0 * wh : 0.0) + (picture ? 1.5 * wh : 0.0);
-}
-
-// Bytes of a row of `width` pixels of an RGB picture, per pixel: 3 or 4 packed, 3 planar 8-bit, 6 planar binary16, 12 planar binary32
-static inline double hmr_rgb_pixel_bytes(int format, int pixel_bytes)
-{
-	return format == HMR_GPU_RGB_PACKED8 ? pixel_bytes : format == HMR_GPU_RGB_PLANAR8 ? 3 : format == HMR_GPU_RGB_PLANAR_F16 ? 6 : 12;
-}
-// Algorithmic bytes of one width x height picture through k_egress_rgb (tools/rgb_egress_bench.py restates it): the int16 planes are read (3 W H), the reference
-// picture is read when sums are asked for (ref_format >= 0), the RGB picture is written when one is asked for (format >= 0).
-static inline double hmr_egress_rgb_bytes(int width, int height, int format, int pixel_bytes, int ref_format, int ref_pixel_bytes)
-{
-	const double wh = (double)width * height;
-	return (3.0 + (format >= 0 ? hmr_rgb_pixel_bytes(format, pixel_bytes) : 0.0) + (ref_format >= 0 ? hmr_rgb_pixel_bytes(ref_format, ref_pixel_bytes) : 0.0)) * wh;
-}
-
-// The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of k_ingest /
-// k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_egress / k_egress_rgb / k_ssim handles all n pictures; both on `stream`, nothing is waited for.
-int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n);
-int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n);
-int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n);
-int hmr_ingest_yuv_launch(hipStream_t stream, const YuvIngestJob *h_jobs, YuvIngestJob *d_jobs, int n);
-int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n);
-int hmr_rgb_scale_launch(hipStream_t stream, const RgbScaleJob *h_jobs, RgbScaleJob *d_jobs, int n);
-int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n);
-int hmr_egress_rgb_launch(hipStream_t stream, const RgbEgressJob *h_jobs, RgbEgressJob *d_jobs, int n);
-// the job of one picture: the sizes have passed hmr_gpu_scale_check; the ratios, their reciprocals and the tile height are derived here
+// k_ingest: the 8-bit width x height picture `pic` into the planes `dst`
+IngestJob hmr_ingest_job(const hmr_gpu_picture &pic, int16_t *const dst[3], int stride_y, int stride_c, int width, int height);
+// k_ingest_rgb, k_ingest_yuv: the same for an RGB picture and for a Y'CbCr picture of any depth and chroma format
+RgbIngestJob hmr_rgb_ingest_job(const hmr_gpu_rgb_picture &pic, int16_t *const dst[3], int stride_y, int stride_c, int width, int height);
+YuvIngestJob hmr_yuv_ingest_job(const hmr_gpu_yuv_picture &pic, int16_t *const dst[3], int stride_y, int stride_c, int width, int height);
+// k_downscale: the sizes have passed hmr_gpu_scale_check; the ratios, their reciprocals and the tile height are derived here
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
-// the same for an RGB source: the descriptor has passed hmr_gpu_rgb_picture_check for the source's size
+// k_rgb_ladder: the same for an RGB source, whose descriptor has passed hmr_gpu_rgb_picture_check for the source's size
 RgbScaleJob hmr_rgb_scale_job(const hmr_gpu_rgb_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
+// k_egress: the planes `rec` (a final picture, a picture slot) into `pic` (NULL: no picture), the sums of their squared differences against the planes `src` of a
+// picture slot (NULL: none) into ssd
+EgressJob hmr_egress_job(int16_t *const rec[3], int stride_y, int stride_c, const hmr_gpu_picture *pic, int16_t *const src[3], int src_stride_y, int src_stride_c, uint64_t *ssd,
+			 int width, int height);
+// k_egress_rgb: the planes `yuv` into `out` (NULL: no picture), the sums of squared differences against `ref` (NULL: none) into ssd; one of the two is given
+RgbEgressJob hmr_rgb_egress_job(int16_t *const yuv[3], int stride_y, int stride_c, const hmr_gpu_rgb_picture *out, const hmr_gpu_rgb_picture *ref, uint64_t *ssd, int width, int height);
+// k_ssim: the window sums between the planes a (a picture slot) and b (a final picture) into sum
+SsimJob hmr_ssim_job(int16_t *const a[3], int stride_a_y, int stride_a_c, int16_t *const b[3], int stride_b_y, int stride_b_c, int64_t *sum, int width, int height);
 
 // The job tables of the calls one encoder leads, in one direction: a ring of tables in page-locked memory (a table is written again only when the launch that read it
 // is known to be over: ev_turn), their copy on the device, the events towards the outside stream (producer or consumer) and towards the streams that go on behind a launch.
@@ -236,12 +218,22 @@ struct JobRing {
 	}
 };
 
-// One launch (hmr_ingest_launch / hmr_egress_launch) over n jobs on `st`, behind what the `outside` stream holds now and behind whatever `before` queues (it may add to
-// `behind`); every distinct stream of `behind` goes on behind the launch.  The host waits for nothing but the ring's turn.
+// The rings of one encoder, one per job type (a table is reused after PICTURE_RING calls of ITS kind): a new kernel adds its job type here and nowhere else.
+struct PictureRings {
+	std::tuple<JobRing<IngestJob>, JobRing<RgbIngestJob>, JobRing<YuvIngestJob>, JobRing<ScaleJob>, JobRing<RgbScaleJob>, JobRing<EgressJob>, JobRing<RgbEgressJob>, JobRing<SsimJob>> of;
+	void release()
+	{
+		std::apply([](auto &...ring) { (ring.release(), ...); }, of);
+	}
+};
+
+// One launch (hmr_picture_launch) over n jobs on `st`, with the ring of the job's type, behind what the `outside` stream holds now and behind whatever `before` queues
+// (it may add to `behind`); every distinct stream of `behind` goes on behind the launch.  The host waits for nothing but the ring's turn.
 template <class Job>
-int run_jobs(JobRing<Job> &ring, int (*launch)(hipStream_t, const Job *, Job *, int), hipStream_t st, const Job *jobs, int n, hipStream_t outside,
-	     std::vector<hipStream_t> behind = {}, const std::function<int(std::vector<hipStream_t> &)> &before = nullptr)
+int run_jobs(PictureRings &rings, hipStream_t st, const Job *jobs, int n, hipStream_t outside, std::vector<hipStream_t> behind = {},
+	     const std::function<int(std::vector<hipStream_t> &)> &before = nullptr)
 {
+	JobRing<Job> &ring = std::get<JobRing<Job>>(rings.of);
 	int rc = ring.prepare(n, st);
 	if (rc) return rc;
 	Job *table;
@@ -253,7 +245,7 @@ int run_jobs(JobRing<Job> &ring, int (*launch)(hipStream_t, const Job *, Job *, 
 		HIP_TRY(hipStreamWaitEvent(st, ring.ev_outside, 0));
 	}
 	if (before && (rc = before(behind))) return rc;
-	if ((rc = launch(st, table, ring.d, n))) return rc;
+	if ((rc = hmr_picture_launch(st, table, ring.d, n))) return rc;
 	HIP_TRY(hipEventRecord(turn, st));
 	std::sort(behind.begin(), behind.end());
 	behind.erase(std::unique(behind.begin(), behind.end()), behind.end());

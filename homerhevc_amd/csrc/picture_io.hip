@@ -1,16 +1,17 @@
-// Picture conversion on the device (include/homer_gpu.h sections 12d and 12e): 8-bit 4:2:0 pictures in device memory - I420 planes or NV12, any base address, any
-// pitch - to and from the int16 planes of the frame encoder (sample (x, y) at y * stride + x).  ONE launch for a batch of pictures in either direction; neither has
-// arithmetic to speak of, both are bound by HBM.
+// Picture conversion on the device (include/homer_gpu.h sections 12d .. 12k): pictures in device memory - any base address, any pitch - to and from the int16 planes of
+// the frame encoder (sample (x, y) at y * stride + x), and quality sums between such planes.  ONE launch for a batch of pictures; k_ingest and k_egress have no
+// arithmetic to speak of and are bound by HBM.  The file holds the nine kernels, behind each the PictureKernel<Job> that names it and its grid size for
+// hmr_picture_launch, the launch itself and the two scale job builders (they need scale_tile); everything else on the host is picture_host.cpp.
 //
 // k_ingest: 8-bit pictures into int16 planes - the source planes of a picture slot, or a reference picture: sample (x, y) at y * stride + x, nothing outside
 // width x height touched.  1.5 W H bytes read, 3 W H written per picture.
 // k_egress: the frame encoder's final pictures (int16 planes with margins) into 8-bit pictures, and / or the exact sums of squared differences of each plane against the
 // int16 source planes of a picture slot.  Per picture 3 W H bytes read (final picture), 3 W H read (slot, when sums are asked for), 1.5 W H written (when a picture is
-// asked for) - hmr_egress_bytes in picture_io.h.
+// asked for).
 //
 // k_ingest_rgb (section 12f): RGB pictures - packed 8-bit with 3 or 4 bytes per pixel and any channel order, planar 8-bit, planar binary16, planar binary32 - into the same
 // int16 planes, converted to 4:2:0 Y'CbCr by the integer arithmetic of rgb_yuv.h in the same pass.  3, 4, 3, 6 or 12 W H bytes read, 4 W H written per picture
-// (hmr_ingest_rgb_bytes in picture_io.h).  blockIdx.y = picture, blockIdx.x = a chunk of CHUNK_ROWS luma rows = CHUNK_ROWS / 2 chroma rows; a lane takes a span of 16
+//.  blockIdx.y = picture, blockIdx.x = a chunk of CHUNK_ROWS luma rows = CHUNK_ROWS / 2 chroma rows; a lane takes a span of 16
 // pixels of TWO adjacent rows, so the 2 x 2 sums of the chroma samples never leave the lane: 16-byte loads at whatever address the pitch gives (per row: three for
 // 3-byte pixels, four for 4-byte pixels, one per plane for planar 8-bit, two / four per plane for binary16 / binary32), channels picked by v_alignbyte_b32 / v_bfe_u32 with
 // the job's byte offsets, four 16-byte stores of int16 luma and one each of eight U and eight V samples.  A row's tail of fewer than 16 pixels goes sample by sample, a lane per 2 x 2 block.
@@ -39,6 +40,9 @@
 #include "picture_io.h"
 
 namespace {
+// A job type's kernel and the grid's x size one of its jobs needs: specialised right behind each kernel, read by hmr_picture_launch.
+template <class Job> struct PictureKernel;
+
 constexpr int CHUNK_ROWS = 8;
 static_assert((uint64_t)CHUNK_ROWS * EGRESS_MAX_WIDTH * 255 * 255 < (1ull << 32), "a workgroup's partial sum of one plane fits 32 bits");
 
@@ -155,21 +159,9 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ingest(const IngestJob *jobs)
 		widen_span((is_v ? sv : su) + (int64_t)y * (is_v ? pv : pu) + x, (is_v ? dv : du) + (size_t)y * stride + x, cw - x < 16 ? cw - x : 16);
 	}
 }
+template <> struct PictureKernel<IngestJob> { static constexpr auto kernel = k_ingest; static int chunks(const IngestJob &j) { return Chunk{0, j.width, j.height}.chunks(); } };
 
 // ---- RGB ingest ----
-// a sample of an RGB picture as 8 bits: `plane` is the packed plane or the channel's own; host and device pointers alike (hmr_gpu_rgb_convert_host, a row's tail)
-template <class Bytes, class Halves, class Floats>
-__host__ __device__ __forceinline__ int rgb_sample(Bytes plane, int64_t pitch, int format, int pixel_bytes, int offset, int x, int y)
-{
-	const Bytes row = plane + (int64_t)y * pitch;
-	switch (format) {
-	case HMR_GPU_RGB_PACKED8: return row[x * pixel_bytes + offset];
-	case HMR_GPU_RGB_PLANAR8: return row[x];
-	case HMR_GPU_RGB_PLANAR_F16: return hmr_rgb_quantize((float)((Halves)row)[x]);
-	default: return hmr_rgb_quantize(((Floats)row)[x]);
-	}
-}
-
 // The forms a span is read in (a launch mixes them: one per picture).  PX pixels of a row are held as raw dwords: packed - the row's bytes as they lie; planar - PX
 // samples of R, then of G, then of B.
 enum { RGB_PACKED3, RGB_PACKED4, RGB_PLANAR8, RGB_F16, RGB_F32 };
@@ -350,11 +342,12 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ingest_rgb(const RgbIngestJob *jo
 	default: rgb_chunk<RGB_F32, HMR_GPU_RGB_PLANAR_F32>(j, y0); break;
 	}
 }
+template <> struct PictureKernel<RgbIngestJob> { static constexpr auto kernel = k_ingest_rgb; static int chunks(const RgbIngestJob &j) { return rgb_chunks(j.height); } };
 
 // ---- deep / 4:2:2 / 4:4:4 ingest (section 12k) ----
 // k_ingest_yuv: Y'CbCr pictures of 8 .. 16 bits - 4:2:0, 4:2:2 or 4:4:4; planar, semi-planar in either order, or packed 4:2:2 in any of its four orders - into the int16
 // planes of a slot, rounded to 8-bit 4:2:0 by the integer arithmetic of yuv_depth.h in the same pass.  sb (W H + 2 Wc Hc) bytes read, 3 W H written per picture
-// (hmr_ingest_yuv_bytes in picture_io.h).  The mapping is k_ingest_rgb's: blockIdx.y = picture, blockIdx.x = a chunk of CHUNK_ROWS luma rows; a lane takes a span of 16
+//.  The mapping is k_ingest_rgb's: blockIdx.y = picture, blockIdx.x = a chunk of CHUNK_ROWS luma rows; a lane takes a span of 16
 // pixels of TWO adjacent luma rows and every chroma sample that lies over them, so the 1, 2 or 4 taps of a chroma output never leave the lane and a packed picture's
 // bytes are read once for luma and chroma.  Per lane: the luma rows' bytes by 16-byte loads at whatever address the pitch gives (one a row for 8-bit planes, two for
 // 16-bit planes or 8-bit packed, four for 16-bit packed); the chroma rows' (one row for 4:2:0, two otherwise; 8 columns, 16 for 4:4:4; ONE 8-byte load where a row's
@@ -534,10 +527,11 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ingest_yuv(const YuvIngestJob *jo
 		break;
 	}
 }
+template <> struct PictureKernel<YuvIngestJob> { static constexpr auto kernel = k_ingest_yuv; static int chunks(const YuvIngestJob &j) { return rgb_chunks(j.height); } };
 
 // ---- downscaling ingest (section 12g) ----
 // k_downscale: 8-bit pictures of one size, area-averaged (scale_area.h) into the int16 planes of a smaller - or equal - size.  1.5 Ws Hs bytes read, 3 Wd Hd written per
-// picture (hmr_scale_bytes in picture_io.h).  blockIdx.y = picture; blockIdx.x = a tile of tile_rows output rows x SCALE_TILE_W output columns of one plane class - the
+// picture.  blockIdx.y = picture; blockIdx.x = a tile of tile_rows output rows x SCALE_TILE_W output columns of one plane class - the
 // luma tiles first, then the chroma tiles (a chroma tile holds SCALE_TILE_W / 2 columns of U and as many of V, so that NV12's pairs are read once); smaller pictures
 // leave their last blocks empty.  Vertical pass first: a lane takes a span of 16 bytes of the source columns the tile covers and ONE output row, walks that row's source
 // rows (at most nine) with 16-byte loads at whatever address the pitch gives and keeps the sixteen weighted column sums in 32-bit registers; they go to LDS, a span in
@@ -677,6 +671,7 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_downscale(const ScaleJob *jobs)
 
 	scale_finish(k, ax, j.den, j.mden, sums, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
 }
+template <> struct PictureKernel<ScaleJob> { static constexpr auto kernel = k_downscale; static int chunks(const ScaleJob &j) { return scale_tiles(j); } };
 
 // ---- downscaling RGB ingest (section 12j) ----
 // k_rgb_ladder: RGB pictures of one size, in any of k_ingest_rgb's forms, into the int16 planes of a smaller - or equal - size: every slot sample is section 12g's
@@ -689,7 +684,7 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_downscale(const ScaleJob *jobs)
 // accumulates U and V apart; its sixteen sums are half a span of the U stream and half a span of the V stream (two 16-byte LDS stores each: eight lanes of such a
 // store hit six different quads of banks, two of them twice).  Sixteen chroma columns a lane would hold 32 sums beside two rows of 32 pixels: eight keeps every form
 // free of spills.  A span that reaches past the end of a row goes sample by sample (rgb_sample), every sample checked against the width.
-// Luma and chroma tiles each read the RGB source: 2 x (3, 4, 3, 6 or 12) Ws Hs bytes read, 3 Wd Hd written per picture (hmr_rgb_scale_bytes in picture_io.h).  No lane
+// Luma and chroma tiles each read the RGB source: 2 x (3, 4, 3, 6 or 12) Ws Hs bytes read, 3 Wd Hd written per picture.  No lane
 // reads a byte outside [plane + y * pitch, plane + y * pitch + row bytes) or writes outside dst_w x dst_h.  The weighted sums fit 32 bits as section 12g's do: the
 // converted samples are 8-bit.  LDS: k_downscale's.
 template <int FMT>
@@ -845,6 +840,7 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_rgb_ladder(const RgbScaleJob *job
 	__syncthreads();
 	scale_finish(k, j.ax, j.den, j.mden, (const uint32_t *)sums4, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
 }
+template <> struct PictureKernel<RgbScaleJob> { static constexpr auto kernel = k_rgb_ladder; static int chunks(const RgbScaleJob &j) { return scale_tiles(j); } };
 
 // ---- egress ----
 // two dwords of two int16 samples each -> their four low bytes
@@ -966,11 +962,12 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_egress(const EgressJob *jobs)
 	}
 	if (sums) add_sums(ssd + 1, acc_u, acc_v, true);
 }
+template <> struct PictureKernel<EgressJob> { static constexpr auto kernel = k_egress; static int chunks(const EgressJob &j) { return Chunk{0, j.width, j.height}.chunks(); } };
 
 // ---- RGB egress (section 12i) ----
 // k_egress_rgb: int16 planes - a final picture (with margins) or a picture slot (without: every chroma index is clamped here) - into RGB pictures in any of the ingest's
 // forms by the integer arithmetic of yuv_rgb.h, and / or the exact sums of squared differences between the 8-bit R, G, B values and a reference RGB picture in any form.
-// 3 W H bytes read, the reference's 3, 4, 3, 6 or 12 W H read, 3, 4, 3, 6 or 12 W H written per picture (hmr_egress_rgb_bytes in picture_io.h).
+// 3 W H bytes read, the reference's 3, 4, 3, 6 or 12 W H read, 3, 4, 3, 6 or 12 W H written per picture.
 // blockIdx.y = picture, blockIdx.x = a chunk of RGB_PAIRS row pairs; pair p is the luma rows 2 p - 1 and 2 p, which both take their chroma from rows p - 1 and p (the
 // pairs 0 and H / 2 have one row, and one chroma row twice: the clamp): H / 2 + 1 pairs, at most CHUNK_ROWS luma rows a chunk.  A lane takes a span of 16 pixels of a
 // pair: one aligned 16-byte load of eight samples per chroma row and plane plus the two neighbour columns (clamped; they are another lane's span: served from cache),
@@ -982,21 +979,6 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_egress(const EgressJob *jobs)
 // pixels, each difference at most 255: the bound at the top of the file.
 constexpr int RGB_PAIRS = CHUNK_ROWS / 2;
 __host__ __device__ __forceinline__ int rgb_egress_chunks(int height) { return ((height >> 1) + 1 + RGB_PAIRS - 1) / RGB_PAIRS; }
-
-// a sample of an RGB picture written as 8 bits' worth: host and device pointers alike (hmr_gpu_rgb_from_yuv_host, a row's tail)
-template <class Bytes, class Halves, class Floats>
-__host__ __device__ __forceinline__ void rgb_put(Bytes plane, int64_t pitch, int format, int pixel_bytes, int offset, int x, int y, int v)
-{
-	const Bytes row = plane + (int64_t)y * pitch;
-	switch (format) {
-	case HMR_GPU_RGB_PACKED8: row[x * pixel_bytes + offset] = (uint8_t)v; break;
-	case HMR_GPU_RGB_PLANAR8: row[x] = (uint8_t)v; break;
-	case HMR_GPU_RGB_PLANAR_F16: ((Halves)row)[x] = (_Float16)hmr_rgb_unit(v); break;
-	default: ((Floats)row)[x] = hmr_rgb_unit(v); break;
-	}
-}
-// the byte of a 4-byte pixel that holds no channel
-__host__ __device__ __forceinline__ int rgb_alpha_offset(const int32_t offset[3]) { return 6 - offset[0] - offset[1] - offset[2]; }
 
 __device__ __forceinline__ uint32_t byte_of(const uint32_t *p, int i) { return (p[i >> 2] >> (8 * (i & 3))) & 255u; }
 
@@ -1214,10 +1196,11 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_egress_rgb(const RgbEgressJob *jo
 	__syncthreads();      // (add_sums' partial sums are read by two lanes while the other wavefronts go on)
 	add_sums(ssd + 2, acc_b, 0, false);
 }
+template <> struct PictureKernel<RgbEgressJob> { static constexpr auto kernel = k_egress_rgb; static int chunks(const RgbEgressJob &j) { return rgb_egress_chunks(j.height); } };
 
 // ---- SSIM (section 12h) ----
 // k_ssim: the exact sums of ssim_window.h's fixed-point SSIM values over every window of every plane, between the int16 planes of a picture slot (a) and the final
-// picture's (b).  Both pictures are read, 6 W H bytes per picture (hmr_ssim_bytes in picture_io.h); nothing is written but three 64-bit sums.  blockIdx.y = picture;
+// picture's (b).  Both pictures are read, 6 W H bytes per picture; nothing is written but three 64-bit sums.  blockIdx.y = picture;
 // blockIdx.x = a tile of SSIM_TW x SSIM_TH windows of one plane, row by row - the luma tiles first, then U's, then V's; smaller pictures leave their last blocks empty.
 // A tile of 32 x 8 windows needs 33 x 9 blocks of 4 x 4 samples.
 // Stage 1, a lane per (block row, 16-byte span): tiles start at even block columns, so a span of 8 samples is two adjacent blocks and is 16-byte aligned in both
@@ -1319,6 +1302,7 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ssim(const SsimJob *jobs)
 		if (total) __hip_atomic_fetch_add((GLOBAL_AS uint64_t *)j.sum + k.plane, (uint64_t)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
 }
+template <> struct PictureKernel<SsimJob> { static constexpr auto kernel = k_ssim; static int chunks(const SsimJob &j) { return ssim_tiles(j.width, j.height); } };
 
 // ---- launches ----
 // a job table from page-locked host memory to the device by a kernel, `words` 32-bit words per job: a host-to-device copy would queue on the copy engines behind a
@@ -1327,38 +1311,23 @@ __global__ __launch_bounds__(64) void k_picture_jobs(const uint32_t *h_jobs, uin
 {
 	for (int k = threadIdx.x; k < words; k += blockDim.x) d_jobs[blockIdx.x * words + k] = h_jobs[blockIdx.x * words + k];
 }
-
-inline int chunks_of(const IngestJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
-inline int chunks_of(const EgressJob &j) { return Chunk{0, j.width, j.height}.chunks(); }
-inline int chunks_of(const RgbIngestJob &j) { return rgb_chunks(j.height); }
-inline int chunks_of(const YuvIngestJob &j) { return rgb_chunks(j.height); }
-inline int chunks_of(const ScaleJob &j) { return scale_tiles(j); }
-inline int chunks_of(const RgbScaleJob &j) { return scale_tiles(j); }
-inline int chunks_of(const SsimJob &j) { return ssim_tiles(j.width, j.height); }
-inline int chunks_of(const RgbEgressJob &j) { return rgb_egress_chunks(j.height); }
+}  // namespace
 
 template <class Job>
-int launch(void (*kernel)(const Job *), hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n)
+int hmr_picture_launch(hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n)
 {
 	static_assert(sizeof(Job) % 4 == 0, "word copies");
 	if (!h_jobs || !d_jobs || n < 1 || n > PICTURE_MAX_JOBS) return HMR_GPU_ERR_ARG;
 	int chunks = 0;      // of the tallest picture
-	for (int i = 0; i < n; i++) chunks = std::max(chunks, chunks_of(h_jobs[i]));
+	for (int i = 0; i < n; i++) chunks = std::max(chunks, PictureKernel<Job>::chunks(h_jobs[i]));
 	hipLaunchKernelGGL(k_picture_jobs, dim3(n), dim3(64), 0, stream, (const uint32_t *)h_jobs, (uint32_t *)d_jobs, (int)(sizeof(Job) / 4));
-	hipLaunchKernelGGL(kernel, dim3(chunks, n), dim3(HMR_BLOCK), 0, stream, (const Job *)d_jobs);
+	hipLaunchKernelGGL(PictureKernel<Job>::kernel, dim3(chunks, n), dim3(HMR_BLOCK), 0, stream, (const Job *)d_jobs);
 	HIP_TRY(hipGetLastError());
 	return HMR_GPU_OK;
 }
-}  // namespace
-
-int hmr_ingest_launch(hipStream_t stream, const IngestJob *h_jobs, IngestJob *d_jobs, int n) { return launch(k_ingest, stream, h_jobs, d_jobs, n); }
-int hmr_egress_launch(hipStream_t stream, const EgressJob *h_jobs, EgressJob *d_jobs, int n) { return launch(k_egress, stream, h_jobs, d_jobs, n); }
-int hmr_ingest_rgb_launch(hipStream_t stream, const RgbIngestJob *h_jobs, RgbIngestJob *d_jobs, int n) { return launch(k_ingest_rgb, stream, h_jobs, d_jobs, n); }
-int hmr_ingest_yuv_launch(hipStream_t stream, const YuvIngestJob *h_jobs, YuvIngestJob *d_jobs, int n) { return launch(k_ingest_yuv, stream, h_jobs, d_jobs, n); }
-int hmr_scale_launch(hipStream_t stream, const ScaleJob *h_jobs, ScaleJob *d_jobs, int n) { return launch(k_downscale, stream, h_jobs, d_jobs, n); }
-int hmr_rgb_scale_launch(hipStream_t stream, const RgbScaleJob *h_jobs, RgbScaleJob *d_jobs, int n) { return launch(k_rgb_ladder, stream, h_jobs, d_jobs, n); }
-int hmr_ssim_launch(hipStream_t stream, const SsimJob *h_jobs, SsimJob *d_jobs, int n) { return launch(k_ssim, stream, h_jobs, d_jobs, n); }
-int hmr_egress_rgb_launch(hipStream_t stream, const RgbEgressJob *h_jobs, RgbEgressJob *d_jobs, int n) { return launch(k_egress_rgb, stream, h_jobs, d_jobs, n); }
+#define HMR_PICTURE_LAUNCH(Job) template int hmr_picture_launch<Job>(hipStream_t, const Job *, Job *, int);
+HMR_PICTURE_LAUNCH(IngestJob) HMR_PICTURE_LAUNCH(RgbIngestJob) HMR_PICTURE_LAUNCH(YuvIngestJob) HMR_PICTURE_LAUNCH(ScaleJob)
+HMR_PICTURE_LAUNCH(RgbScaleJob) HMR_PICTURE_LAUNCH(EgressJob) HMR_PICTURE_LAUNCH(RgbEgressJob) HMR_PICTURE_LAUNCH(SsimJob)
 
 // The output rows of a job's tiles: the widest tile row of the picture, in spans (it does not depend on the tile's rows; at most SCALE_MAX_SPANS at the ratios
 // hmr_gpu_scale_check lets through), and the rows the LDS then holds.  The job's sizes and ratios are set.
@@ -1377,12 +1346,7 @@ ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t
 {
 	ScaleJob j;
 	memset(&j, 0, sizeof j);
-	for (int c = 0; c < 3; c++) {
-		j.src[c] = pic.plane[c];
-		j.pitch[c] = pic.pitch[c];
-		j.dst[c] = dst[c];
-	}
-	j.stride_y = stride_y; j.stride_c = stride_c;
+	hmr_job_planes(j, pic, dst, stride_y, stride_c);
 	j.src_w = src_w; j.src_h = src_h; j.dst_w = dst_w; j.dst_h = dst_h;
 	j.format = pic.format;
 	j.ax = hmr_scale_axis(src_w, dst_w); j.ay = hmr_scale_axis(src_h, dst_h);
@@ -1395,431 +1359,10 @@ RgbScaleJob hmr_rgb_scale_job(const hmr_gpu_rgb_picture &pic, int src_w, int src
 {
 	RgbScaleJob j;
 	memset(&j, 0, sizeof j);
-	for (int c = 0; c < 3; c++) {
-		j.src[c] = (const uint8_t *)pic.plane[c];
-		j.pitch[c] = pic.pitch[c];
-		j.dst[c] = dst[c];
-		j.offset[c] = pic.offset[c];
-	}
-	j.stride_y = stride_y; j.stride_c = stride_c;
+	hmr_rgb_source(j, pic, dst, stride_y, stride_c);
 	j.src_w = src_w; j.src_h = src_h; j.dst_w = dst_w; j.dst_h = dst_h;
-	j.format = pic.format; j.pixel_bytes = pic.pixel_bytes;
-	j.m = hmr_rgb_matrix(pic.matrix, pic.full_range);
 	j.ax = hmr_scale_axis(src_w, dst_w); j.ay = hmr_scale_axis(src_h, dst_h);
 	j.den = j.ax.s * j.ay.s; j.mden = hmr_scale_magic(j.den);
 	j.tile_rows = scale_tile_rows(j, false);
 	return j;
-}
-
-static int refuse(const char *what)
-{
-	hmr_set_error("hmr_gpu_picture: %s", what);
-	return HMR_GPU_ERR_ARG;
-}
-// a descriptor against a picture size, on the host alone
-extern "C" int hmr_gpu_picture_check(const hmr_gpu_picture *pic, int width, int height)
-{
-	if (!pic) return refuse("the descriptor is NULL");
-	if (pic->format != HMR_GPU_PIC_I420 && pic->format != HMR_GPU_PIC_NV12) return refuse("format: neither HMR_GPU_PIC_I420 nor HMR_GPU_PIC_NV12");
-	if (pic->reserved != 0) return refuse("reserved: must be 0");
-	if (width <= 0 || (width & 1)) return refuse("width: must be positive and even");
-	if (height <= 0 || (height & 1)) return refuse("height: must be positive and even");
-	const int planes = pic->format == HMR_GPU_PIC_NV12 ? 2 : 3;
-	static const char *const missing[3] = {"plane[0]: NULL", "plane[1]: NULL", "plane[2]: NULL"};
-	static const char *const negative[3] = {"pitch[0]: negative", "pitch[1]: negative", "pitch[2]: negative"};
-	static const char *const narrow[3] = {"pitch[0]: less than a row's bytes (width)", "pitch[1]: less than a row's bytes (I420: width / 2, NV12: width)", "pitch[2]: less than a row's bytes (width / 2)"};
-	for (int c = 0; c < planes; c++) {
-		if (!pic->plane[c]) return refuse(missing[c]);
-		if (pic->pitch[c] < 0) return refuse(negative[c]);
-		const int row_bytes = c == 0 || pic->format == HMR_GPU_PIC_NV12 ? width : width / 2;
-		if (pic->pitch[c] < row_bytes) return refuse(narrow[c]);
-	}
-	if (planes == 2 && pic->plane[2]) return refuse("plane[2]: must be NULL for NV12 (plane[1] holds the U, V pairs)");
-	return HMR_GPU_OK;
-}
-
-static int refuse_rgb(const char *what)
-{
-	hmr_set_error("hmr_gpu_rgb_picture: %s", what);
-	return HMR_GPU_ERR_ARG;
-}
-// an RGB descriptor against a picture size, on the host alone
-extern "C" int hmr_gpu_rgb_picture_check(const hmr_gpu_rgb_picture *pic, int width, int height)
-{
-	if (!pic) return refuse_rgb("the descriptor is NULL");
-	if (pic->format < HMR_GPU_RGB_PACKED8 || pic->format > HMR_GPU_RGB_PLANAR_F32) return refuse_rgb("format: not one of HMR_GPU_RGB_PACKED8, _PLANAR8, _PLANAR_F16, _PLANAR_F32");
-	if (pic->matrix != HMR_GPU_MATRIX_BT601 && pic->matrix != HMR_GPU_MATRIX_BT709) return refuse_rgb("matrix: neither HMR_GPU_MATRIX_BT601 nor HMR_GPU_MATRIX_BT709");
-	if (pic->full_range != 0 && pic->full_range != 1) return refuse_rgb("full_range: must be 0 or 1");
-	if (pic->reserved != 0) return refuse_rgb("reserved: must be 0");
-	if (width <= 0 || (width & 1)) return refuse_rgb("width: must be positive and even");
-	if (height <= 0 || (height & 1)) return refuse_rgb("height: must be positive and even");
-	const bool packed = pic->format == HMR_GPU_RGB_PACKED8;
-	static const char *const offset_range[3] = {"offset[0]: outside 0 .. pixel_bytes - 1", "offset[1]: outside 0 .. pixel_bytes - 1", "offset[2]: outside 0 .. pixel_bytes - 1"};
-	static const char *const offset_zero[3] = {"offset[0]: must be 0 for a planar format", "offset[1]: must be 0 for a planar format", "offset[2]: must be 0 for a planar format"};
-	if (packed) {
-		if (pic->pixel_bytes != 3 && pic->pixel_bytes != 4) return refuse_rgb("pixel_bytes: must be 3 or 4 for HMR_GPU_RGB_PACKED8");
-		for (int c = 0; c < 3; c++)
-			if (pic->offset[c] < 0 || pic->offset[c] >= pic->pixel_bytes) return refuse_rgb(offset_range[c]);
-		if (pic->offset[1] == pic->offset[0]) return refuse_rgb("offset[1]: the same byte as offset[0]");
-		if (pic->offset[2] == pic->offset[0] || pic->offset[2] == pic->offset[1]) return refuse_rgb("offset[2]: the same byte as another channel's");
-	} else {
-		if (pic->pixel_bytes != 0) return refuse_rgb("pixel_bytes: must be 0 for a planar format");
-		for (int c = 0; c < 3; c++)
-			if (pic->offset[c] != 0) return refuse_rgb(offset_zero[c]);
-	}
-	const int elem = packed ? pic->pixel_bytes : pic->format == HMR_GPU_RGB_PLANAR8 ? 1 : pic->format == HMR_GPU_RGB_PLANAR_F16 ? 2 : 4;
-	const int align = packed ? 1 : elem;
-	static const char *const missing[3] = {"plane[0]: NULL", "plane[1]: NULL", "plane[2]: NULL"};
-	static const char *const extra[3] = {"", "plane[1]: must be NULL for HMR_GPU_RGB_PACKED8 (plane[0] holds the pixels)", "plane[2]: must be NULL for HMR_GPU_RGB_PACKED8 (plane[0] holds the pixels)"};
-	static const char *const negative[3] = {"pitch[0]: negative", "pitch[1]: negative", "pitch[2]: negative"};
-	static const char *const narrow[3] = {"pitch[0]: less than a row's bytes (width x pixel_bytes, or width x the element size)", "pitch[1]: less than a row's bytes (width x the element size)",
-					      "pitch[2]: less than a row's bytes (width x the element size)"};
-	static const char *const plane_align[3] = {"plane[0]: not a multiple of the element size", "plane[1]: not a multiple of the element size", "plane[2]: not a multiple of the element size"};
-	static const char *const pitch_align[3] = {"pitch[0]: not a multiple of the element size", "pitch[1]: not a multiple of the element size", "pitch[2]: not a multiple of the element size"};
-	for (int c = 0; c < 3; c++) {
-		if (packed && c) {
-			if (pic->plane[c]) return refuse_rgb(extra[c]);
-			continue;
-		}
-		if (!pic->plane[c]) return refuse_rgb(missing[c]);
-		if (pic->pitch[c] < 0) return refuse_rgb(negative[c]);
-		if (pic->pitch[c] < (int64_t)width * elem) return refuse_rgb(narrow[c]);
-		if ((uintptr_t)pic->plane[c] % align) return refuse_rgb(plane_align[c]);
-		if (pic->pitch[c] % align) return refuse_rgb(pitch_align[c]);
-	}
-	return HMR_GPU_OK;
-}
-
-// rgb_yuv.h's arithmetic over host memory: the loop a caller would write from the header's formulas
-extern "C" int hmr_gpu_rgb_convert_host(const hmr_gpu_rgb_picture *pic, int width, int height, uint8_t *y, uint8_t *u, uint8_t *v)
-{
-	const int rc = hmr_gpu_rgb_picture_check(pic, width, height);
-	if (rc) return rc;
-	if (!y || !u || !v) {
-		hmr_set_error("hmr_gpu_rgb_convert_host: needs the three output planes");
-		return HMR_GPU_ERR_ARG;
-	}
-	const RgbMatrix m = hmr_rgb_matrix(pic->matrix, pic->full_range);
-	const bool packed = pic->format == HMR_GPU_RGB_PACKED8;
-	for (int by = 0; by < height; by += 2)
-		for (int bx = 0; bx < width; bx += 2) {
-			int s[3] = {0, 0, 0};
-			for (int k = 0; k < 4; k++) {
-				const int px = bx + (k & 1), py = by + (k >> 1);
-				int c3[3];
-				for (int c = 0; c < 3; c++) {
-					c3[c] = rgb_sample<const uint8_t *, const _Float16 *, const float *>((const uint8_t *)pic->plane[packed ? 0 : c], pic->pitch[packed ? 0 : c], pic->format, pic->pixel_bytes,
-													      pic->offset[c], px, py);
-					s[c] += c3[c];
-				}
-				y[(size_t)py * width + px] = (uint8_t)hmr_rgb_luma(m, c3[0], c3[1], c3[2]);
-			}
-			const size_t oc = (size_t)(by >> 1) * (width >> 1) + (bx >> 1);
-			u[oc] = (uint8_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
-			v[oc] = (uint8_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
-		}
-	return HMR_GPU_OK;
-}
-
-// ---- section 12k: the host side of the deep / 4:2:2 / 4:4:4 ingest ----
-static_assert(HMR_YUV_PLANAR == HMR_GPU_YUV_PLANAR && HMR_YUV_SEMIPLANAR == HMR_GPU_YUV_SEMIPLANAR && HMR_YUV_PACKED422 == HMR_GPU_YUV_PACKED422, "yuv_depth.h restates the header's formats");
-static int refuse_yuv(const char *what)
-{
-	hmr_set_error("hmr_gpu_yuv_picture: %s", what);
-	return HMR_GPU_ERR_ARG;
-}
-// a Y'CbCr descriptor against a picture size, on the host alone
-extern "C" int hmr_gpu_yuv_picture_check(const hmr_gpu_yuv_picture *pic, int width, int height)
-{
-	if (!pic) return refuse_yuv("the descriptor is NULL");
-	if (pic->format < HMR_GPU_YUV_PLANAR || pic->format > HMR_GPU_YUV_PACKED422) return refuse_yuv("format: not one of HMR_GPU_YUV_PLANAR, _SEMIPLANAR, _PACKED422");
-	if (pic->chroma < HMR_GPU_CHROMA_420 || pic->chroma > HMR_GPU_CHROMA_444) return refuse_yuv("chroma: not one of HMR_GPU_CHROMA_420, _422, _444");
-	if (pic->bits < 8 || pic->bits > 16) return refuse_yuv("bits: outside 8 .. 16");
-	if (pic->msb_aligned != 0 && pic->msb_aligned != 1) return refuse_yuv("msb_aligned: must be 0 or 1");
-	if (pic->msb_aligned && (pic->bits == 8 || pic->bits == 16)) return refuse_yuv("msb_aligned: must be 0 with bits 8 or 16 (the sample fills its container)");
-	if (pic->reserved != 0) return refuse_yuv("reserved: must be 0");
-	if (width <= 0 || (width & 1)) return refuse_yuv("width: must be positive and even");
-	if (height <= 0 || (height & 1)) return refuse_yuv("height: must be positive and even");
-	if (pic->format == HMR_GPU_YUV_PACKED422 && pic->chroma != HMR_GPU_CHROMA_422) return refuse_yuv("chroma: must be HMR_GPU_CHROMA_422 for HMR_GPU_YUV_PACKED422");
-	static const char *const offset_zero[3] = {"offset[0]: must be 0 for this format", "offset[1]: must be 0 for HMR_GPU_YUV_PLANAR", "offset[2]: must be 0 for HMR_GPU_YUV_PLANAR"};
-	if (pic->format == HMR_GPU_YUV_PLANAR) {
-		for (int c = 0; c < 3; c++)
-			if (pic->offset[c] != 0) return refuse_yuv(offset_zero[c]);
-	} else if (pic->format == HMR_GPU_YUV_SEMIPLANAR) {
-		if (pic->offset[0] != 0) return refuse_yuv(offset_zero[0]);
-		if (pic->offset[1] < 0 || pic->offset[1] > 1) return refuse_yuv("offset[1]: outside 0 .. 1 (U's place in a pair)");
-		if (pic->offset[2] < 0 || pic->offset[2] > 1) return refuse_yuv("offset[2]: outside 0 .. 1 (V's place in a pair)");
-		if (pic->offset[2] == pic->offset[1]) return refuse_yuv("offset[2]: the same sample of a pair as offset[1]");
-	} else {
-		if (pic->offset[0] < 0 || pic->offset[0] > 1) return refuse_yuv("offset[0]: outside 0 .. 1 (the first luma sample of a group of four)");
-		if (pic->offset[1] < 0 || pic->offset[1] > 3) return refuse_yuv("offset[1]: outside 0 .. 3");
-		if (pic->offset[2] < 0 || pic->offset[2] > 3) return refuse_yuv("offset[2]: outside 0 .. 3");
-		if (((pic->offset[1] ^ pic->offset[0]) & 1) == 0) return refuse_yuv("offset[1]: a luma sample's place (offset[0] and offset[0] + 2)");
-		if (((pic->offset[2] ^ pic->offset[0]) & 1) == 0) return refuse_yuv("offset[2]: a luma sample's place (offset[0] and offset[0] + 2)");
-		if (pic->offset[2] == pic->offset[1]) return refuse_yuv("offset[2]: the same sample of a group as offset[1]");
-	}
-	const int planes = pic->format == HMR_GPU_YUV_PLANAR ? 3 : pic->format == HMR_GPU_YUV_SEMIPLANAR ? 2 : 1;
-	const int sb = pic->bits > 8 ? 2 : 1;
-	const int64_t wc = pic->chroma == HMR_GPU_CHROMA_444 ? width : width / 2;
-	const int64_t row_bytes[3] = {(pic->format == HMR_GPU_YUV_PACKED422 ? 2 : 1) * (int64_t)width * sb, (pic->format == HMR_GPU_YUV_SEMIPLANAR ? 2 : 1) * wc * sb, wc * sb};
-	static const char *const missing[3] = {"plane[0]: NULL", "plane[1]: NULL", "plane[2]: NULL"};
-	static const char *const extra[3] = {"", "plane[1]: must be NULL for HMR_GPU_YUV_PACKED422 (plane[0] holds the samples)", "plane[2]: must be NULL for this format (it has no third plane)"};
-	static const char *const negative[3] = {"pitch[0]: negative", "pitch[1]: negative", "pitch[2]: negative"};
-	static const char *const narrow[3] = {"pitch[0]: less than a row's bytes (W sb; PACKED422: 2 W sb)", "pitch[1]: less than a row's bytes (Wc sb; SEMIPLANAR: 2 Wc sb)", "pitch[2]: less than a row's bytes (Wc sb)"};
-	static const char *const plane_align[3] = {"plane[0]: not a multiple of 2 (16-bit containers)", "plane[1]: not a multiple of 2 (16-bit containers)", "plane[2]: not a multiple of 2 (16-bit containers)"};
-	static const char *const pitch_align[3] = {"pitch[0]: not a multiple of 2 (16-bit containers)", "pitch[1]: not a multiple of 2 (16-bit containers)", "pitch[2]: not a multiple of 2 (16-bit containers)"};
-	for (int c = 0; c < 3; c++) {
-		if (c >= planes) {
-			if (pic->plane[c]) return refuse_yuv(extra[c]);
-			continue;
-		}
-		if (!pic->plane[c]) return refuse_yuv(missing[c]);
-		if (pic->pitch[c] < 0) return refuse_yuv(negative[c]);
-		if (pic->pitch[c] < row_bytes[c]) return refuse_yuv(narrow[c]);
-		if ((uintptr_t)pic->plane[c] % sb) return refuse_yuv(plane_align[c]);
-		if (pic->pitch[c] % sb) return refuse_yuv(pitch_align[c]);
-	}
-	return HMR_GPU_OK;
-}
-
-// yuv_depth.h's arithmetic over host memory: the loop a caller would write from the header's formulas
-extern "C" int hmr_gpu_yuv_convert_host(const hmr_gpu_yuv_picture *pic, int width, int height, uint8_t *y, uint8_t *u, uint8_t *v)
-{
-	const int rc = hmr_gpu_yuv_picture_check(pic, width, height);
-	if (rc) return rc;
-	if (!y || !u || !v) {
-		hmr_set_error("hmr_gpu_yuv_convert_host: needs the three output planes");
-		return HMR_GPU_ERR_ARG;
-	}
-	const YuvForm f = hmr_yuv_form(pic->format, pic->chroma, pic->bits, pic->msb_aligned, pic->offset);
-	for (int py = 0; py < height; py++)
-		for (int px = 0; px < width; px++) y[(size_t)py * width + px] = (uint8_t)hmr_yuv_luma<const uint8_t *>(pic->plane, pic->pitch, f, px, py);
-	for (int cy = 0; cy < height / 2; cy++)
-		for (int cx = 0; cx < width / 2; cx++) {
-			u[(size_t)cy * (width / 2) + cx] = (uint8_t)hmr_yuv_chroma<const uint8_t *>(pic->plane, pic->pitch, f, 1, cx, cy);
-			v[(size_t)cy * (width / 2) + cx] = (uint8_t)hmr_yuv_chroma<const uint8_t *>(pic->plane, pic->pitch, f, 2, cx, cy);
-		}
-	return HMR_GPU_OK;
-}
-
-// ---- section 12g: the host side of the downscaling ingest ----
-extern "C" int hmr_gpu_scale_check(int src_w, int src_h, int dst_w, int dst_h)
-{
-	const char *why = hmr_scale_refusal(src_w, src_h, dst_w, dst_h);
-	if (!why) return HMR_GPU_OK;
-	hmr_set_error("hmr_gpu_scale_check: %d x %d -> %d x %d: %s", src_w, src_h, dst_w, dst_h, why);
-	return HMR_GPU_ERR_ARG;
-}
-
-// scale_area.h's arithmetic over host memory: the loop a caller would write from the header's formula
-extern "C" int hmr_gpu_scale_host(const hmr_gpu_scaled_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v)
-{
-	if (!pic) {
-		hmr_set_error("hmr_gpu_scale_host: the descriptor is NULL");
-		return HMR_GPU_ERR_ARG;
-	}
-	const int rc = hmr_gpu_picture_check(&pic->pic, pic->width, pic->height);
-	if (rc) return rc;
-	if (const char *why = hmr_scale_refusal(pic->width, pic->height, dst_w, dst_h, true)) {      // (any ratio: the bound of 8 is the kernel's)
-		hmr_set_error("hmr_gpu_scale_host: %d x %d -> %d x %d: %s", pic->width, pic->height, dst_w, dst_h, why);
-		return HMR_GPU_ERR_ARG;
-	}
-	if (!y || !u || !v) {
-		hmr_set_error("hmr_gpu_scale_host: needs the three output planes");
-		return HMR_GPU_ERR_ARG;
-	}
-	const hmr_gpu_picture &p = pic->pic;
-	const int ws = pic->width, hs = pic->height;
-	hmr_scale_plane_host(p.plane[0], p.pitch[0], 1, ws, hs, dst_w, dst_h, y);
-	if (p.format == HMR_GPU_PIC_NV12) {
-		hmr_scale_plane_host(p.plane[1], p.pitch[1], 2, ws / 2, hs / 2, dst_w / 2, dst_h / 2, u);
-		hmr_scale_plane_host(p.plane[1] + 1, p.pitch[1], 2, ws / 2, hs / 2, dst_w / 2, dst_h / 2, v);
-	} else {
-		hmr_scale_plane_host(p.plane[1], p.pitch[1], 1, ws / 2, hs / 2, dst_w / 2, dst_h / 2, u);
-		hmr_scale_plane_host(p.plane[2], p.pitch[2], 1, ws / 2, hs / 2, dst_w / 2, dst_h / 2, v);
-	}
-	return HMR_GPU_OK;
-}
-
-// ---- section 12j: the host side of the downscaling RGB ingest ----
-// rgb_yuv.h's and scale_area.h's arithmetic over host memory, the loop a caller would write from section 12j: every output sums its taps, and each tap converts the
-// pixel (luma) or the 2 x 2 block (chroma) it stands on; no converted picture in between
-extern "C" int hmr_gpu_scale_rgb_host(const hmr_gpu_scaled_rgb_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v)
-{
-	if (!pic) {
-		hmr_set_error("hmr_gpu_scale_rgb_host: the descriptor is NULL");
-		return HMR_GPU_ERR_ARG;
-	}
-	const int rc = hmr_gpu_rgb_picture_check(&pic->pic, pic->width, pic->height);
-	if (rc) return rc;
-	if (const char *why = hmr_scale_refusal(pic->width, pic->height, dst_w, dst_h, true)) {      // (any ratio: the bound of 8 is the kernel's)
-		hmr_set_error("hmr_gpu_scale_rgb_host: %d x %d -> %d x %d: %s", pic->width, pic->height, dst_w, dst_h, why);
-		return HMR_GPU_ERR_ARG;
-	}
-	if (!y || !u || !v) {
-		hmr_set_error("hmr_gpu_scale_rgb_host: needs the three output planes");
-		return HMR_GPU_ERR_ARG;
-	}
-	const hmr_gpu_rgb_picture &p = pic->pic;
-	const RgbMatrix m = hmr_rgb_matrix(p.matrix, p.full_range);
-	const bool packed = p.format == HMR_GPU_RGB_PACKED8;
-	const ScaleAxis ax = hmr_scale_axis(pic->width, dst_w), ay = hmr_scale_axis(pic->height, dst_h);      // (a chroma axis has the same reduced ratio)
-	const uint32_t den = ax.s * ay.s;
-	auto sample = [&](int c, int px, int py) {
-		return rgb_sample<const uint8_t *, const _Float16 *, const float *>((const uint8_t *)p.plane[packed ? 0 : c], p.pitch[packed ? 0 : c], p.format, p.pixel_bytes, p.offset[c], px, py);
-	};
-	for (int oy = 0; oy < dst_h; oy++)
-		for (int ox = 0; ox < dst_w; ox++) {
-			uint32_t sum = den >> 1;
-			for (uint32_t sj = (uint32_t)oy * ay.s / ay.d; sj * ay.d < ((uint32_t)oy + 1) * ay.s; sj++)
-				for (uint32_t si = (uint32_t)ox * ax.s / ax.d; si * ax.d < ((uint32_t)ox + 1) * ax.s; si++)
-					sum += hmr_scale_weight(ay, (uint32_t)oy, sj) * hmr_scale_weight(ax, (uint32_t)ox, si) *
-					       (uint32_t)hmr_rgb_luma(m, sample(0, (int)si, (int)sj), sample(1, (int)si, (int)sj), sample(2, (int)si, (int)sj));
-			y[(size_t)oy * dst_w + ox] = (uint8_t)(sum / den);
-		}
-	for (int oy = 0; oy < dst_h / 2; oy++)
-		for (int ox = 0; ox < dst_w / 2; ox++) {
-			uint32_t sum_u = den >> 1, sum_v = den >> 1;
-			for (uint32_t sj = (uint32_t)oy * ay.s / ay.d; sj * ay.d < ((uint32_t)oy + 1) * ay.s; sj++)
-				for (uint32_t si = (uint32_t)ox * ax.s / ax.d; si * ax.d < ((uint32_t)ox + 1) * ax.s; si++) {
-					int s[3] = {0, 0, 0};      // the sums of the 2 x 2 block under source chroma sample (si, sj)
-					for (int k = 0; k < 4; k++)
-						for (int c = 0; c < 3; c++) s[c] += sample(c, 2 * (int)si + (k & 1), 2 * (int)sj + (k >> 1));
-					const uint32_t w = hmr_scale_weight(ay, (uint32_t)oy, sj) * hmr_scale_weight(ax, (uint32_t)ox, si);
-					sum_u += w * (uint32_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
-					sum_v += w * (uint32_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
-				}
-			const size_t oc = (size_t)oy * (dst_w / 2) + ox;
-			u[oc] = (uint8_t)(sum_u / den);
-			v[oc] = (uint8_t)(sum_v / den);
-		}
-	return HMR_GPU_OK;
-}
-
-// homer_psnr's arithmetic (hmr_metics.c:66-104) on sums of squared differences: pure host
-extern "C" int hmr_gpu_psnr(const uint64_t ssd[3], int width, int height, double psnr[3])
-{
-	if (!ssd || !psnr || width <= 0 || height <= 0 || (width & 1) || (height & 1)) {
-		hmr_set_error("hmr_gpu_psnr: needs three sums, three results and a positive even width and height (%d x %d)", width, height);
-		return HMR_GPU_ERR_ARG;
-	}
-	for (int c = 0; c < 3; c++) {
-		const double samples = c ? (double)(width / 2) * (height / 2) : (double)width * height;
-		psnr[c] = ssd[c] ? 10.0 * log10(255.0 * 255.0 * samples / (double)ssd[c]) : 99.99;
-	}
-	return HMR_GPU_OK;
-}
-
-// ---- section 12i: the host side of the RGB egress ----
-// yuv_rgb.h's arithmetic over host memory: the loop a caller would write from the header's formulas
-extern "C" int hmr_gpu_rgb_from_yuv_host(const uint8_t *y, const uint8_t *u, const uint8_t *v, int width, int height, const hmr_gpu_rgb_picture *out)
-{
-	const int rc = hmr_gpu_rgb_picture_check(out, width, height);
-	if (rc) return rc;
-	if (!y || !u || !v) {
-		hmr_set_error("hmr_gpu_rgb_from_yuv_host: needs the three input planes");
-		return HMR_GPU_ERR_ARG;
-	}
-	const YuvMatrix m = hmr_yuv_matrix(out->matrix, out->full_range);
-	const bool packed = out->format == HMR_GPU_RGB_PACKED8;
-	const int cw = width >> 1, ch = height >> 1;
-	for (int py = 0; py < height; py++)
-		for (int px = 0; px < width; px++) {
-			int c3[3];
-			hmr_yuv_rgb(m, y[(size_t)py * width + px], hmr_yuv_chroma16(u, cw, cw, ch, px, py), hmr_yuv_chroma16(v, cw, cw, ch, px, py), c3[0], c3[1], c3[2]);
-			for (int c = 0; c < 3; c++)
-				rgb_put<uint8_t *, _Float16 *, float *>((uint8_t *)const_cast<void *>(out->plane[packed ? 0 : c]), out->pitch[packed ? 0 : c], out->format, out->pixel_bytes, out->offset[c], px, py, c3[c]);
-			if (packed && out->pixel_bytes == 4) ((uint8_t *)const_cast<void *>(out->plane[0]))[(int64_t)py * out->pitch[0] + 4 * px + rgb_alpha_offset(out->offset)] = 255;
-		}
-	return HMR_GPU_OK;
-}
-
-// the three sums of squared differences between the 8-bit values of two RGB pictures in host memory
-extern "C" int hmr_gpu_rgb_ssd_host(const hmr_gpu_rgb_picture *a, const hmr_gpu_rgb_picture *b, int width, int height, uint64_t ssd[3])
-{
-	int rc;
-	if ((rc = hmr_gpu_rgb_picture_check(a, width, height)) || (rc = hmr_gpu_rgb_picture_check(b, width, height))) return rc;
-	if (!ssd) {
-		hmr_set_error("hmr_gpu_rgb_ssd_host: needs the three sums");
-		return HMR_GPU_ERR_ARG;
-	}
-	const hmr_gpu_rgb_picture *pics[2] = {a, b};
-	for (int c = 0; c < 3; c++) {
-		uint64_t sum = 0;
-		for (int py = 0; py < height; py++)
-			for (int px = 0; px < width; px++) {
-				int s[2];
-				for (int k = 0; k < 2; k++) {
-					const hmr_gpu_rgb_picture *p = pics[k];
-					const int plane = p->format == HMR_GPU_RGB_PACKED8 ? 0 : c;
-					s[k] = rgb_sample<const uint8_t *, const _Float16 *, const float *>((const uint8_t *)p->plane[plane], p->pitch[plane], p->format, p->pixel_bytes, p->offset[c], px, py);
-				}
-				sum += (uint64_t)((s[0] - s[1]) * (s[0] - s[1]));
-			}
-		ssd[c] = sum;
-	}
-	return HMR_GPU_OK;
-}
-
-// PSNR of R, G, B and of all three together from sums of squared differences: pure host
-extern "C" int hmr_gpu_psnr_rgb(const uint64_t ssd[3], int width, int height, double psnr[4])
-{
-	if (!ssd || !psnr || width <= 0 || height <= 0 || (width & 1) || (height & 1)) {
-		hmr_set_error("hmr_gpu_psnr_rgb: needs three sums, four results and a positive even width and height (%d x %d)", width, height);
-		return HMR_GPU_ERR_ARG;
-	}
-	const double samples = (double)width * height;
-	for (int c = 0; c < 3; c++) psnr[c] = ssd[c] ? 10.0 * log10(255.0 * 255.0 * samples / (double)ssd[c]) : 99.99;
-	const uint64_t all = ssd[0] + ssd[1] + ssd[2];
-	psnr[3] = all ? 10.0 * log10(255.0 * 255.0 * 3.0 * samples / (double)all) : 99.99;
-	return HMR_GPU_OK;
-}
-
-// ---- section 12h: the host side of SSIM ----
-// the mean SSIM of each plane from its sum: pure host
-extern "C" int hmr_gpu_ssim(const int64_t sums[3], int width, int height, double ssim[3])
-{
-	if (!sums || !ssim) {
-		hmr_set_error("hmr_gpu_ssim: needs three sums and three results");
-		return HMR_GPU_ERR_ARG;
-	}
-	if (const char *why = hmr_ssim_refusal(width, height)) {
-		hmr_set_error("hmr_gpu_ssim: %d x %d: %s", width, height, why);
-		return HMR_GPU_ERR_ARG;
-	}
-	for (int c = 0; c < 3; c++) {
-		const int64_t windows = c ? hmr_ssim_windows(width / 2, height / 2) : hmr_ssim_windows(width, height);
-		if (sums[c] > (windows << HMR_SSIM_ONE_BITS) || sums[c] < -(windows << HMR_SSIM_ONE_BITS)) {
-			hmr_set_error("hmr_gpu_ssim: sums[%d] = %lld is outside +- 2^30 x %lld windows of a %d x %d picture", c, (long long)sums[c], (long long)windows, width, height);
-			return HMR_GPU_ERR_ARG;
-		}
-		ssim[c] = (double)sums[c] / (double)(windows << HMR_SSIM_ONE_BITS);      // (both conversions exact below 2^53: ONE rounding)
-	}
-	return HMR_GPU_OK;
-}
-
-// ssim_window.h's arithmetic over host memory: the loop a caller would write from the header's definition
-extern "C" int hmr_gpu_ssim_host(const hmr_gpu_picture *a, const hmr_gpu_picture *b, int width, int height, int64_t sums[3])
-{
-	int rc;
-	if ((rc = hmr_gpu_picture_check(a, width, height)) || (rc = hmr_gpu_picture_check(b, width, height))) return rc;
-	if (const char *why = hmr_ssim_refusal(width, height)) {
-		hmr_set_error("hmr_gpu_ssim_host: %d x %d: %s", width, height, why);
-		return HMR_GPU_ERR_ARG;
-	}
-	if (!sums) {
-		hmr_set_error("hmr_gpu_ssim_host: needs the three sums");
-		return HMR_GPU_ERR_ARG;
-	}
-	// plane c of a picture: its first sample, its pitch, the bytes from sample to sample
-	struct View { const uint8_t *p; int64_t pitch; int step; };
-	auto view = [](const hmr_gpu_picture &pic, int c) {
-		if (c == 0 || pic.format == HMR_GPU_PIC_I420) return View{pic.plane[c], pic.pitch[c], 1};
-		return View{pic.plane[1] + (c - 1), pic.pitch[1], 2};
-	};
-	for (int c = 0; c < 3; c++) {
-		const View va = view(*a, c), vb = view(*b, c);
-		sums[c] = hmr_ssim_plane_host(va.p, va.pitch, va.step, vb.p, vb.pitch, vb.step, c ? width / 2 : width, c ? height / 2 : height);
-	}
-	return HMR_GPU_OK;
 }

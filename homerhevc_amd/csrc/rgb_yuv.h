@@ -1,4 +1,4 @@
-// RGB -> 8-bit 4:2:0 Y'CbCr, defined in integers (include/homer_gpu.h section 12f).  ONE arithmetic: k_ingest_rgb (picture_io.hip) and hmr_gpu_rgb_convert_host compile
+// RGB -> 8-bit 4:2:0 Y'CbCr, defined in integers (include/homer_gpu.h section 12f).  ONE arithmetic: k_ingest_rgb (picture_io.hip) and hmr_gpu_rgb_convert_host (picture_host.cpp) compile
 // these functions, and a caller can reproduce every sample from this comment.
 //
 // Inputs are 8-bit R, G, B.  A float sample x (binary16 is widened exactly to binary32 first) becomes
@@ -20,6 +20,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "../../include/homer_gpu.h"      // (the formats rgb_sample reads)
 
 struct RgbMatrix {
 	int32_t y[3], u[3], v[3], yoff;
@@ -45,6 +46,18 @@ __host__ __device__ inline int hmr_rgb_quantize(float x)
 	const float q = x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f;
 #endif
 	return (int)rintf(q * 255.0f);
+}
+// a sample of an RGB picture as 8 bits: `plane` is the packed plane or the channel's own; host and device pointers alike (hmr_gpu_rgb_convert_host, a row's tail)
+template <class Bytes, class Halves, class Floats>
+__host__ __device__ __forceinline__ int rgb_sample(Bytes plane, int64_t pitch, int format, int pixel_bytes, int offset, int x, int y)
+{
+	const Bytes row = plane + (int64_t)y * pitch;
+	switch (format) {
+	case HMR_GPU_RGB_PACKED8: return row[x * pixel_bytes + offset];
+	case HMR_GPU_RGB_PLANAR8: return row[x];
+	case HMR_GPU_RGB_PLANAR_F16: return hmr_rgb_quantize((float)((Halves)row)[x]);
+	default: return hmr_rgb_quantize(((Floats)row)[x]);
+	}
 }
 // coefficient x sample (or sum of four): both fit 24 bits, so the device's full-rate 24-bit multiply gives the same product
 __host__ __device__ inline int hmr_rgb_mul(int k, int s)

@@ -1,4 +1,4 @@
-// SSIM of 8-bit 4:2:0 pictures, defined in integers (include/homer_gpu.h section 12h).  ONE arithmetic: k_ssim (picture_io.hip) and hmr_gpu_ssim_host compile these
+// SSIM of 8-bit 4:2:0 pictures, defined in integers (include/homer_gpu.h section 12h).  ONE arithmetic: k_ssim (picture_io.hip) and hmr_gpu_ssim_host (picture_host.cpp) compile these
 // functions, and a caller can reproduce every sum from this comment.
 //
 // Every plane is measured on its own: luma W x H, each chroma plane W/2 x H/2; a and b are the two pictures' samples of the plane.  W and H are multiples of 8, so a

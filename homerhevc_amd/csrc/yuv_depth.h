@@ -1,5 +1,5 @@
 // Y'CbCr of 8 .. 16 bits in 4:2:0, 4:2:2 or 4:4:4 -> 8-bit 4:2:0 Y'CbCr, defined in integers (include/homer_gpu.h section 12k).  ONE arithmetic: k_ingest_yuv
-// (picture_io.hip) and hmr_gpu_yuv_convert_host compile these functions, and a caller can reproduce every sample from this comment.
+// (picture_io.hip) and hmr_gpu_yuv_convert_host (picture_host.cpp) compile these functions, and a caller can reproduce every sample from this comment.
 //
 // A source sample is an unsigned integer in a container of 1 byte (bits == 8) or 2 bytes (bits 9 .. 16, little endian).
 //     raw    = the container's value

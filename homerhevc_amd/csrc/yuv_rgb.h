@@ -1,5 +1,5 @@
 // 8-bit 4:2:0 Y'CbCr -> RGB, defined in integers (include/homer_gpu.h section 12i): the mirror image of rgb_yuv.h.  ONE arithmetic: k_egress_rgb (picture_io.hip) and
-// hmr_gpu_rgb_from_yuv_host compile these functions, and a caller can reproduce every sample from this comment.
+// hmr_gpu_rgb_from_yuv_host (picture_host.cpp) compile these functions, and a caller can reproduce every sample from this comment.
 //
 // Inputs are 8-bit Y [H, W] and U, V [H / 2, W / 2]; chroma sample (cx, cy) is sited at the centre of the luma block (2 cx .. 2 cx + 1, 2 cy .. 2 cy + 1) - the siting
 // rgb_yuv.h produces.
@@ -25,6 +25,7 @@
 // nearest even.  hmr_rgb_quantize (rgb_yuv.h) of either returns v for all 256 values.  No fast-math on this file: the division must stay correctly rounded on the device.
 #pragma once
 #include <stdint.h>
+#include "../../include/homer_gpu.h"      // (the formats rgb_put writes)
 
 struct YuvMatrix {
 	int32_t ky, rv, gu, gv, bu, yoff;
@@ -74,3 +75,18 @@ __host__ __device__ inline int hmr_yuv_chroma16(Samples plane, int64_t stride, i
 
 // an 8-bit value as a float output sample
 __host__ __device__ inline float hmr_rgb_unit(int v) { return (float)v / 255.0f; }
+
+// a sample of an RGB picture written as 8 bits' worth: host and device pointers alike (hmr_gpu_rgb_from_yuv_host, a row's tail)
+template <class Bytes, class Halves, class Floats>
+__host__ __device__ __forceinline__ void rgb_put(Bytes plane, int64_t pitch, int format, int pixel_bytes, int offset, int x, int y, int v)
+{
+	const Bytes row = plane + (int64_t)y * pitch;
+	switch (format) {
+	case HMR_GPU_RGB_PACKED8: row[x * pixel_bytes + offset] = (uint8_t)v; break;
+	case HMR_GPU_RGB_PLANAR8: row[x] = (uint8_t)v; break;
+	case HMR_GPU_RGB_PLANAR_F16: ((Halves)row)[x] = (_Float16)hmr_rgb_unit(v); break;
+	default: ((Floats)row)[x] = hmr_rgb_unit(v); break;
+	}
+}
+// the byte of a 4-byte pixel that holds no channel
+__host__ __device__ __forceinline__ int rgb_alpha_offset(const int32_t offset[3]) { return 6 - offset[0] - offset[1] - offset[2]; }

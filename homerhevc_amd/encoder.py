@@ -410,20 +410,24 @@ def _output(cfg, out, nv12, device):
     return torch.empty((h * 3 // 2, w), dtype=torch.uint8, device=f"cuda:{device}")
 
 
+def _outputs(cfgs, outs, nv12, device):
+    """the output descriptors of an export: (Picture array, the tensors written, the tensors to keep until the call has returned)"""
+    pics, results, keep = (Picture * len(cfgs))(), [], []
+    for k, cfg in enumerate(cfgs):
+        target = _output(cfg, outs[k] if outs is not None else None, nv12, device)
+        pics[k], t = picture_of(target, cfg.width, cfg.height)
+        keep.append(t)
+        results.append(target)
+    return pics, results, keep
+
+
 def _export(lib, device, encs, cfgs, slot, picture, ssd, outs, nv12):
     """ONE hmr_gpu_enc_export_pictures_device for the encoders `encs`: (their pictures or None, an int64 tensor [len(encs), 3] or None)"""
     import torch
     n = len(encs)
     if not picture and not ssd:
         raise ValueError("export: neither the picture nor the sums asked for")
-    pics, results, keep = None, None, []
-    if picture:
-        pics, results = (Picture * n)(), []
-        for k, cfg in enumerate(cfgs):
-            target = _output(cfg, outs[k] if outs is not None else None, nv12, device)
-            pics[k], t = picture_of(target, cfg.width, cfg.height)
-            keep.append(t)
-            results.append(target)
+    pics, results, keep = _outputs(cfgs, outs, nv12, device) if picture else (None, None, [])
     sums = torch.empty((n, 3), dtype=torch.int64, device=f"cuda:{device}") if ssd else None
     if lib.hmr_gpu_enc_export_pictures_device((C.c_void_p * n)(*encs), n, pics, (C.c_int * n)(*([slot] * n)) if ssd else None,
                                               C.c_void_p(sums.data_ptr()) if ssd else None, _stream_of(device)) != 0:
@@ -442,29 +446,32 @@ def _ssim(lib, device, encs, slot):
     return sums
 
 
+# What a frame class is loaded by: (ctypes struct, C call, the function that describes frame k of a step).  Consulted in this order; anything else is what
+# picture_of takes (a tensor or a tuple of tensors) and goes through _PLAIN_LOAD.
+_PLAIN_LOAD = (Picture, "hmr_gpu_enc_load_sources_device", lambda f, cfg: picture_of(f, cfg.width, cfg.height))
+_FRAME_LOADS = [
+    (RGBFrame, (RgbPicture, "hmr_gpu_enc_load_sources_rgb_device", lambda f, cfg: rgb_picture_of(f, cfg.width, cfg.height))),
+    (YUVFrame, (YuvPicture, "hmr_gpu_enc_load_sources_yuv_device", lambda f, cfg: yuv_picture_of(f, cfg.width, cfg.height))),
+    (ScaledFrame, (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device", lambda f, cfg: scaled_picture_of(f))),
+    (ScaledRGBFrame, (ScaledRgbPicture, "hmr_gpu_enc_load_sources_scaled_rgb_device", lambda f, cfg: scaled_rgb_picture_of(f))),
+]
+
+
 def _load(lib, device, encs, cfgs, slot, frames):
     """the frames (what picture_of takes, RGBFrame, YUVFrame, ScaledFrame or ScaledRGBFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
-    kinds = {"yuv": [], "rgb": [], "deep": [], "scaled": [], "scaled_rgb": []}
+    members = {load: [] for load in [_PLAIN_LOAD] + [load for _, load in _FRAME_LOADS]}      # (in the order the calls are made)
     for k, f in enumerate(frames):
-        kinds["rgb" if isinstance(f, RGBFrame) else "deep" if isinstance(f, YUVFrame) else "scaled" if isinstance(f, ScaledFrame) else "scaled_rgb" if isinstance(f, ScaledRGBFrame) else "yuv"].append(k)
-    calls = {"yuv": (Picture, "hmr_gpu_enc_load_sources_device"), "rgb": (RgbPicture, "hmr_gpu_enc_load_sources_rgb_device"), "deep": (YuvPicture, "hmr_gpu_enc_load_sources_yuv_device"),
-             "scaled": (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device"), "scaled_rgb": (ScaledRgbPicture, "hmr_gpu_enc_load_sources_scaled_rgb_device")}
+        members[next((load for cls, load in _FRAME_LOADS if isinstance(f, cls)), _PLAIN_LOAD)].append(k)
     keep = []
-    for kind, members in kinds.items():
-        n = len(members)
+    for (struct, name, describe), ks in members.items():
+        n = len(ks)
         if not n:
             continue
-        struct, name = calls[kind]
         pics = (struct * n)()
-        for j, k in enumerate(members):
-            if kind == "scaled":
-                pics[j], t = scaled_picture_of(frames[k])
-            elif kind == "scaled_rgb":
-                pics[j], t = scaled_rgb_picture_of(frames[k])
-            else:
-                pics[j], t = (rgb_picture_of if kind == "rgb" else yuv_picture_of if kind == "deep" else picture_of)(frames[k], cfgs[k].width, cfgs[k].height)
+        for j, k in enumerate(ks):
+            pics[j], t = describe(frames[k], cfgs[k])
             keep.append(t)
-        if getattr(lib, name)((C.c_void_p * n)(*[encs[k] for k in members]), n, (C.c_int * n)(*([slot] * n)), pics, _stream_of(device)) != 0:
+        if getattr(lib, name)((C.c_void_p * n)(*[encs[k] for k in ks]), n, (C.c_int * n)(*([slot] * n)), pics, _stream_of(device)) != 0:
             _fail(lib, name)
     return keep
 
@@ -472,12 +479,7 @@ def _load(lib, device, encs, cfgs, slot, frames):
 def _export_sources(lib, device, encs, cfgs, slot, outs, nv12):
     """ONE hmr_gpu_enc_export_sources_device: what slot `slot` of the encoders holds, as 8-bit 4:2:0"""
     n = len(encs)
-    pics, results, keep = (Picture * n)(), [], []
-    for k, cfg in enumerate(cfgs):
-        target = _output(cfg, outs[k] if outs is not None else None, nv12, device)
-        pics[k], t = picture_of(target, cfg.width, cfg.height)
-        keep.append(t)
-        results.append(target)
+    pics, results, keep = _outputs(cfgs, outs, nv12, device)
     if lib.hmr_gpu_enc_export_sources_device((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([slot] * n)), pics, _stream_of(device)) != 0:
         _fail(lib, "hmr_gpu_enc_export_sources_device")
     del keep

@@ -37,7 +37,7 @@ VARIANTS = [("picture", True, False), ("sums", False, True), ("both", True, True
 
 
 def egress_bytes(width, height, picture, sums):
-    """algorithmic bytes of one picture through k_egress (csrc/picture_io.h hmr_egress_bytes): the final picture is read (int16: 3 W H), the slot's picture is read when
+    """algorithmic bytes of one picture through k_egress (the formula in the header comment of csrc/picture_io.hip): the final picture is read (int16: 3 W H), the slot's picture is read when
     sums are asked for (3 W H), the 8-bit picture is written when one is asked for (1.5 W H)"""
     wh = float(width) * height
     return 3.0 * wh + (3.0 * wh if sums else 0.0) + (1.5 * wh if picture else 0.0)

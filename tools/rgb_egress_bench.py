@@ -50,7 +50,7 @@ def pixel_bytes(form):
 
 
 def egress_rgb_bytes(width, height, out_form, ref_form):
-    """algorithmic bytes of one picture through k_egress_rgb (csrc/picture_io.h hmr_egress_rgb_bytes): the int16 planes are read (3 W H), the reference picture is read
+    """algorithmic bytes of one picture through k_egress_rgb (the comment at k_egress_rgb in csrc/picture_io.hip): the int16 planes are read (3 W H), the reference picture is read
     when sums are asked for, the RGB picture is written when one is asked for (3, 4, 3, 6 or 12 W H by form)"""
     return (3.0 + (pixel_bytes(out_form) if out_form else 0) + (pixel_bytes(ref_form) if ref_form else 0)) * width * height
 

@@ -6,7 +6,7 @@ flagship workload (256 sequences of 1920x1080, bench.py's configuration and clip
 
   kernel_rate      k_ingest_rgb's time for one launch over all sequences' pictures, per format (3- and 4-byte packed, planar 8-bit, binary16, binary32), and k_ingest's
                    over I420 pictures in the same run, from `rocprofv3 --kernel-trace --stats` in a run of its own (this program starts it as a child, the traced
-                   program behind `--`, no counters).  Every job has a source tensor of its own.  Bytes from the formula of csrc/picture_io.h hmr_ingest_rgb_bytes:
+                   program behind `--`, no counters).  Every job has a source tensor of its own.  Bytes from the formula in the comment at k_ingest_rgb (csrc/picture_io.hip):
                    3, 4, 3, 6 or 12 W H read, 4 W H written per picture (k_ingest: 1.5 W H read, 3 W H written)
   replaces         wall time of ONE hmr_gpu_enc_load_sources_rgb_device over one float32 [3, H, W] frame (and one RGBA frame) per sequence, against what a user writes
                    today: the same conversion in torch ops, frame by frame, into I420 tensors, then ONE hmr_gpu_enc_load_sources_device; alternating, five repetitions
@@ -39,7 +39,7 @@ LAUNCHES = 6                                                                # pe
 
 
 def picture_bytes(fmt):
-    """algorithmic bytes of one picture: csrc/picture_io.h hmr_ingest_rgb_bytes (k_ingest: 1.5 W H read, 3 W H written)"""
+    """algorithmic bytes of one picture: the comment at k_ingest_rgb in csrc/picture_io.hip (k_ingest: 1.5 W H read, 3 W H written)"""
     return 4.5 * W * H if fmt == "i420" else (READ_BYTES[fmt] + 4.0) * W * H
 
 

@@ -6,7 +6,7 @@
     python tools/rgb_scale_ingest_bench.py [--sources 64] [--bench-this FILE ... --bench-parent FILE ...]
 
   kernel_rate   k_rgb_ladder's time for one launch over all jobs, from `rocprofv3 --kernel-trace --stats` in a run of its own (this program starts it as a child, the
-                traced program behind `--`, no counters): a warm-up and five launches per workload, the median; bytes from hmr_rgb_scale_bytes: 2 x (source pixel
+                traced program behind `--`, no counters): a warm-up and five launches per workload, the median; bytes from the formula in the comment at k_rgb_ladder (csrc/picture_io.hip): 2 x (source pixel
                 bytes x Ws Hs) read - luma and chroma tiles each read the source - + 3 Wd Hd written per job
   replaces      wall ms to fill the slots through ONE hmr_gpu_enc_load_sources_scaled_rgb_device, and through the composition the library offered before:
                 hmr_gpu_enc_load_sources_rgb_device into source-sized encoders, hmr_gpu_enc_export_sources_device of their slots, then
@@ -37,12 +37,12 @@ COPY_PEAK_TBS = 6.29          # float4 copy, measured (the figure the other prof
 
 
 def rgb_scale_bytes(src, dst, pixel_bytes):
-    """hmr_rgb_scale_bytes (csrc/picture_io.h)"""
+    """the formula in the comment at k_rgb_ladder (csrc/picture_io.hip)"""
     return 2.0 * pixel_bytes * src[0] * src[1] + 3.0 * dst[0] * dst[1]
 
 
 def composition_bytes(src, rungs, pixel_bytes):
-    """the three launches: the source read and its int16 slot written (3 Ws Hs), the slot read and the 8-bit picture written (1.5 Ws Hs) once per source, then hmr_scale_bytes
+    """the three launches: the source read and its int16 slot written (3 Ws Hs), the slot read and the 8-bit picture written (1.5 Ws Hs) once per source, then the formula at k_downscale
     per rung (the 8-bit picture read, the rung's slot written)"""
     wh = src[0] * src[1]
     return (pixel_bytes + 3.0) * wh + (3.0 + 1.5) * wh + sum(1.5 * wh + 3.0 * r[0] * r[1] for r in rungs)

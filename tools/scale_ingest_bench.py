@@ -6,7 +6,7 @@ Writes profiles/scale_ingest_bench.json.
     python tools/scale_ingest_bench.py [--sources 64] [--counters] [--bench-this FILE ... --bench-parent FILE ...]
 
   kernel_rate   k_downscale's time for one launch over all jobs, from `rocprofv3 --kernel-trace --stats` in a run of its own (this program starts it as a child, the
-                traced program behind `--`, no counters): five launches and the median; bytes from hmr_scale_bytes: 1.5 Ws Hs read + 3 Wd Hd written per job
+                traced program behind `--`, no counters): five launches and the median; bytes from the formula in the comment at k_downscale (csrc/picture_io.hip): 1.5 Ws Hs read + 3 Wd Hd written per job
   replaces      wall ms to fill the 256 slots of the ladder through ONE hmr_gpu_enc_load_sources_scaled_device, and through what the library offered before:
                 torch.nn.functional.interpolate(mode="area") per rung on float planes, rounded and cast to uint8, then ONE hmr_gpu_enc_load_sources_device;
                 alternating, five repetitions each
@@ -36,7 +36,7 @@ K_INGEST_TBS = 4.9            # profiles/ingest_bench.json: k_ingest on 256 x 10
 
 
 def scale_bytes(src, dst):
-    """hmr_scale_bytes (csrc/picture_io.h)"""
+    """the formula in the comment at k_downscale (csrc/picture_io.hip)"""
     return 1.5 * src[0] * src[1] + 3.0 * dst[0] * dst[1]
 
 

@@ -36,7 +36,7 @@ LAUNCHES = 6      # per kernel in the traced child: a warm-up and five timed
 
 
 def ssim_bytes(width, height):
-    """algorithmic bytes of one picture through k_ssim (csrc/picture_io.h hmr_ssim_bytes): the int16 planes of the final picture and of the slot are read once"""
+    """algorithmic bytes of one picture through k_ssim (the comment at k_ssim in csrc/picture_io.hip): the int16 planes of the final picture and of the slot are read once"""
     return 6.0 * float(width) * height
 
 

@@ -7,7 +7,7 @@ flagship workload (256 sequences of 1920x1080, bench.py's configuration and clip
   kernel_rate      k_ingest_yuv's time for one launch over all sequences' pictures, per form (8-bit 4:2:2 planar, 8-bit 4:4:4 planar, YUYV, P010 4:2:0, 10-bit low-aligned
                    planar 4:2:0, 16-bit 4:4:4 planar), and k_ingest's over I420 pictures in the same run - the yardstick -, from `rocprofv3 --kernel-trace --stats` in a run
                    of its own (this program starts it as a child, the traced program behind `--`, no counters).  Every job has a source of its own.  Bytes from the
-                   formula of csrc/picture_io.h hmr_ingest_yuv_bytes: sb (W H + 2 Wc Hc) read, 3 W H written per picture (k_ingest: 1.5 W H read, 3 W H written).
+                   formula in the comment at k_ingest_yuv (csrc/picture_io.hip): sb (W H + 2 Wc Hc) read, 3 W H written per picture (k_ingest: 1.5 W H read, 3 W H written).
                    With --rgb-bench (profiles/rgb_ingest_bench.json of the same GPU visit): the comparison kernel's share - k_ingest_rgb planar 8-bit over k_ingest -
                    and whether every form reaches that share of k_ingest's rate, the margin being the spread of the five timed launches
   replaces         wall time of ONE hmr_gpu_enc_load_sources_yuv_device over one P010 frame per sequence, against what a user writes today: the rounding in torch ops,
@@ -42,7 +42,7 @@ LAUNCHES = 6                                                                # pe
 
 
 def picture_bytes(form):
-    """algorithmic bytes of one picture: csrc/picture_io.h hmr_ingest_yuv_bytes (k_ingest: 1.5 W H read, 3 W H written)"""
+    """algorithmic bytes of one picture: the comment at k_ingest_yuv in csrc/picture_io.hip (k_ingest: 1.5 W H read, 3 W H written)"""
     if form == "i420":
         return 4.5 * W * H
     _, chroma, bits, _ = FORMS[form]
@@ -179,7 +179,7 @@ def target_of(res, rgb_bench):
             missed[form] = {"rate_over_k_ingest_i420": res[form]["rate_over_k_ingest_i420"], "margin": round(margin, 3)}
     target.update({"measured": True, "share": share, "holds": not missed, "forms_below": missed,
                    "comparison": {"k_ingest_i420_median_us": kr["i420"]["median_us"], "k_ingest_rgb_planar8_median_us": kr["planar8"]["median_us"], "k_ingest_rgb_planar8_tb_per_s": kr["planar8"]["tb_per_s"]},
-                   # the two formulas do not count alike: hmr_ingest_rgb_bytes takes 4 W H for the slot's int16 planes, hmr_ingest_yuv_bytes and k_ingest's 4.5 W H take the 3 W H
+                   # the two formulas do not count alike: the formula at k_ingest_rgb takes 4 W H for the slot's int16 planes, the formula at k_ingest_yuv and k_ingest's 4.5 W H take the 3 W H
                    # they hold (Y 2 W H, U and V W H / 2 each).  The pair below moves the same bytes whichever way they are counted: three 8-bit planes of W x H in, one slot out
                    "same_traffic": {"what": "planar 8-bit 4:4:4 through k_ingest_yuv against planar 8-bit RGB through k_ingest_rgb: 3 W H read and one slot written by both",
                                     "k_ingest_yuv_planar_444_8_median_us": res["planar_444_8"]["median_us"], "k_ingest_rgb_planar8_median_us": kr["planar8"]["median_us"],
