@@ -261,30 +261,41 @@ _lib = None
 _host_lib = None
 
 
+def _declare_metrics(lib):
+    lib.hmr_gpu_last_error.restype = C.c_char_p
+    lib.hmr_gpu_psnr.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib.hmr_gpu_psnr_rgb.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib.hmr_gpu_ssim.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    return lib
+
+
+def _metric_library():
+    """the handle psnr, psnr_rgb and ssim call through: load_library()'s once it has run, else one cached handle that needs neither torch nor a GPU"""
+    global _host_lib
+    if _lib is not None:
+        return _lib
+    if _host_lib is None:
+        _host_lib = _declare_metrics(C.CDLL(LIB_PATH))
+    return _host_lib
+
+
 def psnr(ssd, width, height):
     """homer_psnr's three values (Y, U, V, in dB; 99.99 for a zero sum) of three sums of squared differences - Python ints, e.g. export(ssd=True)[1].tolist() - of a
     width x height 4:2:0 picture, through hmr_gpu_psnr.  Pure host arithmetic: needs neither torch nor a GPU."""
-    global _host_lib
-    if _host_lib is None:
-        lib = _lib or C.CDLL(LIB_PATH)
-        lib.hmr_gpu_last_error.restype = C.c_char_p
-        lib.hmr_gpu_psnr.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
-        _host_lib = lib
+    lib = _metric_library()
     sums = [int(v) for v in ssd]
     if len(sums) != 3 or min(sums) < 0:
         raise ValueError(f"psnr: three non-negative sums, got {sums}")
     out = (C.c_double * 3)()
-    if _host_lib.hmr_gpu_psnr((C.c_uint64 * 3)(*sums), int(width), int(height), out) != 0:
-        raise ValueError((_host_lib.hmr_gpu_last_error() or b"hmr_gpu_psnr").decode(errors="replace"))
+    if lib.hmr_gpu_psnr((C.c_uint64 * 3)(*sums), int(width), int(height), out) != 0:
+        raise ValueError((lib.hmr_gpu_last_error() or b"hmr_gpu_psnr").decode(errors="replace"))
     return tuple(out)
 
 
 def psnr_rgb(ssd, width, height):
     """PSNR in dB of R, G, B and of the three together (99.99 for a zero sum) from three sums of squared differences - Python ints, e.g. export_rgb(reference=...)[1].tolist()
     - of a width x height RGB picture, through hmr_gpu_psnr_rgb (include/homer_gpu.h section 12i).  Pure host arithmetic: needs neither torch nor a GPU."""
-    lib = _lib or _host_lib or C.CDLL(LIB_PATH)
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    lib.hmr_gpu_psnr_rgb.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib = _metric_library()
     sums = [int(v) for v in ssd]
     if len(sums) != 3 or min(sums) < 0:
         raise ValueError(f"psnr_rgb: three non-negative sums, got {sums}")
@@ -298,9 +309,7 @@ def ssim(sums, width, height):
     """The mean SSIM of each plane (Y, U, V; 1.0 for identical pictures, negative for inverted ones) from three SSIM sums - Python ints, e.g. Encoder.ssim().tolist() - of a
     width x height 4:2:0 picture, through hmr_gpu_ssim: sum / (2^30 x the plane's windows), include/homer_gpu.h section 12h.  Pure host arithmetic: needs neither torch
     nor a GPU."""
-    lib = _lib or _host_lib or C.CDLL(LIB_PATH)
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    lib.hmr_gpu_ssim.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib = _metric_library()
     values = [int(v) for v in sums]
     if len(values) != 3 or not all(-(1 << 63) <= v < 1 << 63 for v in values):
         raise ValueError(f"ssim: three 64-bit sums, got {values}")
@@ -320,9 +329,8 @@ def load_library():
                 torch.cuda.init()
         except ImportError:
             pass
-        lib = C.CDLL(LIB_PATH)
+        lib = _declare_metrics(C.CDLL(LIB_PATH))
         P, I, L = C.c_void_p, C.c_int, C.c_long
-        lib.hmr_gpu_last_error.restype = C.c_char_p
         lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
         lib.hmr_gpu_destroy.argtypes = [P]
         lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(EncoderConfig), C.POINTER(P)]

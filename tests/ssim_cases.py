@@ -109,15 +109,8 @@ class HostPicture:
             self.pic.plane[c], self.pic.pitch[c] = buf.ctypes.data + offset, pitch
 
 
-def declare(lib):
-    lib.hmr_gpu_ssim.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_double)]
-    lib.hmr_gpu_ssim_host.argtypes = [C.POINTER(Picture), C.POINTER(Picture), C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
-
-
 def host_sums(lib, a, b, width, height, layout_a="tight_i420", layout_b="tight_i420"):
-    """hmr_gpu_ssim_host on two I420 pictures given as bytes"""
+    """hmr_gpu_ssim_host (through picture_gpu.load()'s binding) on two I420 pictures given as bytes"""
     pa, pb = HostPicture(a, width, height, layout_a, seed=1), HostPicture(b, width, height, layout_b, seed=2)
     out = (C.c_int64 * 3)()
     assert lib.hmr_gpu_ssim_host(C.byref(pa.pic), C.byref(pb.pic), width, height, out) == 0, lib.hmr_gpu_last_error()

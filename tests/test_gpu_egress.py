@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 import encoder_cases as ec
-import libs
-from homerhevc_amd.encoder import PIC_I420, PIC_NV12, BatchEncoder, Encoder, Picture, psnr
-from test_gpu_ingest import BATCH_CASES, GOLD, LAYOUTS, as_tensors, config_of, current_stream, drop, make_encoder, upload
+from homerhevc_amd.encoder import PIC_I420, BatchEncoder, Encoder, Picture, psnr
+from picture_gpu import (BATCH_CASES, GOLD, LAYOUTS, Output, as_tensors, config_of, current_stream, drop, export_many, export_one, gpu, make_encoder, new_sums,  # noqa: F401
+                         upload)
 
 pytestmark = pytest.mark.gpu
 QUALITY = json.load(open(os.path.join(ec.GOLDEN, "quality.json")))
@@ -24,88 +24,10 @@ CASES = ["200x136", "416x240", "328x264_wpp3", "416x240_wpp_rows", "832x480_wpp_
          "384x192_noise_qp0", "1920x1080_cfg2_wpp_rows", "3840x2160_cfg2_wpp32"]
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_enc_encode_batch.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
-    lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = lib.hmr_gpu_enc_encode_batch.argtypes
-    lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
-    lib.hmr_gpu_enc_export_picture_device.argtypes = [P, C.POINTER(Picture), I, P, P]
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
-
-
-class Output:
-    """An output picture in device memory in one of the three layouts.  Every buffer is filled with seeded random bytes first and ends with its plane's last row;
-    picture() gathers the I420 bytes the export left and asserts that every byte outside the rows is what it was."""
-
-    def __init__(self, w, h, layout, seed=0):
-        import torch
-        rng = np.random.default_rng(seed)
-        self.w, self.h, self.layout = w, h, layout
-        self.pic = Picture(format=PIC_NV12 if layout == "nv12" else PIC_I420, reserved=0)
-        if layout == "tight_i420":
-            geometry = [(h * 3 // 2, w, w, 0)]
-        elif layout == "offset_i420":
-            geometry = [(h, w, w + 13, 1), (h // 2, w // 2, w // 2 + 7, 2), (h // 2, w // 2, w // 2 + 3, 3)]
-        else:
-            geometry = [(h, w, w + 6, 0), (h // 2, w, w + 6, 0)]
-        self.geometry, self.before, self.tensors = geometry, [], []
-        for c, (rows, row_bytes, pitch, offset) in enumerate(geometry):
-            buf = rng.integers(0, 256, offset + pitch * (rows - 1) + row_bytes, dtype=np.uint8)
-            self.before.append(buf)
-            self.tensors.append(torch.from_numpy(buf.copy()).cuda())
-        if layout == "tight_i420":
-            base = self.tensors[0].data_ptr()
-            self.pic.plane[0], self.pic.plane[1], self.pic.plane[2] = base, base + w * h, base + w * h * 5 // 4
-            self.pic.pitch[0], self.pic.pitch[1], self.pic.pitch[2] = w, w // 2, w // 2
-        else:
-            for c, (rows, row_bytes, pitch, offset) in enumerate(geometry):
-                self.pic.plane[c], self.pic.pitch[c] = self.tensors[c].data_ptr() + offset, pitch
-
-    def picture(self):
-        planes = []
-        for (rows, row_bytes, pitch, offset), before, t in zip(self.geometry, self.before, self.tensors):
-            after = t.cpu().numpy().copy()
-            view = np.lib.stride_tricks.as_strided(after[offset:], (rows, row_bytes), (pitch, 1))
-            planes.append(view.copy())
-            view[:] = np.lib.stride_tricks.as_strided(before[offset:], (rows, row_bytes), (pitch, 1))
-            assert np.array_equal(after, before), f"{self.layout}: bytes outside the picture's rows were written"
-        if self.layout == "nv12":
-            y, uv = planes
-            return y.tobytes() + uv[:, 0::2].tobytes() + uv[:, 1::2].tobytes()
-        return b"".join(p.tobytes() for p in planes)
-
-
 def numpy_ssd(a, b, w, h):
     d = (np.frombuffer(a, np.uint8).astype(np.int64) - np.frombuffer(b, np.uint8).astype(np.int64)) ** 2
     y, c = w * h, (w // 2) * (h // 2)
     return [int(d[:y].sum()), int(d[y:y + c].sum()), int(d[y + c:].sum())]
-
-
-def new_sums(n=1):
-    import torch
-    return torch.full((n, 3), -7, dtype=torch.int64, device="cuda")
-
-
-def export_one(lib, enc, out, slot, sums):
-    assert lib.hmr_gpu_enc_export_picture_device(enc, C.byref(out.pic) if out is not None else None, slot, C.c_void_p(sums.data_ptr()) if sums is not None else None,
-                                                 current_stream()) == 0, lib.hmr_gpu_last_error()
-
-
-def export_many(lib, encs, outs, slots, sums):
-    k = len(encs)
-    assert lib.hmr_gpu_enc_export_pictures_device((C.c_void_p * k)(*encs), k, (Picture * k)(*[o.pic for o in outs]) if outs is not None else None,
-                                                  (C.c_int * k)(*slots) if slots is not None else None, C.c_void_p(sums.data_ptr()) if sums is not None else None,
-                                                  current_stream()) == 0, lib.hmr_gpu_last_error()
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -234,8 +156,6 @@ def test_chain_pictures_and_sums(gpu):
     g, q = GOLD[case], QUALITY[case]
     w, h, frames, keys = g["width"], g["height"], g["frames"], dict(g["keys"])
     E = keys["engines"]
-    lib.hmr_gpu_enc_create_engine.argtypes = [C.c_void_p, C.POINTER(ec.EncCfg), C.c_int, C.POINTER(C.c_void_p)]
-    lib.hmr_gpu_enc_encode_chain.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_long), C.POINTER(C.c_long)]
     cfg = ec.default_cfg(w, h, **keys)
     ctxs, encs = [], []
     for k in range(E):

@@ -3,100 +3,16 @@ fixtures are uploaded with torch - tightly packed I420, I420 planes at odd addre
 kernel; every stream and every reconstructed picture must be what the compiled reference produced (tests/golden/streams.json)."""
 import ctypes as C
 import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import encoder_cases as ec
-import libs
-from homerhevc_amd.encoder import PIC_I420, PIC_NV12, BatchEncoder, Encoder, EncoderConfig, Picture
+from homerhevc_amd.encoder import PIC_I420, BatchEncoder, Encoder, Picture
+from picture_gpu import BATCH_CASES, GOLD, LAYOUTS, as_tensors, config_of, current_stream, drop, gpu, make_encoder, upload  # noqa: F401  (gpu: the fixture)
 
 pytestmark = pytest.mark.gpu
-GOLD = json.load(open(os.path.join(ec.GOLDEN, "streams.json")))
 ERR_ARG = -3
-LAYOUTS = ["tight_i420", "offset_i420", "nv12"]
-BATCH_CASES = ["416x240_wpp_rows", "832x480_wpp_rows", "416x240_scene_cut_wpp_rows", "328x264_wpp3", "832x480_cbr1500_perf1_wpp_rows", "416x240_cbr300_nosao_wpp_rows",
-               "416x240_noise_wpp_rows", "416x240_extremes_wpp_rows"]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_enc_encode_batch.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
-    lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = lib.hmr_gpu_enc_encode_batch.argtypes
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
-
-
-def case_clip(case):
-    """(width, height, configuration keys, image_type, the clip's frames as (y, u, v) bytes) of a fixture"""
-    g = GOLD[case]
-    keys = dict(g["keys"])
-    cut_at, seed, content = keys.pop("cut_at", None), keys.pop("clip_seed", 1234), keys.pop("content", "default")
-    image_type = 3 if keys.pop("force_intra", 0) else 0
-    return g["width"], g["height"], keys, image_type, ec.clip_frames(g["width"], g["height"], g["frames"], cut_at, seed, content)
-
-
-def make_encoder(lib, case):
-    w, h, keys, image_type, clip = case_clip(case)
-    ctx, enc = C.c_void_p(), C.c_void_p()
-    assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()      # a context (stream) of its own per sequence
-    cfg = ec.default_cfg(w, h, **keys)
-    assert lib.hmr_gpu_enc_create(ctx, C.byref(cfg), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
-    return ctx, enc, w, h, image_type, clip
-
-
-def drop(lib, ctx, enc):
-    lib.hmr_gpu_enc_destroy(enc)
-    lib.hmr_gpu_destroy(ctx)
-
-
-def embed(rng, plane, rows, row_bytes, pitch, offset):
-    """a plane of `rows` rows at byte `offset` and pitch `pitch` of a buffer that ends with the plane's last row; every other byte is random"""
-    buf = rng.integers(0, 256, offset + pitch * (rows - 1) + row_bytes, dtype=np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf[offset:], (rows, row_bytes), (pitch, 1))
-    view[:] = np.frombuffer(plane, np.uint8).reshape(rows, row_bytes)
-    return buf
-
-
-def upload(planes, w, h, layout, seed=0):
-    """the picture in device memory in one of the three layouts: (descriptor, the tensors that hold it)"""
-    import torch
-    rng = np.random.default_rng(seed)
-    y, u, v = planes
-    pic = Picture(format=PIC_I420, reserved=0)
-    if layout == "tight_i420":
-        t = torch.from_numpy(np.frombuffer(y + u + v, np.uint8).copy()).cuda()
-        pic.plane[0], pic.plane[1], pic.plane[2] = t.data_ptr(), t.data_ptr() + w * h, t.data_ptr() + w * h * 5 // 4
-        pic.pitch[0], pic.pitch[1], pic.pitch[2] = w, w // 2, w // 2
-        return pic, [t]
-    if layout == "offset_i420":
-        geometry = [(y, h, w, w + 13, 1), (u, h // 2, w // 2, w // 2 + 7, 2), (v, h // 2, w // 2, w // 2 + 3, 3)]
-    else:
-        uv = np.stack([np.frombuffer(u, np.uint8), np.frombuffer(v, np.uint8)], axis=1).tobytes()
-        geometry = [(y, h, w, w + 6, 0), (uv, h // 2, w, w + 6, 0)]
-        pic.format = PIC_NV12
-    keep = []
-    for c, (plane, rows, row_bytes, pitch, offset) in enumerate(geometry):
-        t = torch.from_numpy(embed(rng, plane, rows, row_bytes, pitch, offset)).cuda()
-        pic.plane[c], pic.pitch[c] = t.data_ptr() + offset, pitch
-        keep.append(t)
-    return pic, keep
-
-
-def current_stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
@@ -198,30 +114,6 @@ def test_ingest_is_ordered_against_the_producer_stream(gpu):
     drop(lib, ctx, enc)
     assert all(pending), f"the picture was already produced when the load call returned (frames {pending}): the test did not exercise the ordering"
     assert len(stream) == g["stream_bytes"] and hashlib.md5(stream).hexdigest() == g["stream_md5"]
-
-
-def config_of(case):
-    w, h, keys, image_type, clip = case_clip(case)
-    return EncoderConfig(w, h, **{ec.KEY_NAMES.get(k, k): v for k, v in keys.items()}), image_type, clip
-
-
-def as_tensors(planes, w, h, form, seed):
-    """what Encoder.encode takes: one contiguous [h * 3 // 2, w] tensor, (y, u, v) views into larger tensors, or (y, uv) for NV12"""
-    import torch
-    y, u, v = planes
-    if form == 0:
-        return torch.from_numpy(np.frombuffer(y + u + v, np.uint8).copy()).cuda().view(h * 3 // 2, w)
-    rng = np.random.default_rng(seed)
-    if form == 1:
-        views = []
-        for plane, rows, cols, pad, left in ((y, h, w, 13, 1), (u, h // 2, w // 2, 7, 2), (v, h // 2, w // 2, 3, 3)):
-            big = rng.integers(0, 256, (rows + 2, cols + pad), dtype=np.uint8)
-            big[1:rows + 1, left:left + cols] = np.frombuffer(plane, np.uint8).reshape(rows, cols)
-            views.append(torch.from_numpy(big).cuda()[1:rows + 1, left:left + cols])
-        assert not any(t.is_contiguous() for t in views)
-        return tuple(views)
-    uv = np.stack([np.frombuffer(u, np.uint8).reshape(h // 2, w // 2), np.frombuffer(v, np.uint8).reshape(h // 2, w // 2)], axis=2)
-    return torch.from_numpy(np.frombuffer(y, np.uint8).reshape(h, w).copy()).cuda(), torch.from_numpy(uv.copy()).cuda()
 
 
 @pytest.mark.parametrize("case", ["416x240", "416x240_force_intra"])

@@ -12,42 +12,18 @@ import numpy as np
 import pytest
 
 import encoder_cases as ec
-import libs
 import rgb_cases as rc
 import rgb_egress_cases as re_
 from homerhevc_amd.encoder import BatchEncoder, Encoder, Picture, RGBFrame, psnr_rgb
-from test_gpu_egress import Output, export_one
-from test_gpu_ingest import BATCH_CASES, GOLD, LAYOUTS, as_tensors, config_of, current_stream, drop, make_encoder, upload
-from test_gpu_rgb_ingest import Source, chans_of, new_encoder, rgb_frame
+from picture_gpu import (BATCH_CASES, GOLD, LAYOUTS, Output, as_tensors, config_of, current_stream, drop, export_one, gpu, make_encoder, new_encoder, new_sums,  # noqa: F401
+                         rgb_frame, upload)
+from picture_gpu import RgbSource as Source      # the references: rc.lay_out's buffers uploaded, rc.descriptor over them
+from rgb_scale_cases import chans_of
 
 pytestmark = pytest.mark.gpu
 ERR_ARG = -3
 FORMS = sorted(rc.FORMS)
 RGB_GOLD = json.load(open(os.path.join(ec.GOLDEN, "rgb_egress.json")))
-R = C.POINTER(rc.RgbPicture)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_source_rgb_device.argtypes = [P, I, R, P]
-    lib.hmr_gpu_enc_export_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_enc_encode_batch.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
-    lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = lib.hmr_gpu_enc_encode_batch.argtypes
-    lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
-    lib.hmr_gpu_enc_export_picture_device.argtypes = [P, C.POINTER(Picture), I, P, P]
-    lib.hmr_gpu_enc_export_pictures_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), R, R, P, P]
-    lib.hmr_gpu_enc_export_picture_rgb_device.argtypes = [P, I, R, R, P, P]
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
 
 
 class Target:
@@ -64,11 +40,6 @@ class Target:
 
     def untouched(self):
         return all(np.array_equal(t.cpu().numpy(), b) for t, b in zip(self.tensors, self.canvas.before))
-
-
-def new_sums(n=1):
-    import torch
-    return torch.full((n, 3), -7, dtype=torch.int64, device="cuda")
 
 
 def export_rgb(lib, encs, which, targets, refs, sums, stream=None):

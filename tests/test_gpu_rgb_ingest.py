@@ -14,78 +14,16 @@ import hashlib
 import numpy as np
 import pytest
 
-import encoder_cases as ec
-import libs
 import rgb_cases as rc
 from homerhevc_amd.encoder import BatchEncoder, Encoder, Picture, RGBFrame
-from test_gpu_egress import Output
-from test_gpu_ingest import BATCH_CASES, GOLD, LAYOUTS, as_tensors, config_of, current_stream, drop, make_encoder, upload
+from picture_gpu import (BATCH_CASES, GOLD, LAYOUTS, Output, as_tensors, config_of, current_stream, drop, first_difference, gpu, make_encoder, new_encoder,  # noqa: F401
+                         rgb_frame, slot_picture, upload)
+from picture_gpu import RgbSource as Source      # rc.lay_out's buffers uploaded, rc.descriptor over them, rc.restate's picture as `want`
+from rgb_scale_cases import chans_of
 
 pytestmark = pytest.mark.gpu
 ERR_ARG = -3
 FORMS = sorted(rc.FORMS)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_source_rgb_device.argtypes = [P, I, C.POINTER(rc.RgbPicture), P]
-    lib.hmr_gpu_enc_load_sources_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(rc.RgbPicture), P]
-    lib.hmr_gpu_enc_export_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_enc_encode_batch.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
-    lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = lib.hmr_gpu_enc_encode_batch.argtypes
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
-
-
-class Source:
-    """An RGB picture in device memory: laid out by rc.lay_out (odd base addresses, padded pitches, random bytes around the rows), uploaded buffer by buffer."""
-
-    def __init__(self, form, chans, matrix, full, rng, padded=True):
-        import torch
-        fmt, pb, offs, planes = rc.lay_out(form, chans, rng, padded)
-        self.before = [buf for buf, _, _ in planes]
-        self.tensors = [torch.from_numpy(buf.copy()).cuda() for buf in self.before]
-        self.pic = rc.descriptor(fmt, pb, offs, [t.data_ptr() + base for t, (_, base, _) in zip(self.tensors, planes)], [pitch for _, _, pitch in planes], matrix, full)
-        self.want = b"".join(p.tobytes() for p in rc.restate(*rc.eight_bit(form, chans), matrix, full))      # the I420 picture the slot has to hold
-
-    def untouched(self):
-        return all(np.array_equal(t.cpu().numpy(), b) for t, b in zip(self.tensors, self.before))
-
-
-def chans_of(form, rng, r, g, b):
-    return rc.as_floats(form, rng, r, g, b) if form in rc.FLOAT_TYPES else [r, g, b]
-
-
-def new_encoder(lib, w, h, **keys):
-    ctx, enc = C.c_void_p(), C.c_void_p()
-    assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()
-    cfg = ec.default_cfg(w, h, **keys)
-    assert lib.hmr_gpu_enc_create(ctx, C.byref(cfg), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
-    return ctx, enc
-
-
-def slot_picture(lib, enc, slot, w, h, layout, seed=0):
-    out = Output(w, h, layout, seed)
-    assert lib.hmr_gpu_enc_export_source_device(enc, slot, C.byref(out.pic), current_stream()) == 0, lib.hmr_gpu_last_error()
-    return out.picture()      # (synchronises; asserts the bytes around the rows)
-
-
-def first_difference(got, want, w, h):
-    a, b = np.frombuffer(got, np.uint8), np.frombuffer(want, np.uint8)
-    k = int(np.flatnonzero(a != b)[0])
-    plane = "Y" if k < w * h else "U" if k < w * h * 5 // 4 else "V"
-    return f"{int((a != b).sum())} bytes differ, first at byte {k} ({plane}): got {a[k]}, want {b[k]}"
 
 
 @pytest.mark.parametrize("size", [(200, 136), (328, 264), (416, 240), (1920, 1080)], ids=lambda s: f"{s[0]}x{s[1]}")
@@ -157,7 +95,7 @@ def rgb_of_clip(made):
 
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_end_to_end_against_the_converted_i420(gpu, pipelined):
-    """The clips of test_gpu_ingest.py's BATCH_CASES as RGB: ONE hmr_gpu_enc_load_sources_rgb_device per step for all sequences that still have frames, formats, matrices and
+    """The clips of picture_gpu.BATCH_CASES as RGB: ONE hmr_gpu_enc_load_sources_rgb_device per step for all sequences that still have frames, formats, matrices and
     ranges mixed within the call, then one batch launch.  The control encoders get the numpy-converted I420 through hmr_gpu_enc_load_sources_device.  Streams and exported
     reconstructions are byte-identical, sequence by sequence, and so are the slots."""
     lib = gpu
@@ -358,37 +296,6 @@ def test_refusals_leave_the_encoder_working(gpu):
 
 # ---- the Python classes ----
 TENSOR_FORMS = ["hwc3", "hwc3_bgr_view", "hwc4_rgba", "hwc4_bgra_view", "hwc4_argb", "hwc4_abgr", "chw_u8", "chw_u8_slice", "chw_f16", "chw_f16_view", "chw_f32", "chw_f32_slice"]
-
-
-def rgb_frame(kind, r, g, b, matrix, full, rng):
-    """(RGBFrame, the 8-bit R, G, B it stands for) in one of the tensor forms"""
-    import torch
-    h, w = r.shape
-    if kind.startswith("hwc"):
-        order = {"hwc3": "rgb", "hwc3_bgr_view": "bgr", "hwc4_rgba": "rgba", "hwc4_bgra_view": "bgra", "hwc4_argb": "argb", "hwc4_abgr": "abgr"}[kind]
-        pb, offs = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0)), "argb": (4, (1, 2, 3)), "abgr": (4, (3, 2, 1))}[order]
-        view = kind.endswith("_view")
-        big = rng.integers(0, 256, (h + (2 if view else 0), w + (5 if view else 0), pb), dtype=np.uint8)
-        for c, p in enumerate((r, g, b)):
-            big[(1 if view else 0):(1 if view else 0) + h, (3 if view else 0):(3 if view else 0) + w, offs[c]] = p
-        t = torch.from_numpy(big).cuda()
-        if view:
-            t = t[1:1 + h, 3:3 + w]
-            assert not t.is_contiguous()
-        return RGBFrame(t, order=order, matrix=matrix, full_range=full), [r, g, b]
-    dtype = {"u8": np.uint8, "f16": np.float16, "f32": np.float32}[kind.split("_")[1]]
-    chans = [r, g, b] if dtype is np.uint8 else rc.as_floats("f16" if dtype is np.float16 else "f32", rng, r, g, b)
-    if kind.endswith("_slice"):      # channels 1 .. 3 of a four-channel tensor
-        big = np.stack([chans[0] * 0] + chans)
-        t = torch.from_numpy(big).cuda()[1:]
-    elif kind.endswith("_view"):     # a window of a larger tensor
-        big = np.zeros((3, h + 3, w + 7), dtype)
-        big[:, 2:2 + h, 5:5 + w] = np.stack(chans)
-        t = torch.from_numpy(big).cuda()[:, 2:2 + h, 5:5 + w]
-        assert not t.is_contiguous()
-    else:
-        t = torch.from_numpy(np.stack(chans)).cuda()
-    return RGBFrame(t, matrix=matrix, full_range=full), rc.eight_bit("f16" if dtype is np.float16 else "f32" if dtype is np.float32 else "planar8", chans)
 
 
 def test_encoder_class(gpu):

@@ -11,76 +11,29 @@ import numpy as np
 import pytest
 
 import encoder_cases as ec
-import libs
+import picture_gpu
 import rgb_cases as rc
 import rgb_scale_cases as rs
 import scale_cases as sc
 from homerhevc_amd.encoder import BatchEncoder, Encoder, EncoderConfig, Picture, RGBFrame, ScaledFrame, ScaledRGBFrame, scaled_rgb_picture_of
-from test_gpu_egress import Output
-from test_gpu_ingest import LAYOUTS, current_stream, drop
+from picture_gpu import LAYOUTS, Output, current_stream, drop, first_difference, gpu, new_encoder, slot_picture  # noqa: F401  (gpu: the fixture)
 
 pytestmark = pytest.mark.gpu
 ERR_ARG = -3
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_rgb_device.argtypes = [P, I, C.POINTER(rc.RgbPicture), P]
-    lib.hmr_gpu_enc_load_source_scaled_rgb_device.argtypes = [P, I, C.POINTER(rs.ScaledRgbPicture), P]
-    lib.hmr_gpu_enc_load_sources_scaled_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(rs.ScaledRgbPicture), P]
-    lib.hmr_gpu_enc_export_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
-
-
-class Source:
-    """An RGB picture in device memory: laid out by rc.lay_out (odd base addresses, padded pitches, random bytes around the rows), uploaded buffer by buffer."""
+class Source(picture_gpu.Source):
+    """An RGB picture laid out by rc.lay_out, with the descriptor of section 12j"""
 
     def __init__(self, form, chans, matrix, full, rng, padded=True):
-        import torch
-        h, w = chans[0].shape
         fmt, pb, offs, planes = rc.lay_out(form, chans, rng, padded)
-        self.form, self.chans, self.matrix, self.full, self.w, self.h = form, chans, matrix, full, w, h
-        self.before = [buf for buf, _, _ in planes]
-        self.tensors = [torch.from_numpy(buf.copy()).cuda() for buf in self.before]
-        self.pic = rs.descriptor(fmt, pb, offs, [t.data_ptr() + base for t, (_, base, _) in zip(self.tensors, planes)], [pitch for _, _, pitch in planes], matrix, full, w, h)
+        super().__init__(planes)
+        self.form, self.chans, self.matrix, self.full, (self.h, self.w) = form, chans, matrix, full, chans[0].shape
+        self.pic = rs.descriptor(fmt, pb, offs, self.addresses, self.pitches, matrix, full, self.w, self.h)
 
     def want(self, wd, hd):
         """the I420 picture a wd x hd slot has to hold"""
         return rs.comparator_bytes(self.form, self.chans, self.matrix, self.full, wd, hd)
-
-    def untouched(self):
-        return all(np.array_equal(t.cpu().numpy(), b) for t, b in zip(self.tensors, self.before))
-
-
-def new_encoder(lib, w, h, **keys):
-    ctx, enc = C.c_void_p(), C.c_void_p()
-    assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()
-    cfg = ec.default_cfg(w, h, **keys)
-    assert lib.hmr_gpu_enc_create(ctx, C.byref(cfg), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
-    return ctx, enc
-
-
-def slot_picture(lib, enc, slot, w, h, layout, seed=0):
-    out = Output(w, h, layout, seed)
-    assert lib.hmr_gpu_enc_export_source_device(enc, slot, C.byref(out.pic), current_stream()) == 0, lib.hmr_gpu_last_error()
-    return out.picture()      # (synchronises; asserts the bytes around the rows)
-
-
-def first_difference(got, want, w, h):
-    a, b = np.frombuffer(got, np.uint8), np.frombuffer(want, np.uint8)
-    k = int(np.flatnonzero(a != b)[0])
-    plane, at = ("Y", k) if k < w * h else ("U", k - w * h) if k < w * h * 5 // 4 else ("V", k - w * h * 5 // 4)
-    pw = w if plane == "Y" else w // 2
-    return f"{int((a != b).sum())} bytes differ, first in {plane} at x = {at % pw}, y = {at // pw}: got {a[k]}, want {b[k]}"
 
 
 def load_one(lib, enc, slot, src):

@@ -11,11 +11,10 @@ import numpy as np
 import pytest
 
 import encoder_cases as ec
-import libs
+import picture_gpu
 import scale_cases as sc
 from homerhevc_amd.encoder import BatchEncoder, Encoder, EncoderConfig, Picture, ScaledFrame
-from test_gpu_egress import Output
-from test_gpu_ingest import LAYOUTS, current_stream, drop
+from picture_gpu import LAYOUTS, Output, current_stream, drop, first_difference, gpu, new_encoder, slot_picture  # noqa: F401  (gpu: the fixture)
 
 pytestmark = pytest.mark.gpu
 ERR_ARG = -3
@@ -23,63 +22,17 @@ ERR_ARG = -3
 SINGLE = [p for p in sc.PAIRS if p[1] != (2, 2)] + [((400, 272), (400, 272))]
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_source_scaled_device.argtypes = [P, I, C.POINTER(sc.ScaledPicture), P]
-    lib.hmr_gpu_enc_load_sources_scaled_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(sc.ScaledPicture), P]
-    lib.hmr_gpu_enc_export_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
-
-
-class Source:
-    """A 4:2:0 picture in device memory: laid out by sc.lay_out (odd base addresses, padded pitches, random bytes around the rows), uploaded buffer by buffer."""
+class Source(picture_gpu.Source):
+    """A 4:2:0 picture laid out by sc.lay_out, with the descriptor of section 12g"""
 
     def __init__(self, planes, fmt, rng, padded=True):
-        import torch
-        h, w = planes[0].shape
-        parts = sc.lay_out(planes, fmt, rng, padded)
-        self.planes, self.w, self.h = planes, w, h
-        self.before = [buf for buf, _, _ in parts]
-        self.tensors = [torch.from_numpy(buf.copy()).cuda() for buf in self.before]
-        self.pic = sc.descriptor(fmt, [t.data_ptr() + off for t, (_, off, _) in zip(self.tensors, parts)], [pitch for _, _, pitch in parts], w, h)
+        super().__init__(sc.lay_out(planes, fmt, rng, padded))
+        self.planes, (self.h, self.w) = planes, planes[0].shape
+        self.pic = sc.descriptor(fmt, self.addresses, self.pitches, self.w, self.h)
 
     def want(self, wd, hd):
         """the I420 picture a wd x hd slot has to hold"""
         return sc.as_bytes(sc.restate(self.planes, wd, hd))
-
-    def untouched(self):
-        return all(np.array_equal(t.cpu().numpy(), b) for t, b in zip(self.tensors, self.before))
-
-
-def new_encoder(lib, w, h, **keys):
-    ctx, enc = C.c_void_p(), C.c_void_p()
-    assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()
-    cfg = ec.default_cfg(w, h, **keys)
-    assert lib.hmr_gpu_enc_create(ctx, C.byref(cfg), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
-    return ctx, enc
-
-
-def slot_picture(lib, enc, slot, w, h, layout, seed=0):
-    out = Output(w, h, layout, seed)
-    assert lib.hmr_gpu_enc_export_source_device(enc, slot, C.byref(out.pic), current_stream()) == 0, lib.hmr_gpu_last_error()
-    return out.picture()      # (synchronises; asserts the bytes around the rows)
-
-
-def first_difference(got, want, w, h):
-    a, b = np.frombuffer(got, np.uint8), np.frombuffer(want, np.uint8)
-    k = int(np.flatnonzero(a != b)[0])
-    plane = "Y" if k < w * h else "U" if k < w * h * 5 // 4 else "V"
-    return f"{int((a != b).sum())} bytes differ, first at byte {k} ({plane}): got {a[k]}, want {b[k]}"
 
 
 @pytest.mark.parametrize("pair", SINGLE, ids=sc.pair_id)

@@ -10,11 +10,10 @@ import numpy as np
 import pytest
 
 import encoder_cases as ec
-import libs
 import ssim_cases as sc
 from homerhevc_amd.encoder import PIC_I420, BatchEncoder, Encoder, Picture, ssim
-from test_gpu_egress import Output, export_one
-from test_gpu_ingest import BATCH_CASES, GOLD, LAYOUTS, as_tensors, config_of, current_stream, drop, make_encoder, upload
+from picture_gpu import (BATCH_CASES, GOLD, LAYOUTS, Output, as_tensors, config_of, current_stream, drop, export_one, gpu, make_encoder, new_sums,  # noqa: F401
+                         upload)
 
 pytestmark = pytest.mark.gpu
 SSIM = json.load(open(os.path.join(ec.GOLDEN, "ssim.json")))
@@ -26,31 +25,6 @@ CASES = ["200x136", "328x264_wpp3", "416x240_wpp_rows", "384x192_noise_qp0", "41
 # 32 x 8: 256 x 64); 136 x 40 and 200 x 136 have odd chroma block counts (17 x 5, 25 x 17), 200 x 136 more than one tile row in both planes.
 SHAPES = [(128, 32), (136, 40), (256, 64), (264, 72), (272, 80), (200, 136)]
 FAMILIES = ["default", "noise", "extremes", "flat", "motion", "chroma"]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_enc_encode_batch.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
-    lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = lib.hmr_gpu_enc_encode_batch.argtypes
-    lib.hmr_gpu_enc_export_picture_device.argtypes = [P, C.POINTER(Picture), I, P, P]
-    lib.hmr_gpu_enc_export_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_ssim_device.argtypes = [C.POINTER(P), I, C.POINTER(I), P, P]
-    lib.hmr_gpu_enc_ssim_one_device.argtypes = [P, I, P, P]
-    return sc.declare(lib)
-
-
-def new_sums(n=1):
-    import torch
-    return torch.full((n, 3), -7, dtype=torch.int64, device="cuda")
 
 
 def ssim_one(lib, enc, slot, sums):
@@ -201,8 +175,6 @@ def test_chain_sums(gpu):
     g, s = GOLD[case], SSIM[case]
     w, h, frames, keys = g["width"], g["height"], g["frames"], dict(g["keys"])
     E = keys["engines"]
-    lib.hmr_gpu_enc_create_engine.argtypes = [C.c_void_p, C.POINTER(ec.EncCfg), C.c_int, C.POINTER(C.c_void_p)]
-    lib.hmr_gpu_enc_encode_chain.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_long), C.POINTER(C.c_long)]
     cfg = ec.default_cfg(w, h, **keys)
     ctxs, encs = [], []
     for k in range(E):

@@ -5,78 +5,31 @@ restatement, never the kernel.  End to end, the streams and reconstructions of e
 existing hmr_gpu_enc_load_sources_device, with the numpy-converted I420.
 
 What the canaries see: every byte of the source buffers (the rows and the random bytes around them; every buffer ends with its plane's last row) is what it was after the
-load, and every byte of the export's output buffers outside the pictures' rows is what it was (test_gpu_egress.Output)."""
+load, and every byte of the export's output buffers outside the pictures' rows is what it was (picture_gpu.Output)."""
 import ctypes as C
 import hashlib
 
 import numpy as np
 import pytest
 
-import encoder_cases as ec
-import libs
+import picture_gpu
 import rgb_cases as rc
 import yuv_cases as yc
 from homerhevc_amd.encoder import BatchEncoder, Encoder, Picture, RGBFrame, ScaledFrame, YUVFrame, yuv_picture_of
-from test_gpu_egress import Output
-from test_gpu_ingest import GOLD, LAYOUTS, as_tensors, config_of, current_stream, drop, make_encoder, upload
+from picture_gpu import (GOLD, LAYOUTS, Output, as_tensors, config_of, current_stream, drop, first_difference, gpu, make_encoder, new_encoder, slot_picture,  # noqa: F401
+                         upload)
 
 pytestmark = pytest.mark.gpu
 ERR_ARG = -3
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_source_yuv_device.argtypes = [P, I, C.POINTER(yc.YuvPicture), P]
-    lib.hmr_gpu_enc_load_sources_yuv_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(yc.YuvPicture), P]
-    lib.hmr_gpu_enc_export_source_device.argtypes = [P, I, C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    return lib
-
-
-class Source:
-    """A picture in device memory: laid out by yc.lay_out (odd, sample-aligned base addresses, padded pitches, random bytes around the rows, every buffer ending with its
-    plane's last row), uploaded buffer by buffer."""
+class Source(picture_gpu.Source):
+    """A picture laid out by yc.lay_out (sample-aligned base addresses), with the descriptor of section 12k and, as `want`, the I420 picture the slot has to hold"""
 
     def __init__(self, form, planes3, rng, padded=True):
-        import torch
-        planes = yc.lay_out(form, *planes3, rng, padded)
-        self.before = [buf for buf, _, _ in planes]
-        self.tensors = [torch.from_numpy(buf.copy()).cuda() for buf in self.before]
-        self.pic = yc.descriptor(form, [t.data_ptr() + base for t, (_, base, _) in zip(self.tensors, planes)], [pitch for _, _, pitch in planes])
-        self.want = b"".join(p.tobytes() for p in yc.restate(form, *planes3))      # the I420 picture the slot has to hold
-
-    def untouched(self):
-        return all(np.array_equal(t.cpu().numpy(), b) for t, b in zip(self.tensors, self.before))
-
-
-def new_encoder(lib, w, h, **keys):
-    ctx, enc = C.c_void_p(), C.c_void_p()
-    assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()
-    cfg = ec.default_cfg(w, h, **keys)
-    assert lib.hmr_gpu_enc_create(ctx, C.byref(cfg), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
-    return ctx, enc
-
-
-def slot_picture(lib, enc, slot, w, h, layout, seed=0):
-    out = Output(w, h, layout, seed)
-    assert lib.hmr_gpu_enc_export_source_device(enc, slot, C.byref(out.pic), current_stream()) == 0, lib.hmr_gpu_last_error()
-    return out.picture()      # (synchronises; asserts the bytes around the rows)
-
-
-def first_difference(got, want, w, h):
-    a, b = np.frombuffer(got, np.uint8), np.frombuffer(want, np.uint8)
-    k = int(np.flatnonzero(a != b)[0])
-    plane = "Y" if k < w * h else "U" if k < w * h * 5 // 4 else "V"
-    return f"{int((a != b).sum())} bytes differ, first at byte {k} ({plane}): got {a[k]}, want {b[k]}"
+        super().__init__(yc.lay_out(form, *planes3, rng, padded))
+        self.pic = yc.descriptor(form, self.addresses, self.pitches)
+        self.want = b"".join(p.tobytes() for p in yc.restate(form, *planes3))
 
 
 @pytest.mark.parametrize("size", [(200, 136), (328, 264), (416, 240)], ids=lambda s: f"{s[0]}x{s[1]}")

@@ -13,6 +13,7 @@ import pytest
 
 import encoder_cases as ec
 import libs
+import picture_gpu
 import ssim_cases as sc
 from homerhevc_amd.encoder import Picture
 from test_egress_cpu import QUALITY_CASES
@@ -31,7 +32,7 @@ SIZES = [(16, 16), (24, 16), (72, 16), (200, 136)]
 def lib():
     from homerhevc_amd.build import build_native
     build_native()
-    return sc.declare(C.CDLL(libs.GPU_SO))
+    return picture_gpu.load()
 
 
 @pytest.fixture(scope="module")

@@ -15,25 +15,21 @@
   bench            bench.py's lines of this build and of the parent commit's, when the files are given (all from the same GPU visit, alternating)
 Timed windows are walls between two device synchronisations, in one process with the steady state warmed first."""
 import argparse
-import csv
 import ctypes as C
-import glob
-import json
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 import ingest_bench as ib  # noqa: E402  (the workload, the encoders' set-up and k_ingest's trace)
+import picture_bench as pb  # noqa: E402
+from picture_bench import COPY_PEAK_TBS, spread  # noqa: E402
 
-W, H, CLIP_FRAMES, COPY_PEAK_TBS = ib.W, ib.H, ib.CLIP_FRAMES, ib.COPY_PEAK_TBS
+W, H, CLIP_FRAMES = ib.W, ib.H, ib.CLIP_FRAMES
 VARIANTS = [("picture", True, False), ("sums", False, True), ("both", True, True)]
+LAUNCHES = 6      # per variant and format in the traced child: a warm-up and five timed
 
 
 def egress_bytes(width, height, picture, sums):
@@ -43,92 +39,69 @@ def egress_bytes(width, height, picture, sums):
     return 3.0 * wh + (3.0 * wh if sums else 0.0) + (1.5 * wh if picture else 0.0)
 
 
-def declare(lib, Picture):
-    P, I = C.c_void_p, C.c_int
-    lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
-    lib.hmr_gpu_enc_export_references8.argtypes = [C.POINTER(P), I, P, C.c_long, P]
-    lib.hmr_gpu_enc_reference_bytes.restype = C.c_long
-    lib.hmr_gpu_enc_reference_bytes.argtypes = [P]
-    lib.hmr_gpu_enc_state_bytes.restype = C.c_int
-
-
-def export_device(lib, Picture, encs, pics, slot, sums, torch):
+def export_device(lib, encs, pics, slot, sums):
+    from homerhevc_amd.encoder import Picture
     S = len(encs)
     assert lib.hmr_gpu_enc_export_pictures_device((C.c_void_p * S)(*encs), S, (Picture * S)(*pics) if pics is not None else None,
                                                   (C.c_int * S)(*([slot] * S)) if sums is not None else None, C.c_void_p(sums.data_ptr()) if sums is not None else None,
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0, lib.hmr_gpu_last_error()
+                                                  pb.stream_of()) == 0, lib.hmr_gpu_last_error()
 
 
-def outputs(torch, Picture, S, i420):
+def outputs(torch, S):
     """an output picture of its own per sequence, as I420 and as NV12 descriptors of the same memory"""
     outs = [torch.empty(W * H * 3 // 2, dtype=torch.uint8, device="cuda") for _ in range(S)]
-
-    def nv12(t):
-        p = Picture(format=1, reserved=0)
-        p.plane[0], p.plane[1] = t.data_ptr(), t.data_ptr() + W * H
-        p.pitch[0], p.pitch[1] = W, W
-        return p
-    return outs, [i420(t) for t in outs], [nv12(t) for t in outs]
+    return outs, [ib.i420(t) for t in outs], [pb.nv12_picture(t, W, H) for t in outs]
 
 
-def encode_one_step(lib, encs, slot):
-    S = len(encs)
-    bufs = [C.create_string_buffer(4 << 20) for _ in range(S)]
-    e_arr = (C.c_void_p * S)(*encs)
-    ptrs = (C.c_char_p * S)(*[C.cast(b, C.c_char_p) for b in bufs])
-    caps = (C.c_long * S)(*[len(b) for b in bufs])
-    got = (C.c_long * S)()
-    return bufs, e_arr, ptrs, caps, got
+def encoded_once(S):
+    """what the egress and SSIM kernel children begin with: every sequence has encoded one picture of the clips (a picture the encoder is known to take; every sequence
+    has planes of its own) from slot 0"""
+    torch, lib, made, clips, dev = ib.setup(S, with_clips=True)
+    encs = [e for _, e in made]
+    ib.load_device(lib, encs, 0, [ib.i420(dev[i % len(dev)][0]) for i in range(S)])
+    ib.Streams(lib, encs).encode(lib.hmr_gpu_enc_encode_batch, 0)
+    return torch, lib, made, encs
 
 
 def kernel_child(S):
     """the traced program: every sequence encodes one picture, then per variant and format a warm-up launch and five timed ones over the S pictures"""
-    torch, lib, Picture, encs, ctxs, clips, dev, i420 = ib.setup(S, with_clips=True)      # (the clips: a picture the encoder is known to take; every sequence has planes of its own)
-    declare(lib, Picture)
-    ib.load_device(lib, Picture, encs, 0, [i420(dev[i % len(dev)][0]) for i in range(S)], torch)
-    bufs, e_arr, ptrs, caps, got = encode_one_step(lib, encs, 0)
-    lib.hmr_gpu_enc_encode_batch.argtypes = lib.hmr_gpu_enc_encode_batch_pipelined.argtypes
-    assert lib.hmr_gpu_enc_encode_batch(e_arr, S, (C.c_int * S)(*([0] * S)), None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
-    outs, as_i420, as_nv12 = outputs(torch, Picture, S, i420)
+    torch, lib, made, encs = encoded_once(S)
+    outs, as_i420, as_nv12 = outputs(torch, S)
     sums = torch.zeros((S, 3), dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
     for pics in (as_i420, as_nv12):
         for _, picture, with_sums in VARIANTS:
-            for _ in range(6):
-                export_device(lib, Picture, encs, pics if picture else None, 0, sums if with_sums else None, torch)
+            for _ in range(LAUNCHES):
+                export_device(lib, encs, pics if picture else None, 0, sums if with_sums else None)
                 torch.cuda.synchronize()
-    for e, c in zip(encs, ctxs):
-        lib.hmr_gpu_enc_destroy(e)
-        lib.hmr_gpu_destroy(c)
+    pb.close(lib, made)
 
 
 def kernel_rate(S):
-    with tempfile.TemporaryDirectory(prefix="egress_prof_") as out:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "egress", "--", sys.executable, os.path.abspath(__file__), "--kernel-child",
-               "--sequences", str(S)]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        if r.returncode != 0:
-            return {"error": f"rocprofv3 run failed ({r.returncode})", "stderr_tail": r.stderr[-1500:]}
-        traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
-        if not traces:
-            return {"error": "no kernel trace written", "files": sorted(os.listdir(out))}
-        rows = [r for r in csv.DictReader(open(traces[0])) if "k_egress" in r["Kernel_Name"]]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows]
-    if len(us) != 36:
-        return {"error": f"{len(us)} launches of k_egress in the trace, 36 expected", "us": us}
-    res = {"command": "rocprofv3 --kernel-trace --stats --output-format csv -d TRACE_DIR -o egress -- python tools/egress_bench.py --kernel-child --sequences " + str(S),
-           "pictures_per_launch": S, "output_pictures": "one tensor per sequence", "bytes_formula": "3 W H read + 3 W H read (sums) + 1.5 W H written (picture), per picture"}
-    k = 0
-    for fmt in ("i420", "nv12"):
-        for name, picture, with_sums in VARIANTS:
-            part = us[k + 1:k + 6]
-            k += 6
-            med, nbytes = statistics.median(part), egress_bytes(W, H, picture, with_sums) * S
-            tbs = nbytes / (med * 1e-6) / 1e12
-            res[f"{fmt}_{name}"] = {"bytes_per_launch": nbytes, "launch_us": [round(x, 1) for x in part], "median_us": round(med, 1), "tb_per_s": round(tbs, 3),
-                                    "share_of_float4_copy_6.29": round(tbs / COPY_PEAK_TBS, 3)}
+    rows, command = pb.traced_child(__file__, ["--sequences", str(S)], "egress")
+    groups = pb.launch_groups(rows, "k_egress", 2 * len(VARIANTS), LAUNCHES)
+    if isinstance(groups, dict):
+        return groups
+    res = {"command": command, "pictures_per_launch": S, "output_pictures": "one tensor per sequence",
+           "bytes_formula": "3 W H read + 3 W H read (sums) + 1.5 W H written (picture), per picture"}
+    names = [(fmt, variant) for fmt in ("i420", "nv12") for variant in VARIANTS]
+    for (fmt, (name, picture, with_sums)), part in zip(names, groups):
+        nbytes = egress_bytes(W, H, picture, with_sums) * S
+        res[f"{fmt}_{name}"] = pb.rate(part, nbytes, bytes_per_launch=nbytes)
     return res
+
+
+def bench_runs(result, a):
+    """the bench section of the egress and SSIM tools: the last line of every file, their median and spread"""
+    for name, paths in (("this_build", a.bench_this), ("parent", a.bench_parent)):
+        runs = pb.last_bench_lines(paths)
+        if runs:
+            values = [r["value"] for r in runs]
+            result.setdefault("bench", {})[name] = {"runs": runs, "median": statistics.median(values), "spread": round(max(values) - min(values), 4)}
+    if "bench" not in result:
+        result["bench"] = "not measured"
+    if a.notes and os.path.exists(a.notes):
+        result["notes"] = [ln.strip() for ln in open(a.notes) if ln.strip()]
 
 
 def main():
@@ -157,26 +130,26 @@ def main():
         ingest = ib.kernel_rate(S)
         result["kernel_rate"]["yardsticks"] = {"k_ingest_same_visit": {k: ingest.get(k) for k in ("i420", "nv12", "error") if k in ingest},
                                                "k_ingest_profiles_ingest_bench_json_tb_per_s": {"i420": 4.94, "nv12": 5.27}, "float4_copy_tb_per_s": COPY_PEAK_TBS}
-    torch, lib, Picture, encs, ctxs, clips, dev, i420 = ib.setup(S, with_clips=True)
-    declare(lib, Picture)
+    torch, lib, made, clips, dev = ib.setup(S, with_clips=True)
+    encs = [e for _, e in made]
     sync = torch.cuda.synchronize
     nclip = len(clips)
-    pics = [[i420(dev[i % nclip][f]) for i in range(S)] for f in range(CLIP_FRAMES)]
+    pics = [[ib.i420(dev[i % nclip][f]) for i in range(S)] for f in range(CLIP_FRAMES)]
     for s in (0, 1):
-        ib.load_device(lib, Picture, encs, s, pics[0], torch)
-    bufs, e_arr, ptrs, caps, got = encode_one_step(lib, encs, 0)
+        ib.load_device(lib, encs, s, pics[0])
+    streams = ib.Streams(lib, encs)
     frame = [0]
 
     def step(export):
         f = frame[0] % CLIP_FRAMES
         frame[0] += 1
         slot = frame[0] & 1
-        ib.load_device(lib, Picture, encs, slot, pics[f], torch)
-        assert lib.hmr_gpu_enc_encode_batch_pipelined(e_arr, S, (C.c_int * S)(*([slot] * S)), None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
+        ib.load_device(lib, encs, slot, pics[f])
+        streams.encode(lib.hmr_gpu_enc_encode_batch_pipelined, slot)
         if export:
-            export_device(lib, Picture, encs, as_i420, slot, sums, torch)
+            export_device(lib, encs, as_i420, slot, sums)
 
-    outs, as_i420, as_nv12 = outputs(torch, Picture, S, i420)
+    outs, as_i420, as_nv12 = outputs(torch, S)
     sums = torch.zeros((S, 3), dtype=torch.int64, device="cuda")
     for _ in range(CLIP_FRAMES // 2):      # steady state: the pool's buffers, the staging buffers, both paths' first calls; one round of the clip
         step(False)
@@ -191,37 +164,26 @@ def main():
     for rep in range(5):
         sync()
         t0 = time.perf_counter()
-        assert lib.hmr_gpu_enc_export_references8(e_arr, S, C.c_void_p(rows8.data_ptr()), nb, states) == 0, lib.hmr_gpu_last_error()
+        assert lib.hmr_gpu_enc_export_references8(streams.encs, S, C.c_void_p(rows8.data_ptr()), nb, states) == 0, lib.hmr_gpu_last_error()
         sync()
         old_ms.append((time.perf_counter() - t0) * 1e3)
         t0 = time.perf_counter()
-        export_device(lib, Picture, encs, as_i420, 0, None, torch)
+        export_device(lib, encs, as_i420, 0, None)
         t1 = time.perf_counter()
         sync()
         new_ms.append((time.perf_counter() - t0) * 1e3)
         returns_ms.append(round((t1 - t0) * 1e3, 3))
     same = all(bool(torch.equal(rows8[i], outs[i])) for i in range(S))
     result["replaces"] = {"what": f"one 8-bit picture of each of {S} sequences left in device memory, wall ms between device synchronisations, alternating",
-                          "hmr_gpu_enc_export_references8_ms": ib.spread(old_ms), "hmr_gpu_enc_export_pictures_device_ms": ib.spread(new_ms),
+                          "hmr_gpu_enc_export_references8_ms": spread(old_ms), "hmr_gpu_enc_export_pictures_device_ms": spread(new_ms),
                           "export_pictures_device_call_returns_after_ms": returns_ms, "both_left_the_same_pictures": same,
                           "ratio_of_medians": round(statistics.median(old_ms) / statistics.median(new_ms), 1)}
 
-    def window(export):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step(export)
-        sync()
-        return (time.perf_counter() - t0) * 1e3 / a.steps
-
-    plain, exporting = [], []
-    for _ in range(3):
-        plain.append(window(False))
-        exporting.append(window(True))
-    assert lib.hmr_gpu_enc_encode_batch_pipelined(e_arr, S, None, None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
+    plain, exporting = ib.windows(torch, a.steps, step)
+    streams.encode(lib.hmr_gpu_enc_encode_batch_pipelined, None)
     kr = result["kernel_rate"]
     kernel_ms = kr["i420_both"]["median_us"] / 1e3 if "i420_both" in kr else None
-    sp, se = ib.spread(plain), ib.spread(exporting)
+    sp, se = spread(plain), spread(exporting)
     result["streaming_step"] = {"steps_per_window": a.steps, "pictures": f"every step ingests a fresh device picture per sequence (the clips' {CLIP_FRAMES} pictures in turn) and encodes it",
                                 "plain_ms_per_step": sp, "with_export_ms_per_step": se, "egress_kernel_ms": kernel_ms}
     if kernel_ms is not None:
@@ -229,28 +191,9 @@ def main():
         result["streaming_step"].update({"bound_ms": round(bound, 3), "condition": "median with export <= median plain + egress kernel + spread of plain", "holds": bool(se["median"] <= bound)})
     else:
         result["streaming_step"]["holds"] = "not measured (no kernel time)"
-    for name, paths in (("this_build", a.bench_this), ("parent", a.bench_parent)):
-        runs = []
-        for path in paths:
-            lines = [ln for ln in open(path).read().splitlines() if ln.startswith("{")] if os.path.exists(path) else []
-            if lines:
-                b = json.loads(lines[-1])
-                runs.append({k: b.get(k) for k in ("value", "unit", "ms_per_step", "steps", "warmup", "build")})
-        if runs:
-            values = [r["value"] for r in runs]
-            result.setdefault("bench", {})[name] = {"runs": runs, "median": statistics.median(values), "spread": round(max(values) - min(values), 4)}
-    if "bench" not in result:
-        result["bench"] = "not measured"
-    if a.notes and os.path.exists(a.notes):
-        result["notes"] = [ln.strip() for ln in open(a.notes) if ln.strip()]
-    for e, c in zip(encs, ctxs):
-        lib.hmr_gpu_enc_destroy(e)
-        lib.hmr_gpu_destroy(c)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(result))
+    bench_runs(result, a)
+    pb.close(lib, made)
+    pb.write_result(result, a.out)
 
 
 if __name__ == "__main__":

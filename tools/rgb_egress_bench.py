@@ -13,25 +13,19 @@
                 are recorded without a gate.
   resources     the compiler's resource report for the kernel (hipcc -Rpass-analysis=kernel-resource-usage), when hipcc is there."""
 import argparse
-import csv
 import ctypes as C
-import glob
 import json
 import os
-import re
-import shutil
-import statistics
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+import egress_bench as eb  # noqa: E402  (the kernel child's first step and the yardstick's launches)
 import ingest_bench as ib  # noqa: E402  (the workload and the encoders' set-up)
+import picture_bench  # noqa: E402
 
-W, H, COPY_PEAK_TBS = ib.W, ib.H, ib.COPY_PEAK_TBS
+W, H = ib.W, ib.H
+
 PACKED8, PLANAR8, PLANAR_F16, PLANAR_F32 = 0, 1, 2, 3
 # form -> (format, pixel bytes, byte of R, G, B)
 FORMS = {"rgb": (PACKED8, 3, (0, 1, 2)), "rgba": (PACKED8, 4, (0, 1, 2)), "planar8": (PLANAR8, 0, (0, 0, 0)), "f16": (PLANAR_F16, 0, (0, 0, 0)), "f32": (PLANAR_F32, 0, (0, 0, 0))}
@@ -85,25 +79,17 @@ def pictures(torch, RgbPicture, S, form, random):
 def kernel_child(S):
     """the traced program: every sequence encodes one picture, then LAUNCHES launches of k_egress (I420 pictures) and LAUNCHES of k_egress_rgb per variant over the S final
     pictures"""
-    import egress_bench as eb
-    from homerhevc_amd.encoder import RgbPicture
-    torch, lib, Picture, encs, ctxs, clips, dev, i420 = ib.setup(S, with_clips=True)
-    eb.declare(lib, Picture)
-    P, I = C.c_void_p, C.c_int
-    lib.hmr_gpu_enc_export_pictures_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), C.POINTER(RgbPicture), P, P]
-    ib.load_device(lib, Picture, encs, 0, [i420(dev[i % len(dev)][0]) for i in range(S)], torch)
-    bufs, e_arr, ptrs, caps, got = eb.encode_one_step(lib, encs, 0)
-    lib.hmr_gpu_enc_encode_batch.argtypes = lib.hmr_gpu_enc_encode_batch_pipelined.argtypes
-    assert lib.hmr_gpu_enc_encode_batch(e_arr, S, (C.c_int * S)(*([0] * S)), None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
-    outs, as_i420, as_nv12 = eb.outputs(torch, Picture, S, i420)
+    from rgb_cases import RgbPicture
+    torch, lib, made, encs = eb.encoded_once(S)
+    outs, as_i420, as_nv12 = eb.outputs(torch, S)
     sums = torch.zeros((S, 3), dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
     print("encoded one picture per sequence; k_egress", flush=True)
     for _ in range(LAUNCHES):
-        eb.export_device(lib, Picture, encs, as_i420, 0, None, torch)
+        eb.export_device(lib, encs, as_i420, 0, None)
         torch.cuda.synchronize()
     del outs
-    which = (C.c_int * S)(*([-1] * S))
+    e_arr, which = (C.c_void_p * S)(*encs), (C.c_int * S)(*([-1] * S))
     for name, out_form, ref_form in VARIANTS:
         out_t, out_pics = pictures(torch, RgbPicture, S, out_form, False) if out_form else (None, None)
         ref_t, ref_pics = pictures(torch, RgbPicture, S, ref_form, True) if ref_form else (None, None)
@@ -111,64 +97,30 @@ def kernel_child(S):
         print("k_egress_rgb:", name, flush=True)
         for _ in range(LAUNCHES):
             assert lib.hmr_gpu_enc_export_pictures_rgb_device(e_arr, S, which, (RgbPicture * S)(*out_pics) if out_pics else None, (RgbPicture * S)(*ref_pics) if ref_pics else None,
-                                                              C.c_void_p(sums.data_ptr()) if ref_pics else None, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0, lib.hmr_gpu_last_error()
+                                                              C.c_void_p(sums.data_ptr()) if ref_pics else None, picture_bench.stream_of()) == 0, lib.hmr_gpu_last_error()
             torch.cuda.synchronize()
         del out_t, ref_t
-    for e, c in zip(encs, ctxs):
-        lib.hmr_gpu_enc_destroy(e)
-        lib.hmr_gpu_destroy(c)
+    picture_bench.close(lib, made)
 
 
 def kernel_rate(S):
-    with tempfile.TemporaryDirectory(prefix="rgb_egress_prof_") as out:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "rgb_egress", "--", sys.executable, os.path.abspath(__file__), "--kernel-child",
-               "--sequences", str(S)]
-        with open(os.path.join(out, "stderr.txt"), "w") as err:      # (the child's progress lines go to this program's output as they come)
-            r = subprocess.run(cmd, stderr=err, timeout=1100)
-        if r.returncode != 0:
-            return {"error": f"rocprofv3 run failed ({r.returncode})", "stderr_tail": open(os.path.join(out, "stderr.txt")).read()[-1500:]}
-        traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
-        if not traces:
-            return {"error": "no kernel trace written", "files": sorted(os.listdir(out))}
-        rows = [r for r in csv.DictReader(open(traces[0])) if "k_egress" in r["Kernel_Name"]]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    us = lambda part: [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in part]
-    rgb, plain = us([r for r in rows if "k_egress_rgb" in r["Kernel_Name"]]), us([r for r in rows if "k_egress_rgb" not in r["Kernel_Name"]])
-    if len(rgb) != LAUNCHES * len(VARIANTS) or len(plain) != LAUNCHES:
-        return {"error": f"{len(rgb)} launches of k_egress_rgb and {len(plain)} of k_egress in the trace, {LAUNCHES * len(VARIANTS)} and {LAUNCHES} expected", "us": rgb, "k_egress_us": plain}
-
-    def record(part, nbytes):
-        med = statistics.median(part)
-        tbs = nbytes / (med * 1e-6) / 1e12
-        return {"bytes_per_launch": nbytes, "launch_us": [round(x, 1) for x in part], "median_us": round(med, 1), "tb_per_s": round(tbs, 3), "share_of_float4_copy_6.29": round(tbs / COPY_PEAK_TBS, 3)}
-
-    res = {"command": "rocprofv3 --kernel-trace --stats --output-format csv -d TRACE_DIR -o rgb_egress -- python tools/rgb_egress_bench.py --kernel-child --sequences " + str(S),
-           "pictures_per_launch": S, "source": "the encoders' final pictures (which = -1)", "output_pictures": "one picture per sequence, BT.709 limited range",
+    rows, command = picture_bench.traced_child(__file__, ["--sequences", str(S)], "rgb_egress", timeout=1100, show_progress=True)
+    plain = picture_bench.launch_groups(rows, "k_egress", 1, LAUNCHES)
+    rgb = picture_bench.launch_groups(rows, "k_egress_rgb", len(VARIANTS), LAUNCHES)
+    for groups in (plain, rgb):
+        if isinstance(groups, dict):
+            return groups
+    res = {"command": command, "pictures_per_launch": S, "source": "the encoders' final pictures (which = -1)", "output_pictures": "one picture per sequence, BT.709 limited range",
            "bytes_formula": "3 W H read + the reference form's bytes read (sums) + the output form's bytes written: 3 / 4 / 3 / 6 / 12 W H for rgb / rgba / planar8 / f16 / f32"}
-    yard = record(plain[1:], (3.0 + 1.5) * W * H * S)
+    yard = picture_bench.rate(plain[0], (3.0 + 1.5) * W * H * S, bytes_per_launch=(3.0 + 1.5) * W * H * S)
     res["yardstick_k_egress_i420_picture_same_visit"] = dict(yard, profiles_egress_bench_json_tb_per_s=5.08)
-    for k, (name, out_form, ref_form) in enumerate(VARIANTS):
-        res[name] = record(rgb[LAUNCHES * k + 1:LAUNCHES * (k + 1)], egress_rgb_bytes(W, H, out_form, ref_form) * S)
+    for (name, out_form, ref_form), part in zip(VARIANTS, rgb):
+        nbytes = egress_rgb_bytes(W, H, out_form, ref_form) * S
+        res[name] = picture_bench.rate(part, nbytes, bytes_per_launch=nbytes)
         res[name]["ratio_to_yardstick"] = round(res[name]["tb_per_s"] / yard["tb_per_s"], 3)
     res["gate"] = {"condition": f"bytes per second of {', '.join(GATED)} (no sums) >= {GATE} x the yardstick's", "ratios": {n: res[n]["ratio_to_yardstick"] for n in GATED},
                    "holds": all(res[n]["tb_per_s"] >= GATE * yard["tb_per_s"] for n in GATED)}
     return res
-
-
-def resources():
-    """the compiler's resource report for k_egress_rgb"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        return {"skipped": "no hipcc"}
-    with tempfile.TemporaryDirectory(prefix="rgb_egress_isa_") as out:
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S",
-                            "-o", os.path.join(out, "picture_io.s"), os.path.join(ROOT, "homerhevc_amd", "csrc", "picture_io.hip")], capture_output=True, text=True, timeout=600)
-    if r.returncode != 0:
-        return {"error": r.stderr[-800:]}
-    for blk in r.stderr.split("Function Name: ")[1:]:
-        if "k_egress_rgb" in blk.split()[0]:
-            return {k: int(v) for k, v in re.findall(r"(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\d+)", blk)}
-    return {"error": "k_egress_rgb is not in the report"}
 
 
 def main():
@@ -186,15 +138,11 @@ def main():
               "configuration": "bench.py cfg2-1080p-encode (wfpp_num_threads 17)",
               "algorithmic_bytes_per_picture": {name: egress_rgb_bytes(W, H, o, r) for name, o, r in VARIANTS}}
     result["kernel_rate"] = kernel_rate(a.sequences)
-    res = resources()
+    res = picture_bench.resources("k_egress_rgb")
     result["notes"] = [f"compiler's resource report for k_egress_rgb (hipcc -O3, gfx950): {json.dumps(res)}"]
     if a.notes and os.path.exists(a.notes):
         result["notes"] += [ln.strip() for ln in open(a.notes) if ln.strip()]
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(result))
+    picture_bench.write_result(result, a.out)
 
 
 if __name__ == "__main__":

@@ -17,24 +17,20 @@
   bench         bench.py's line of this build and of the parent commit's, when their files are given (alternating runs of the same GPU visit)
 Timed windows are walls between two device synchronisations, in one process with the steady state warmed first."""
 import argparse
-import csv
 import ctypes as C
-import glob
-import json
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+import picture_bench as pb  # noqa: E402
+from picture_bench import COPY_PEAK_TBS, spread  # noqa: E402
+from scale_ingest_bench import ladder_bench  # noqa: E402
+
 WORKLOADS = {"ladder_1080p_f16_x3": {"source": (1920, 1080), "form": "f16", "pixel_bytes": 6, "rungs": [(1280, 720), (960, 544), (640, 360)]},
              "2160p_rgba_to_1080p": {"source": (3840, 2160), "form": "rgba", "pixel_bytes": 4, "rungs": [(1920, 1080)]}}
-COPY_PEAK_TBS = 6.29          # float4 copy, measured (the figure the other profile files use)
-
+LAUNCHES = 6                  # per workload in the traced child: a warm-up and five timed
 
 def rgb_scale_bytes(src, dst, pixel_bytes):
     """the formula in the comment at k_rgb_ladder (csrc/picture_io.hip)"""
@@ -54,96 +50,61 @@ class Setup:
 
     def __init__(self, n_sources, names, composition):
         import torch
-        import encoder_cases as ec
-        import libs
-        from homerhevc_amd.encoder import Picture, RgbPicture, ScaledPicture, ScaledRgbPicture
-        self.torch, self.n = torch, n_sources
-        self.Picture, self.RgbPicture, self.ScaledPicture, self.ScaledRgbPicture = Picture, RgbPicture, ScaledPicture, ScaledRgbPicture
-        self.lib = lib = libs.load_gpu()
-        P, I = C.c_void_p, C.c_int
-        lib.hmr_gpu_last_error.restype = C.c_char_p
-        lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-        lib.hmr_gpu_destroy.argtypes = [P]
-        lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-        lib.hmr_gpu_enc_destroy.argtypes = [P]
-        lib.hmr_gpu_enc_load_sources_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), P]
-        lib.hmr_gpu_enc_load_sources_scaled_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledPicture), P]
-        lib.hmr_gpu_enc_load_sources_scaled_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledRgbPicture), P]
-        lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-        self.made = []
-        self.work = {}
+        import rgb_cases as rc
+        import rgb_scale_cases as rs
+        import scale_cases as sc
+        from homerhevc_amd.encoder import Picture
+        self.torch, self.n, self.lib, self.made, self.work = torch, n_sources, pb.library(), [], {}
+        self.structs = {"hmr_gpu_enc_load_sources_rgb_device": rc.RgbPicture, "hmr_gpu_enc_load_sources_scaled_device": sc.ScaledPicture,
+                        "hmr_gpu_enc_load_sources_scaled_rgb_device": rs.ScaledRgbPicture, "hmr_gpu_enc_export_sources_device": Picture}
         for name in names:
             wl = WORKLOADS[name]
             w, h = wl["source"]
             if wl["form"] == "f16":      # (the kernel's time does not depend on the samples; a tensor of its own per source)
                 srcs = [torch.rand((3, h, w), dtype=torch.float16, device="cuda") for _ in range(n_sources)]
+                rgb = [rc.descriptor(rc.RGB_PLANAR_F16, 0, (0, 0, 0), [t.data_ptr() + 2 * c * w * h for c in range(3)], [2 * w] * 3, "bt709", 0) for t in srcs]
             else:
                 srcs = [torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda") for _ in range(n_sources)]
-            rung_encs = [self.encoder(ec, *r) for _ in range(n_sources) for r in wl["rungs"]]
-            rgb = [self.rgb_picture(t, wl["form"], w, h) for t in srcs]
+                rgb = [rc.descriptor(rc.RGB_PACKED8, 4, (0, 1, 2), [t.data_ptr()], [4 * w], "bt709", 0) for t in srcs]
+            rung_encs = [self.encoder(*r) for _ in range(n_sources) for r in wl["rungs"]]
             entry = {"srcs": srcs, "rung_encs": rung_encs, "rgb": rgb,
-                     "scaled_rgb": [ScaledRgbPicture(pic=rgb[k // len(wl["rungs"])], width=w, height=h) for k in range(len(rung_encs))]}
+                     "scaled_rgb": [rs.ScaledRgbPicture(pic=rgb[k // len(wl["rungs"])], width=w, height=h) for k in range(len(rung_encs))]}
             if composition:
-                entry["top_encs"] = [self.encoder(ec, w, h) for _ in range(n_sources)]
+                entry["top_encs"] = [self.encoder(w, h) for _ in range(n_sources)]
                 entry["mid"] = [torch.empty((h * 3 // 2, w), dtype=torch.uint8, device="cuda") for _ in range(n_sources)]
-                entry["mid_pics"] = [self.i420(t, w, h) for t in entry["mid"]]
-                entry["scaled"] = [ScaledPicture(pic=entry["mid_pics"][k // len(wl["rungs"])], width=w, height=h) for k in range(len(rung_encs))]
+                entry["mid_pics"] = [pb.i420_picture(t, w, h) for t in entry["mid"]]
+                planes = lambda t: [t.data_ptr(), t.data_ptr() + w * h, t.data_ptr() + w * h * 5 // 4]
+                entry["scaled"] = [sc.descriptor(0, planes(entry["mid"][k // len(wl["rungs"])]), [w, w // 2, w // 2], w, h) for k in range(len(rung_encs))]
             self.work[name] = entry
         torch.cuda.synchronize()
 
-    def encoder(self, ec, w, h):
-        ctx, enc = C.c_void_p(), C.c_void_p()
-        assert self.lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, self.lib.hmr_gpu_last_error()
-        assert self.lib.hmr_gpu_enc_create(ctx, C.byref(ec.default_cfg(w, h)), C.byref(enc)) == 0, self.lib.hmr_gpu_last_error()
-        self.made.append((ctx, enc))
-        return enc
+    def encoder(self, w, h):
+        self.made += pb.encoders(self.lib, 1, w, h)
+        return self.made[-1][1]
 
-    def rgb_picture(self, t, form, w, h):
-        p = self.RgbPicture(matrix=1, full_range=0, reserved=0)
-        if form == "f16":
-            p.format, p.pixel_bytes = 2, 0
-            for c in range(3):
-                p.plane[c], p.pitch[c] = t.data_ptr() + 2 * c * w * h, 2 * w
-        else:
-            p.format, p.pixel_bytes = 0, 4
-            p.offset[0], p.offset[1], p.offset[2] = 0, 1, 2
-            p.plane[0], p.pitch[0] = t.data_ptr(), 4 * w
-        return p
-
-    def i420(self, t, w, h):
-        p = self.Picture(format=0, reserved=0)
-        p.plane[0], p.plane[1], p.plane[2] = t.data_ptr(), t.data_ptr() + w * h, t.data_ptr() + w * h * 5 // 4
-        p.pitch[0], p.pitch[1], p.pitch[2] = w, w // 2, w // 2
-        return p
-
-    def stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
-
-    def call(self, name, encs, pics, struct):
+    def call(self, name, encs, pics):
         n = len(encs)
-        assert getattr(self.lib, name)((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([0] * n)), (struct * n)(*pics), self.stream()) == 0, self.lib.hmr_gpu_last_error()
+        assert getattr(self.lib, name)((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([0] * n)), (self.structs[name] * n)(*pics), pb.stream_of()) == 0, self.lib.hmr_gpu_last_error()
 
     def new_call(self, name):
         e = self.work[name]
-        self.call("hmr_gpu_enc_load_sources_scaled_rgb_device", e["rung_encs"], e["scaled_rgb"], self.ScaledRgbPicture)
+        self.call("hmr_gpu_enc_load_sources_scaled_rgb_device", e["rung_encs"], e["scaled_rgb"])
 
     def composition(self, name):
         e = self.work[name]
-        self.call("hmr_gpu_enc_load_sources_rgb_device", e["top_encs"], e["rgb"], self.RgbPicture)
-        self.call("hmr_gpu_enc_export_sources_device", e["top_encs"], e["mid_pics"], self.Picture)
-        self.call("hmr_gpu_enc_load_sources_scaled_device", e["rung_encs"], e["scaled"], self.ScaledPicture)
+        self.call("hmr_gpu_enc_load_sources_rgb_device", e["top_encs"], e["rgb"])
+        self.call("hmr_gpu_enc_export_sources_device", e["top_encs"], e["mid_pics"])
+        self.call("hmr_gpu_enc_load_sources_scaled_device", e["rung_encs"], e["scaled"])
 
     def close(self):
-        for ctx, enc in self.made:
-            self.lib.hmr_gpu_enc_destroy(enc)
-            self.lib.hmr_gpu_destroy(ctx)
+        pb.close(self.lib, self.made)
 
 
 def kernel_child(n_sources):
     """the traced program: per workload a warm-up launch and five timed ones"""
     for name in WORKLOADS:      # (one workload's tensors at a time: 64 2160p RGBA sources are 2.1 GB)
         s = Setup(n_sources, [name], composition=False)
-        for _ in range(6):
+        for _ in range(LAUNCHES):
             s.new_call(name)
             s.torch.cuda.synchronize()
         s.close()
@@ -151,34 +112,17 @@ def kernel_child(n_sources):
 
 
 def kernel_rate(n_sources):
-    with tempfile.TemporaryDirectory(prefix="rgb_scale_prof_") as out:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "rgb_scale", "--", sys.executable, os.path.abspath(__file__), "--kernel-child",
-               "--sources", str(n_sources)]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        if r.returncode != 0:
-            return {"error": f"rocprofv3 run failed ({r.returncode})", "stderr_tail": r.stderr[-1500:]}
-        traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
-        if not traces:
-            return {"error": "no kernel trace written", "files": sorted(os.listdir(out))}
-        rows = [r for r in csv.DictReader(open(traces[0])) if "k_rgb_ladder" in r["Kernel_Name"]]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows]
-    if len(us) != 12:
-        return {"error": f"{len(us)} launches of k_rgb_ladder in the trace, 12 expected", "us": us}
-    res = {"command": "rocprofv3 --kernel-trace --stats --output-format csv -d TRACE_DIR -o rgb_scale -- python tools/rgb_scale_ingest_bench.py --kernel-child --sources " + str(n_sources),
-           "yardsticks": {"float4_copy_tb_per_s": COPY_PEAK_TBS}}
-    for k, (name, wl) in enumerate(WORKLOADS.items()):
-        part = us[6 * k + 1:6 * k + 6]
+    rows, command = pb.traced_child(__file__, ["--sources", str(n_sources)], "rgb_scale")
+    groups = pb.launch_groups(rows, "k_rgb_ladder", len(WORKLOADS), LAUNCHES)
+    if isinstance(groups, dict):
+        return groups
+    res = {"command": command, "yardsticks": {"float4_copy_tb_per_s": COPY_PEAK_TBS}}
+    for (name, wl), part in zip(WORKLOADS.items(), groups):
         nbytes = n_sources * sum(rgb_scale_bytes(wl["source"], r, wl["pixel_bytes"]) for r in wl["rungs"])
-        med = statistics.median(part)
-        tbs = nbytes / (med * 1e-6) / 1e12
-        res[name] = {"jobs_per_launch": n_sources * len(wl["rungs"]), "bytes_per_launch": nbytes, "launch_us": [round(x, 1) for x in part], "median_us": round(med, 1),
-                     "gb_per_s": round(tbs * 1e3, 1), "share_of_float4_copy_6.29": round(tbs / COPY_PEAK_TBS, 3)}
+        record = pb.rate(part, nbytes, jobs_per_launch=n_sources * len(wl["rungs"]), bytes_per_launch=nbytes)
+        record["tb_per_s"] = round(pb.tb_per_s(part, nbytes) * 1e3, 1)      # (this file has always recorded GB/s)
+        res[name] = {"gb_per_s" if k == "tb_per_s" else k: v for k, v in record.items()}
     return res
-
-
-def spread(xs):
-    return {"runs": [round(x, 3) for x in xs], "median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3), "spread": round(max(xs) - min(xs), 3)}
 
 
 def replaces(n_sources, name):
@@ -234,24 +178,8 @@ def main():
     result["kernel_rate"] = {"skipped": True} if a.no_kernel_rate else kernel_rate(N)
     result["replaces"] = {name: replaces(N, name) for name in WORKLOADS}
     result["replaces"]["expected"] = "2160p_rgba_to_1080p: the new call is not slower than the composition; ladder_1080p_f16_x3: either may win (the composition converts once)"
-    for name, paths in (("this_build", a.bench_this), ("parent", a.bench_parent)):
-        runs = []
-        for path in paths:
-            lines = [ln for ln in open(path).read().splitlines() if ln.startswith("{")] if os.path.exists(path) else []
-            if lines:
-                b = json.loads(lines[-1])
-                runs.append({k: b.get(k) for k in ("value", "unit", "ms_per_step", "steps", "warmup", "build")})
-        if runs:
-            result.setdefault("bench", {})[name] = {"runs": runs, "frames_per_s": spread([r["value"] for r in runs])}
-    if set(result.get("bench", {})) == {"this_build", "parent"}:
-        t, p = result["bench"]["this_build"]["frames_per_s"], result["bench"]["parent"]["frames_per_s"]
-        result["bench"]["condition"] = "median of this build >= median of the parent - the parent's run-to-run spread"
-        result["bench"]["holds"] = bool(t["median"] >= p["median"] - p["spread"])
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(result))
+    ladder_bench(result, a)
+    pb.write_result(result, a.out)
 
 
 if __name__ == "__main__":

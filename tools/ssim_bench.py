@@ -12,25 +12,17 @@
   bench            bench.py's lines of this build and of the parent commit's, when the files are given (all from the same GPU visit, alternating)
 Timed windows are walls between two device synchronisations, in one process with the steady state warmed first."""
 import argparse
-import csv
 import ctypes as C
-import glob
-import json
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+import egress_bench as eb  # noqa: E402  (the kernel child's first step, k_egress with sums only, the bench section)
 import ingest_bench as ib  # noqa: E402  (the workload and the encoders' set-up)
-from egress_bench import encode_one_step  # noqa: E402
+import picture_bench as pb  # noqa: E402
 
-W, H, CLIP_FRAMES, COPY_PEAK_TBS = ib.W, ib.H, ib.CLIP_FRAMES, ib.COPY_PEAK_TBS
+W, H, CLIP_FRAMES = ib.W, ib.H, ib.CLIP_FRAMES
 BAR = 1.5
 LAUNCHES = 6      # per kernel in the traced child: a warm-up and five timed
 
@@ -40,68 +32,37 @@ def ssim_bytes(width, height):
     return 6.0 * float(width) * height
 
 
-def declare(lib, Picture):
-    P, I = C.c_void_p, C.c_int
-    lib.hmr_gpu_enc_ssim_device.argtypes = [C.POINTER(P), I, C.POINTER(I), P, P]
-    lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
-
-
-def ssim_device(lib, encs, slot, sums, torch):
+def ssim_device(lib, encs, slot, sums):
     S = len(encs)
-    assert lib.hmr_gpu_enc_ssim_device((C.c_void_p * S)(*encs), S, (C.c_int * S)(*([slot] * S)), C.c_void_p(sums.data_ptr()),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0, lib.hmr_gpu_last_error()
+    assert lib.hmr_gpu_enc_ssim_device((C.c_void_p * S)(*encs), S, (C.c_int * S)(*([slot] * S)), C.c_void_p(sums.data_ptr()), pb.stream_of()) == 0, lib.hmr_gpu_last_error()
 
 
-def ssd_device(lib, encs, slot, sums, torch):
-    S = len(encs)
-    assert lib.hmr_gpu_enc_export_pictures_device((C.c_void_p * S)(*encs), S, None, (C.c_int * S)(*([slot] * S)), C.c_void_p(sums.data_ptr()),
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0, lib.hmr_gpu_last_error()
+def ssd_device(lib, encs, slot, sums):
+    eb.export_device(lib, encs, None, slot, sums)
 
 
 def kernel_child(S):
     """the traced program: every sequence encodes one picture, then LAUNCHES launches of k_ssim and as many of k_egress (sums only) over the S pictures, alternating"""
-    torch, lib, Picture, encs, ctxs, clips, dev, i420 = ib.setup(S, with_clips=True)      # (the clips: a picture the encoder is known to take; every sequence has planes of its own)
-    declare(lib, Picture)
-    ib.load_device(lib, Picture, encs, 0, [i420(dev[i % len(dev)][0]) for i in range(S)], torch)
-    bufs, e_arr, ptrs, caps, got = encode_one_step(lib, encs, 0)
-    lib.hmr_gpu_enc_encode_batch.argtypes = lib.hmr_gpu_enc_encode_batch_pipelined.argtypes
-    assert lib.hmr_gpu_enc_encode_batch(e_arr, S, (C.c_int * S)(*([0] * S)), None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
+    torch, lib, made, encs = eb.encoded_once(S)
     sums = torch.zeros((S, 3), dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
     for _ in range(LAUNCHES):
         for call in (ssim_device, ssd_device):
-            call(lib, encs, 0, sums, torch)
+            call(lib, encs, 0, sums)
             torch.cuda.synchronize()
-    for e, c in zip(encs, ctxs):
-        lib.hmr_gpu_enc_destroy(e)
-        lib.hmr_gpu_destroy(c)
+    pb.close(lib, made)
 
 
 def kernel_rate(S):
-    with tempfile.TemporaryDirectory(prefix="ssim_prof_") as out:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "ssim", "--", sys.executable, os.path.abspath(__file__), "--kernel-child",
-               "--sequences", str(S)]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-        if r.returncode != 0:
-            return {"error": f"rocprofv3 run failed ({r.returncode})", "stderr_tail": r.stderr[-1500:]}
-        traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
-        if not traces:
-            return {"error": "no kernel trace written", "files": sorted(os.listdir(out))}
-        rows = list(csv.DictReader(open(traces[0])))
-    res = {"command": "rocprofv3 --kernel-trace --stats --output-format csv -d TRACE_DIR -o ssim -- python tools/ssim_bench.py --kernel-child --sequences " + str(S),
-           "pictures_per_launch": S, "bytes_formula": "3 W H read (final picture) + 3 W H read (slot), per picture: the same for both kernels",
+    rows, command = pb.traced_child(__file__, ["--sequences", str(S)], "ssim")
+    res = {"command": command, "pictures_per_launch": S, "bytes_formula": "3 W H read (final picture) + 3 W H read (slot), per picture: the same for both kernels",
            "bytes_per_launch": ssim_bytes(W, H) * S}
     for name in ("k_ssim", "k_egress"):
-        mine = sorted((r for r in rows if name in r["Kernel_Name"]), key=lambda r: int(r["Start_Timestamp"]))
-        us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in mine]
-        if len(us) != LAUNCHES:
-            return {"error": f"{len(us)} launches of {name} in the trace, {LAUNCHES} expected", "us": us}
-        part = us[1:]
-        med = statistics.median(part)
-        tbs = res["bytes_per_launch"] / (med * 1e-6) / 1e12
-        res[name if name == "k_ssim" else "k_egress_sums_only"] = {"launch_us": [round(x, 1) for x in part], "median_us": round(med, 1), "tb_per_s": round(tbs, 3),
-                                                                  "share_of_float4_copy_6.29": round(tbs / COPY_PEAK_TBS, 3),
-                                                                  "vgpr_sgpr_lds": [mine[-1].get(k) for k in ("VGPR_Count", "SGPR_Count", "LDS_Block_Size")]}
+        groups = pb.launch_groups(rows, name, 1, LAUNCHES)
+        if isinstance(groups, dict):
+            return groups
+        last = pb.kernel_rows(rows, name)[-1]
+        res[name if name == "k_ssim" else "k_egress_sums_only"] = dict(pb.rate(groups[0], res["bytes_per_launch"]), vgpr_sgpr_lds=[last.get(k) for k in ("VGPR_Count", "SGPR_Count", "LDS_Block_Size")])
     ratio = res["k_ssim"]["median_us"] / res["k_egress_sums_only"]["median_us"]
     res.update({"ratio_k_ssim_to_k_egress_sums_only": round(ratio, 3), "bar": BAR, "within_bar": bool(ratio <= BAR)})
     return res
@@ -132,36 +93,18 @@ def main():
         result["streaming_step"] = {"skipped": True}
     else:
         result["streaming_step"] = streaming_step(S, a.steps, result["kernel_rate"])
-    for name, paths in (("this_build", a.bench_this), ("parent", a.bench_parent)):
-        runs = []
-        for path in paths:
-            lines = [ln for ln in open(path).read().splitlines() if ln.startswith("{")] if os.path.exists(path) else []
-            if lines:
-                b = json.loads(lines[-1])
-                runs.append({k: b.get(k) for k in ("value", "unit", "ms_per_step", "steps", "warmup", "build")})
-        if runs:
-            values = [r["value"] for r in runs]
-            result.setdefault("bench", {})[name] = {"runs": runs, "median": statistics.median(values), "spread": round(max(values) - min(values), 4)}
-    if "bench" not in result:
-        result["bench"] = "not measured"
-    if a.notes and os.path.exists(a.notes):
-        result["notes"] = [ln.strip() for ln in open(a.notes) if ln.strip()]
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(result))
+    eb.bench_runs(result, a)
+    pb.write_result(result, a.out)
 
 
 def streaming_step(S, steps, kr):
-    torch, lib, Picture, encs, ctxs, clips, dev, i420 = ib.setup(S, with_clips=True)
-    declare(lib, Picture)
-    sync = torch.cuda.synchronize
+    torch, lib, made, clips, dev = ib.setup(S, with_clips=True)
+    encs = [e for _, e in made]
     nclip = len(clips)
-    pics = [[i420(dev[i % nclip][f]) for i in range(S)] for f in range(CLIP_FRAMES)]
+    pics = [[ib.i420(dev[i % nclip][f]) for i in range(S)] for f in range(CLIP_FRAMES)]
     for s in (0, 1):
-        ib.load_device(lib, Picture, encs, s, pics[0], torch)
-    bufs, e_arr, ptrs, caps, got = encode_one_step(lib, encs, 0)
+        ib.load_device(lib, encs, s, pics[0])
+    streams = ib.Streams(lib, encs)
     sums = torch.zeros((S, 3), dtype=torch.int64, device="cuda")
     frame = [0]
 
@@ -169,32 +112,20 @@ def streaming_step(S, steps, kr):
         f = frame[0] % CLIP_FRAMES
         frame[0] += 1
         slot = frame[0] & 1
-        ib.load_device(lib, Picture, encs, slot, pics[f], torch)
-        assert lib.hmr_gpu_enc_encode_batch_pipelined(e_arr, S, (C.c_int * S)(*([slot] * S)), None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
+        ib.load_device(lib, encs, slot, pics[f])
+        streams.encode(lib.hmr_gpu_enc_encode_batch_pipelined, slot)
         if with_ssim:
-            ssim_device(lib, encs, slot, sums, torch)
+            ssim_device(lib, encs, slot, sums)
 
     for _ in range(CLIP_FRAMES // 2):      # steady state: the pool's buffers, the staging buffers, both paths' first calls; one round of the clip
         step(False)
         step(True)
-    sync()
-
-    def window(with_ssim):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            step(with_ssim)
-        sync()
-        return (time.perf_counter() - t0) * 1e3 / steps
-
-    plain, measuring = [], []
-    for _ in range(3):
-        plain.append(window(False))
-        measuring.append(window(True))
-    assert lib.hmr_gpu_enc_encode_batch_pipelined(e_arr, S, None, None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
+    torch.cuda.synchronize()
+    plain, measuring = ib.windows(torch, steps, step)
+    streams.encode(lib.hmr_gpu_enc_encode_batch_pipelined, None)
     last = sums.cpu()
     kernel_ms = kr["k_ssim"]["median_us"] / 1e3 if "k_ssim" in kr else None
-    sp, sm = ib.spread(plain), ib.spread(measuring)
+    sp, sm = pb.spread(plain), pb.spread(measuring)
     res = {"steps_per_window": steps, "pictures": f"every step ingests a fresh device picture per sequence (the clips' {CLIP_FRAMES} pictures in turn) and encodes it",
            "plain_ms_per_step": sp, "with_ssim_ms_per_step": sm, "k_ssim_ms": kernel_ms,
            "mean_luma_ssim_of_the_last_step": round(float(last[:, 0].double().mean()) / float(((W // 4 - 1) * (H // 4 - 1)) << 30), 4)}
@@ -203,9 +134,7 @@ def streaming_step(S, steps, kr):
         res.update({"bound_ms": round(bound, 3), "condition": "median with SSIM <= median plain + k_ssim + spread of plain", "holds": bool(sm["median"] <= bound)})
     else:
         res["holds"] = "not measured (no kernel time)"
-    for e, c in zip(encs, ctxs):
-        lib.hmr_gpu_enc_destroy(e)
-        lib.hmr_gpu_destroy(c)
+    pb.close(lib, made)
     return res
 
 

@@ -18,22 +18,18 @@ flagship workload (256 sequences of 1920x1080, bench.py's configuration and clip
   bench            bench.py's line of this build and of the parent commit's, when the two files are given (both from the same GPU visit)
 Timed windows are walls between two device synchronisations, in one process with the steady state warmed first."""
 import argparse
-import csv
-import ctypes as C
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from ingest_bench import CLIP_FRAMES, CLIP_SEEDS, COPY_PEAK_TBS, KEYS, H, W, spread  # noqa: E402
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+import ingest_bench as ib  # noqa: E402  (the workload, the encoders' set-up, the timed loops)
+import picture_bench as pb  # noqa: E402
+from ingest_bench import CLIP_FRAMES, CLIP_SEEDS, KEYS, H, W  # noqa: E402
+from picture_bench import spread  # noqa: E402
+
 
 # form -> (tensors of a YUVFrame: "planar" / "semi" / "packed", chroma, bits, msb_aligned)
 FORMS = {"planar_422_8": ("planar", "422", 8, False), "planar_444_8": ("planar", "444", 8, False), "yuyv_8": ("packed", "422", 8, False), "p010_420": ("semi", "420", 10, True),
@@ -49,46 +45,18 @@ def picture_bytes(form):
     return ((2 if bits > 8 else 1) * {"420": 1.5, "422": 2.0, "444": 3.0}[chroma] + 3.0) * W * H
 
 
-def setup(S):
-    import torch
-    import encoder_cases as ec
-    import libs
-    from homerhevc_amd.encoder import Picture, YuvPicture
-    lib = libs.load_gpu()
-    P, I, L = C.c_void_p, C.c_int, C.c_long
-    lib.hmr_gpu_last_error.restype = C.c_char_p
-    lib.hmr_gpu_create.argtypes = [C.POINTER(P), I, P]
-    lib.hmr_gpu_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_create.argtypes = [P, C.POINTER(ec.EncCfg), C.POINTER(P)]
-    lib.hmr_gpu_enc_destroy.argtypes = [P]
-    lib.hmr_gpu_enc_load_source.argtypes = [P, I] + [C.c_char_p] * 3
-    lib.hmr_gpu_enc_load_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
-    lib.hmr_gpu_enc_load_sources_yuv_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(YuvPicture), P]
-    lib.hmr_gpu_enc_encode_batch_pipelined.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
-    encs, ctxs = [], []
-    for _ in range(S):
-        ctx, enc = P(), P()
-        assert lib.hmr_gpu_create(C.byref(ctx), 0, None) == 0, lib.hmr_gpu_last_error()
-        assert lib.hmr_gpu_enc_create(ctx, C.byref(ec.default_cfg(W, H, **KEYS)), C.byref(enc)) == 0, lib.hmr_gpu_last_error()
-        encs.append(enc)
-        ctxs.append(ctx)
-    return torch, lib, encs, ctxs
-
-
-def i420_picture(t):
-    from homerhevc_amd.encoder import Picture
-    p = Picture(format=0, reserved=0)
-    p.plane[0], p.plane[1], p.plane[2] = t.data_ptr(), t.data_ptr() + W * H, t.data_ptr() + W * H * 5 // 4
-    p.pitch[0], p.pitch[1], p.pitch[2] = W, W // 2, W // 2
-    return p
+def yuv_picture(frame):
+    from homerhevc_amd.encoder import yuv_picture_of
+    from yuv_cases import YuvPicture
+    return YuvPicture.from_buffer_copy(yuv_picture_of(frame, W, H)[0])
 
 
 def new_source(torch, form):
     """(the tensors of one picture of the form, its descriptor): random containers"""
-    from homerhevc_amd.encoder import YUVFrame, yuv_picture_of
+    from homerhevc_amd.encoder import YUVFrame
     if form == "i420":
         t = torch.randint(0, 256, (W * H * 3 // 2,), dtype=torch.uint8, device="cuda")
-        return t, i420_picture(t)
+        return t, ib.i420(t)
     kind, chroma, bits, msb = FORMS[form]
     wc, hc = (W if chroma == "444" else W // 2), (H // 2 if chroma == "420" else H)
 
@@ -99,62 +67,45 @@ def new_source(torch, form):
 
     tensors = {"planar": lambda: (plane(H, W), plane(hc, wc), plane(hc, wc)), "semi": lambda: (plane(H, W), plane(hc, 2 * wc)), "packed": lambda: (plane(H, 2 * W),)}[kind]()
     frame = YUVFrame(tensors if len(tensors) > 1 else tensors[0], chroma=chroma, bits=bits, msb_aligned=msb)
-    return tensors, yuv_picture_of(frame, W, H)[0]
+    return tensors, yuv_picture(frame)
 
 
-def load(lib, torch, encs, slot, pics, deep):
-    from homerhevc_amd.encoder import Picture, YuvPicture
-    S = len(encs)
-    fn = lib.hmr_gpu_enc_load_sources_yuv_device if deep else lib.hmr_gpu_enc_load_sources_device
-    assert fn((C.c_void_p * S)(*encs), S, (C.c_int * S)(*([slot] * S)), ((YuvPicture if deep else Picture) * S)(*pics), C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0, \
-        lib.hmr_gpu_last_error()
+def load(lib, encs, slot, pics, deep):
+    from yuv_cases import YuvPicture
+    if deep:
+        ib.load_many(lib, "hmr_gpu_enc_load_sources_yuv_device", YuvPicture, encs, slot, pics)
+    else:
+        ib.load_device(lib, encs, slot, pics)
 
 
 def kernel_child(S):
     """the traced program: per form a warm-up launch and five timed ones over S pictures, each with a source of its own (the kernel's time does not depend on the
     samples); k_ingest over I420 first"""
-    torch, lib, encs, ctxs = setup(S)
+    import torch
+    lib = pb.library()
+    made = pb.encoders(lib, S, W, H, **KEYS)
+    encs = [e for _, e in made]
     for form in ["i420"] + list(FORMS):
-        made = [new_source(torch, form) for _ in range(S)]
-        pics = [m[1] for m in made]
+        made_pics = [new_source(torch, form) for _ in range(S)]
+        pics = [m[1] for m in made_pics]
         torch.cuda.synchronize()
         for _ in range(LAUNCHES):
-            load(lib, torch, encs, 0, pics, form != "i420")
+            load(lib, encs, 0, pics, form != "i420")
             torch.cuda.synchronize()
-        del made, pics
+        del made_pics, pics
         torch.cuda.empty_cache()
-    for e, c in zip(encs, ctxs):
-        lib.hmr_gpu_enc_destroy(e)
-        lib.hmr_gpu_destroy(c)
+    pb.close(lib, made)
 
 
 def kernel_rate(S, rgb_bench):
-    with tempfile.TemporaryDirectory(prefix="yuv_ingest_prof_") as out:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "yuv_ingest", "--", sys.executable, os.path.abspath(__file__), "--kernel-child",
-               "--sequences", str(S)]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
-        if r.returncode != 0:
-            return {"error": f"rocprofv3 run failed ({r.returncode})", "stderr_tail": r.stderr[-1500:]}
-        traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
-        if not traces:
-            return {"error": "no kernel trace written", "files": sorted(os.listdir(out))}
-        rows = [r for r in csv.DictReader(open(traces[0])) if "k_ingest" in r["Kernel_Name"]]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    plain = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if "k_ingest_yuv" not in r["Kernel_Name"]]
-    deep = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if "k_ingest_yuv" in r["Kernel_Name"]]
-    if len(plain) != LAUNCHES or len(deep) != LAUNCHES * len(FORMS):
-        return {"error": f"{len(plain)} launches of k_ingest and {len(deep)} of k_ingest_yuv in the trace, {LAUNCHES} and {LAUNCHES * len(FORMS)} expected", "k_ingest_us": plain, "k_ingest_yuv_us": deep}
-    res = {"source_pictures": "one set of tensors per sequence (no two jobs of a launch share source bytes)",
-           "command": "rocprofv3 --kernel-trace --stats --output-format csv -d TRACE_DIR -o yuv_ingest -- python tools/yuv_ingest_bench.py --kernel-child --sequences " + str(S),
-           "pictures_per_launch": S}
-    parts = {"i420": plain[1:]}
-    for k, form in enumerate(FORMS):
-        parts[form] = deep[LAUNCHES * k + 1:LAUNCHES * (k + 1)]
-    for form, part in parts.items():
-        med = statistics.median(part)
-        tbs = picture_bytes(form) * S / (med * 1e-6) / 1e12
-        res[form] = {"kernel": "k_ingest" if form == "i420" else "k_ingest_yuv", "bytes_per_launch": picture_bytes(form) * S, "launch_us": [round(x, 1) for x in part], "median_us": round(med, 1),
-                     "tb_per_s": round(tbs, 3), "share_of_float4_copy_6.29": round(tbs / COPY_PEAK_TBS, 3)}
+    rows, command = pb.traced_child(__file__, ["--sequences", str(S)], "yuv_ingest", timeout=1500)
+    plain, deep = pb.launch_groups(rows, "k_ingest", 1, LAUNCHES), pb.launch_groups(rows, "k_ingest_yuv", len(FORMS), LAUNCHES)
+    for groups in (plain, deep):
+        if isinstance(groups, dict):
+            return groups
+    res = {"source_pictures": "one set of tensors per sequence (no two jobs of a launch share source bytes)", "command": command, "pictures_per_launch": S}
+    for form, part in zip(["i420"] + list(FORMS), plain + deep):
+        res[form] = pb.rate(part, picture_bytes(form) * S, kernel="k_ingest" if form == "i420" else "k_ingest_yuv", bytes_per_launch=picture_bytes(form) * S)
     for form in FORMS:
         res[form]["rate_over_k_ingest_i420"] = round(res[form]["tb_per_s"] / res["i420"]["tb_per_s"], 3)
     res["target"] = target_of(res, rgb_bench)
@@ -189,19 +140,13 @@ def target_of(res, rgb_bench):
     return target
 
 
-def bench_lines(path):
-    lines = [json.loads(ln) for ln in open(path).read().splitlines() if ln.startswith("{")]
-    return [{k: b.get(k) for k in ("value", "unit", "ms_per_step", "steps", "warmup", "build")} for b in lines if b.get("value") is not None and "metric" in b]
-
-
 def bench_of(result, a):
     """bench.py's lines of this build and of the parent's, and whether this build's median lies inside (or above) the parent's run-to-run spread"""
     for name, path in (("this_build", a.bench_this), ("parent", a.bench_parent)):
-        if path and os.path.exists(path):
-            runs = bench_lines(path)
-            if runs:
-                values = [r["value"] for r in runs]
-                result.setdefault("bench", {})[name] = {"runs": runs, "median": round(statistics.median(values), 4), "min": min(values), "max": max(values)}
+        runs = pb.bench_lines(path)
+        if runs:
+            values = [r["value"] for r in runs]
+            result.setdefault("bench", {})[name] = {"runs": runs, "median": round(statistics.median(values), 4), "min": min(values), "max": max(values)}
     b = result.get("bench", {})
     if "this_build" in b and "parent" in b:
         b["this_build_not_below_the_parents_runs"] = bool(b["this_build"]["median"] >= b["parent"]["min"])
@@ -248,42 +193,36 @@ def main():
     import numpy as np
     import encoder_cases as ec
     from homerhevc_amd.build import source_digest
-    from homerhevc_amd.encoder import YUVFrame, yuv_picture_of
+    from homerhevc_amd.encoder import YUVFrame
     result = {"tool": "tools/yuv_ingest_bench.py", "source_digest": source_digest(), "sequences": S, "width": W, "height": H, "configuration": "bench.py cfg2-1080p-encode (wfpp_num_threads 17)",
               "algorithmic_bytes_per_picture": {form: picture_bytes(form) for form in ["i420"] + list(FORMS)}}
     # (the traced child first: this process has not opened the GPU yet)
     result["kernel_rate"] = {"skipped": True} if a.no_kernel_rate else kernel_rate(S, a.rgb_bench)
-    torch, lib, encs, ctxs = setup(S)
+    import torch
+    lib = pb.library()
+    made = pb.encoders(lib, S, W, H, **KEYS)
+    encs = [e for _, e in made]
     sync = torch.cuda.synchronize
 
     # ---- replaces ----
-    made = [new_source(torch, "p010_420") for _ in range(S)]
+    sources = [new_source(torch, "p010_420") for _ in range(S)]
     yuv = [torch.empty((H * 3 // 2, W), dtype=torch.uint8, device="cuda") for _ in range(S)]
-    deep_pics, yuv_pics = [m[1] for m in made], [i420_picture(t) for t in yuv]
+    deep_pics, yuv_pics = [m[1] for m in sources], [ib.i420(t) for t in yuv]
 
     def torch_route():
-        for (tensors, _), o in zip(made, yuv):
+        for (tensors, _), o in zip(sources, yuv):
             torch_round_p010(torch, tensors[0], tensors[1], o)
-        load(lib, torch, encs, 1, yuv_pics, False)
+        load(lib, encs, 1, yuv_pics, False)
 
     torch_route()
-    load(lib, torch, encs, 0, deep_pics, True)
+    load(lib, encs, 0, deep_pics, True)
     sync()
-    fused_ms, torch_ms = [], []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        torch_route()
-        sync()
-        torch_ms.append((time.perf_counter() - t0) * 1e3)
-        t0 = time.perf_counter()
-        load(lib, torch, encs, 0, deep_pics, True)
-        sync()
-        fused_ms.append((time.perf_counter() - t0) * 1e3)
+    torch_ms, fused_ms = ib.alternating(torch, torch_route, lambda: load(lib, encs, 0, deep_pics, True))
     result["replaces"] = {"what": f"one P010 frame of each of {S} sequences into a slot, wall ms between device synchronisations, alternating; torch route: widen to int32, mask, shift, "
                                   "round, clamp, to uint8, split the pairs, frame by frame into I420 tensors, then one hmr_gpu_enc_load_sources_device",
                           "p010_420": {"torch_ops_then_load_sources_device_ms": spread(torch_ms), "load_sources_yuv_device_ms": spread(fused_ms),
                                        "ratio_of_medians": round(statistics.median(torch_ms) / statistics.median(fused_ms), 1)}}
-    del made, yuv, deep_pics, yuv_pics
+    del sources, yuv, deep_pics, yuv_pics
     torch.cuda.empty_cache()
 
     # ---- streaming step ----
@@ -304,60 +243,16 @@ def main():
     for i, e in enumerate(encs):
         for f, planes in enumerate(clips[i % nclip]):
             assert lib.hmr_gpu_enc_load_source(e, f, *planes) == 0, lib.hmr_gpu_last_error()
-    pics = [[yuv_picture_of(p010[i % nclip][f], W, H)[0] for i in range(S)] for f in range(CLIP_FRAMES)]
+    pics = [[yuv_picture(p010[i % nclip][f]) for i in range(S)] for f in range(CLIP_FRAMES)]
     for s in (CLIP_FRAMES, CLIP_FRAMES + 1):
-        load(lib, torch, encs, s, pics[0], True)
+        load(lib, encs, s, pics[0], True)
     sync()
-    bufs = [C.create_string_buffer(4 << 20) for _ in range(S)]
-    e_arr = (C.c_void_p * S)(*encs)
-    ptrs = (C.c_char_p * S)(*[C.cast(b, C.c_char_p) for b in bufs])
-    caps = (C.c_long * S)(*[len(b) for b in bufs])
-    got = (C.c_long * S)()
-    frame = [0]
-
-    def step(streaming):
-        f = frame[0] % CLIP_FRAMES
-        frame[0] += 1
-        slot = f
-        if streaming:
-            slot = CLIP_FRAMES + (frame[0] & 1)
-            load(lib, torch, encs, slot, pics[f], True)
-        assert lib.hmr_gpu_enc_encode_batch_pipelined(e_arr, S, (C.c_int * S)(*([slot] * S)), None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
-
-    def window(streaming):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step(streaming)
-        sync()
-        return (time.perf_counter() - t0) * 1e3 / a.steps
-
-    for _ in range(CLIP_FRAMES // 2):      # steady state: the pool's buffers, the staging buffers, both paths' first calls; one round of the clip
-        step(False)
-        step(True)
-    pre, stream = [], []
-    for _ in range(3):
-        pre.append(window(False))
-        stream.append(window(True))
-    assert lib.hmr_gpu_enc_encode_batch_pipelined(e_arr, S, None, None, ptrs, caps, got) == 0, lib.hmr_gpu_last_error()
     kr = result["kernel_rate"]
-    kernel_ms = kr["p010_420"]["median_us"] / 1e3 if "p010_420" in kr else None
-    sp, ss = spread(pre), spread(stream)
-    result["streaming_step"] = {"steps_per_window": a.steps, "pictures": f"every window encodes the clips' {CLIP_FRAMES} pictures (as P010) in turn, starting at the first",
-                                "preloaded_ms_per_step": sp, "streaming_ms_per_step": ss, "ingest_kernel_ms": kernel_ms}
-    if kernel_ms is not None:
-        bound = sp["median"] + kernel_ms + sp["spread"]
-        result["streaming_step"].update({"bound_ms": round(bound, 3), "condition": "median streaming <= median preloaded + ingest kernel + spread of preloaded",
-                                         "holds": bool(ss["median"] <= bound)})
+    result["streaming_step"] = ib.streaming_step(torch, lib, encs, a.steps, lambda slot, f: load(lib, encs, slot, pics[f], True), kr["p010_420"]["median_us"] / 1e3 if "p010_420" in kr else None,
+                                                 f"every window encodes the clips' {CLIP_FRAMES} pictures (as P010) in turn, starting at the first")
     bench_of(result, a)
-    for e, c in zip(encs, ctxs):
-        lib.hmr_gpu_enc_destroy(e)
-        lib.hmr_gpu_destroy(c)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(result))
+    pb.close(lib, made)
+    pb.write_result(result, a.out)
 
 
 if __name__ == "__main__":
