@@ -39,7 +39,15 @@ enum { PF_SETUP = 0, PF_MERGE, PF_ME_INT, PF_ME_SUB, PF_PRED_INTER, PF_ENC_INTER
 // regular phase timers only keep the total)
 #define HENC_PROF_ADD(e, cat) do { if ((cat) == PF_TOTAL && (e).prof && threadIdx.x == 0) (e).prof[cat] += __builtin_amdgcn_s_memtime() - prof_t0_; } while (0)
 #define HENC_QPROF_T0() unsigned long long qprof_t_ = __builtin_amdgcn_s_memtime()
+#if defined(HENC_QPROF_ME)
+// (-DHENC_QPROF -DHENC_QPROF_ME: the slots go to the marks inside motion_estimation - enc_inter.h ME_MARK_* - and the merge evaluation's marks are off)
+#define HENC_QPROF_MARK(e, cat) do { (void)qprof_t_; } while (0)
+#define HENC_MEPROF_T0() unsigned long long meprof_t_ = __builtin_amdgcn_s_memtime()
+#define HENC_MEPROF_MARK(e, cat) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); if ((e).prof && threadIdx.x == 0) (e).prof[cat] += now_ - meprof_t_; meprof_t_ = now_; } while (0)
+#define HENC_MEPROF_COUNT(e, cat) do { if ((e).prof && threadIdx.x == 0) (e).prof[cat] += 1; } while (0)
+#else
 #define HENC_QPROF_MARK(e, cat) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); if ((e).prof && threadIdx.x == 0) (e).prof[cat] += now_ - qprof_t_; qprof_t_ = now_; } while (0)
+#endif
 #define HENC_QPROF_ARG , unsigned long long &qprof_t_
 #define HENC_QPROF_PASS , qprof_t_
 #else
@@ -55,6 +63,14 @@ enum { PF_SETUP = 0, PF_MERGE, PF_ME_INT, PF_ME_SUB, PF_PRED_INTER, PF_ENC_INTER
 #define HENC_QPROF_ARG
 #define HENC_QPROF_PASS
 #endif
+#if !defined(HENC_MEPROF_MARK)
+#define HENC_MEPROF_T0() do { } while (0)
+#define HENC_MEPROF_MARK(e, cat) do { } while (0)
+#define HENC_MEPROF_COUNT(e, cat) do { } while (0)
+#endif
+// the motion search's marks: candidate set-up (positions, window tests, vector costs), the SAD calls, the walks of the integer rounds, the walks of the sub-sample
+// rounds, what is left of a search (entry, exit), and two counts - searches and rounds
+enum { ME_MARK_SETUP = 1, ME_MARK_SADS, ME_MARK_WALK_INT, ME_MARK_WALK_SUB, ME_MARK_REST, ME_COUNT_SEARCHES, ME_COUNT_ROUNDS };
 
 namespace henc {
 

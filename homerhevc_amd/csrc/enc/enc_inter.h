@@ -188,6 +188,225 @@ HENC_INLINE uint32_t mv_cost_sqrt(const MvCandList &l, uint32_t qp, int mvx, int
 // The source block sits at (ox, oy) of the CTU, (gx, gy) in the picture.  Returns the best SAD.
 // The candidates of a search round do not depend on each other - only the comparisons do - so every round asks for all its SADs at once (cand_sads) and
 // then walks them in the reference's order, with its loop bounds that move while the loop runs.
+#if defined(__HIPCC__)
+// Device form: not only the SADs, a round's positions, window tests and vector costs are independent of the walk too (the centre does not move inside a round),
+// so lane k < MAXC computes candidate k's - the double arithmetic of mv_cost_fast once per round on the lanes instead of once per visited candidate on a uniform
+// value - and after cand_sads lane k holds rd[k] = sad[k] + cost[k], all ones where the candidate lies outside the window (no "rd < cur_rd" is true for it).  The walk
+// keeps the reference's order and its moving bounds; a visited candidate is a lane read with a scalar index, a scalar compare and a branch.  Offsets are packed
+// constants selected by lane (a nibble per candidate), the AMVP list is read from LDS once per search.
+struct MeAmvp { int num, x0, y0, x1, y1; };      // the AMVP list (at most two vectors) in registers
+// mv_cost_fast for the lane's own vector: the same operations in the same order, in double
+__device__ __forceinline__ uint32_t lane_mv_cost(const MeAmvp &a, double corr, int mvx, int mvy)
+{
+	uint32_t best = 0x7fffffff;
+	{
+		const double cx = corr * ((float)habs(a.x0 - mvx)), cy = corr * ((float)habs(a.y0 - mvy));
+		const uint32_t c = (uint32_t)(cx + cy + .5);
+		best = (a.num > 0 && best > c) ? c : best;
+	}
+	{
+		const double cx = corr * ((float)habs(a.x1 - mvx)), cy = corr * ((float)habs(a.y1 - mvy));
+		const uint32_t c = (uint32_t)(cx + cy + .5);
+		best = (a.num > 1 && best > c) ? c : best;
+	}
+	return best;
+}
+// signed nibble k of a packed constant
+__device__ __forceinline__ int me_nibble(uint32_t packed, int k) { return (int)(packed << (28 - 4 * k)) >> 28; }
+#if defined(HENC_QPROF_ME)
+#define HENC_MEPROF_ARG , unsigned long long &meprof_t_
+#define HENC_MEPROF_PASS , meprof_t_
+#else
+#define HENC_MEPROF_ARG
+#define HENC_MEPROF_PASS
+#endif
+// The SADs of a round whose candidates' positions (qx, qy: quarter samples) and ok the lanes k < MAXC hold: out[k], uniform
+template <int MAXC, class G>
+__device__ __forceinline__ void lane_round_sads(const G g, Enc &__restrict__ e, int ox, int oy, int gx, int gy, int size, int vqx, int vqy, bool vok, uint32_t (&out)[MAXC] HENC_MEPROF_ARG)
+{
+	const uint64_t okm = __ballot(vok);
+	int qx[MAXC], qy[MAXC];
+	bool ok[MAXC];
+#pragma unroll
+	for (int k = 0; k < MAXC; k++) {
+		qx[k] = __builtin_amdgcn_readlane(vqx, k);
+		qy[k] = __builtin_amdgcn_readlane(vqy, k);
+		ok[k] = (okm >> k) & 1;
+	}
+	HENC_MEPROF_MARK(e, ME_MARK_SETUP);
+	cand_sads<MAXC>(g, e, ox, oy, gx, gy, size, qx, qy, ok, out);
+	HENC_MEPROF_MARK(e, ME_MARK_SADS);
+	HENC_MEPROF_COUNT(e, ME_COUNT_ROUNDS);
+}
+// ... and for a round of the integer search (x, y: whole samples; cost: the lane's vector cost) the SADs and rd back in the lanes
+template <int MAXC, class G>
+__device__ __forceinline__ void lane_round(const G g, Enc &__restrict__ e, int ox, int oy, int gx, int gy, int size, int vx, int vy, bool vok, uint32_t vcost, uint32_t &vsad, uint32_t &vrd HENC_MEPROF_ARG)
+{
+	uint32_t s[MAXC];
+	lane_round_sads<MAXC>(g, e, ox, oy, gx, gy, size, vx << 2, vy << 2, vok, s HENC_MEPROF_PASS);
+	const int lane = g.tid;
+	uint32_t vs = 0;
+#pragma unroll
+	for (int k = 0; k < MAXC; k++) {
+		asm("" : "+s"(s[k]));      // (as in pick(): a plain chain of selects is turned back into s[lane], an array in private memory)
+		vs = lane == k ? s[k] : vs;
+	}
+	vsad = vs;
+	vrd = vok ? vs + vcost : 0xffffffffu;
+}
+template <class G>
+HENC_HD uint32_t motion_estimation(const G g, Enc &__restrict__ e, int ox, int oy, int gx, int gy, int size, const MvCandList &amvp, const MvCandList &search, double corr,
+				   int action, MV *mv_io, MV *subpix_out)
+{
+	HENC_ENC_IN_LDS(e);
+	const int lane = g.tid;
+	const int fw = e.seq->width, fh = e.seq->height;
+	const int xlow = (gx - SEARCH_RANGE_X) < 0 ? -gx : -SEARCH_RANGE_X, xhigh = (gx + SEARCH_RANGE_X) > (fw - size) ? fw - gx - size : SEARCH_RANGE_X;
+	const int ylow = (gy - SEARCH_RANGE_Y) < 0 ? -gy : -SEARCH_RANGE_Y, yhigh = (gy + SEARCH_RANGE_Y) > (fh - size) ? fh - gy - size : SEARCH_RANGE_Y;
+	uint32_t cur_sad = 0, cur_rd = 0, best_sad = 0xffffffffu;
+	int cur_x = 0, cur_y = 0, best_x = 0, best_y = 0, mvx = 0, mvy = 0, subx = 0, suby = 0;
+#define HENC_IN_WIN(x, y) ((x) >= xlow && (x) <= xhigh && (y) >= ylow && (y) <= yhigh)
+#define HENC_LANE(v, k) __builtin_amdgcn_readlane((int)(v), (k))
+	// the winner k of a round's walk (-1: none): its SAD and position come out of the lanes once, after the walk
+#define HENC_TAKE(k)                                                                                                     \
+	do {                                                                                                             \
+		if ((k) >= 0) { cur_sad = (uint32_t)HENC_LANE(vsad, k); cur_x = HENC_LANE(x, k); cur_y = HENC_LANE(y, k); } \
+	} while (0)
+	HENC_PROF_T0();
+	HENC_MEPROF_T0();
+	HENC_MEPROF_COUNT(e, ME_COUNT_SEARCHES);
+	if (action & ME_PEL) {
+		const MeAmvp a = {uni(amvp.num), uni(amvp.mv[0].x), uni(amvp.mv[0].y), uni(amvp.mv[1].x), uni(amvp.mv[1].y)};
+		// the small diamond {-1, 0}, {0, -1}, {1, 0}, {0, 1} and the eight directions {-2, 0}, {-1, -1}, {0, -2}, {1, -1}, {2, 0}, {1, 1}, {0, 2}, {-1, 1}
+		const int ds_x = (lane & 1) ? 0 : (lane & 3) - 1, ds_y = (lane & 1) ? (lane & 3) - 2 : 0;
+		const int db_x = me_nibble(0xF01210FEu, lane & 7), db_y = me_nibble(0x1210FEF0u, lane & 7);
+		bool early = false;
+		cur_x = hclip(0, xlow, xhigh);
+		cur_y = hclip(0, ylow, yhigh);
+		{
+			// the start position (lane 0) and the predictor positions (lanes 1 .. 3)
+			const int snum = uni(search.num), si = hclip(lane - 1, 0, 2);
+			const bool pred = lane >= 1 && lane - 1 < snum;
+			const int x = lane == 0 ? cur_x : (pred ? search.mv[si].x >> 2 : 0), y = lane == 0 ? cur_y : (pred ? search.mv[si].y >> 2 : 0);
+			const bool vok = lane == 0 || (pred && !(x == 0 && y == 0) && HENC_IN_WIN(x, y));
+			uint32_t vsad, vrd;
+			lane_round<4>(g, e, ox, oy, gx, gy, size, x, y, vok, lane_mv_cost(a, corr, x << 2, y << 2), vsad, vrd HENC_MEPROF_PASS);
+			cur_sad = (uint32_t)HENC_LANE(vsad, 0);
+			cur_rd = (uint32_t)HENC_LANE(vrd, 0);
+			best_sad = cur_sad; best_x = cur_x; best_y = cur_y;
+			if (best_sad <= 0) early = true;
+			if (!early) {
+				int ck = -1;
+#pragma unroll
+				for (int i = 1; i < 4; i++) {      // (a predictor that is missing, zero or outside the window holds all ones)
+					const uint32_t rd = (uint32_t)HENC_LANE(vrd, i);
+					if (rd < cur_rd) { cur_rd = rd; ck = i; }
+				}
+				HENC_TAKE(ck);
+				best_sad = cur_sad; best_x = cur_x; best_y = cur_y;
+				if (best_sad <= 0) early = true;
+			}
+			HENC_MEPROF_MARK(e, ME_MARK_WALK_INT);
+		}
+		if (!early) {
+			const int x = best_x + ds_x, y = best_y + ds_y;
+			uint32_t vsad, vrd;
+			lane_round<4>(g, e, ox, oy, gx, gy, size, x, y, HENC_IN_WIN(x, y), lane_mv_cost(a, corr, x << 2, y << 2), vsad, vrd HENC_MEPROF_PASS);
+			int ck = -1;
+#pragma unroll
+			for (int i = 0; i < 4; i++) {
+				const uint32_t rd = (uint32_t)HENC_LANE(vrd, i);
+				if (rd < cur_rd) { cur_rd = rd; ck = i; }
+			}
+			HENC_TAKE(ck);
+			HENC_MEPROF_MARK(e, ME_MARK_WALK_INT);
+			if (best_sad <= 0) early = true;
+		}
+		if (!early) {
+			int dist = 2;
+			const int end = (best_x != 0 && best_y != 0) ? 4 : 8;
+			int next_start = 0, search_size = 8;
+			best_sad = cur_sad; best_x = cur_x; best_y = cur_y;
+			while (dist < end) {
+				// the eight directions at this distance around the (fixed) centre; the walk below visits a data-dependent subset of them
+				const int x = best_x + db_x * dist, y = best_y + db_y * dist;
+				uint32_t vsad, vrd;
+				lane_round<8>(g, e, ox, oy, gx, gy, size, x, y, HENC_IN_WIN(x, y), lane_mv_cost(a, corr, x << 2, y << 2), vsad, vrd HENC_MEPROF_PASS);
+				int ck = -1;
+				for (int i = next_start; i < next_start + search_size; i++) {
+					const int idx = i & 7;
+					const uint32_t rd = (uint32_t)HENC_LANE(vrd, idx);
+					if (rd < cur_rd) { next_start = (idx - 2 + 8) & 7; search_size = 5; cur_rd = rd; ck = idx; }
+				}
+				HENC_TAKE(ck);
+				HENC_MEPROF_MARK(e, ME_MARK_WALK_INT);
+				dist *= 2;
+			}
+		}
+		// last search: small-diamond descent
+		best_sad = cur_sad; best_x = cur_x; best_y = cur_y;
+		{
+			int next_start = 0, search_size = 4;
+			for (;;) {
+				const int x = best_x + ds_x, y = best_y + ds_y;
+				uint32_t vsad, vrd;
+				lane_round<4>(g, e, ox, oy, gx, gy, size, x, y, HENC_IN_WIN(x, y), lane_mv_cost(a, corr, x << 2, y << 2), vsad, vrd HENC_MEPROF_PASS);
+				int ck = -1;
+				for (int i = next_start; i < next_start + search_size; i++) {
+					const int idx = i & 3;
+					const uint32_t rd = (uint32_t)HENC_LANE(vrd, idx);
+					if (rd < cur_rd) { next_start = (idx - 1 + 4) & 3; search_size = 3; cur_rd = rd; ck = idx; }
+				}
+				HENC_TAKE(ck);
+				HENC_MEPROF_MARK(e, ME_MARK_WALK_INT);
+				if (best_x == cur_x && best_y == cur_y) break;
+				best_sad = cur_sad; best_x = cur_x; best_y = cur_y;
+			}
+		}
+		best_sad = cur_sad; best_x = cur_x; best_y = cur_y;
+		mvx = best_x << 2; mvy = best_y << 2;
+	} else {
+		mvx = mv_io->x; mvy = mv_io->y;
+	}
+	HENC_MEPROF_MARK(e, ME_MARK_REST);
+	HENC_PROF_ADD(e, PF_ME_INT);
+	if (action & ME_HALF) {
+		// The sub-sample rounds: the eight positions around the centre - ref_h / ref_q of the reference without their entry 0, which is the centre itself: its SAD is
+		// cur_sad already and "s < cur_sad" cannot hold for it - so a round is eight candidates (two passes of the 8 x 8 form, not three).  One body serves the
+		// stages: 1 the half round, 2 the quarter round around the chosen half position, and, only when no integer search ran, 0: the integer position alone, whose
+		// SAD the comparisons start from.  The SADs stay uniform values, the walk is eight scalar compares in the reference's order.
+		// x: 0, 0, -1, 1, -1, 1, -1, 1 (both tables);  y: -1, 1, 0, 0, -1, -1, 1, 1 (half), -1, 1, -1, -1, 0, 0, 1, 1 (quarter)
+		const int rx = me_nibble(0x1F1F1F00u, lane & 7), ry_h = me_nibble(0x11FF001Fu, lane & 7), ry_q = me_nibble(0x1100FF1Fu, lane & 7);
+		const int last = (action & ME_QUARTER) ? 2 : 1;
+		int offx = 0, offy = 0;      // the sub-sample part chosen so far
+		best_x = mvx >> 2; best_y = mvy >> 2;
+		for (int stage = (action & ME_PEL) ? 1 : 0; stage <= last; stage++) {
+			const int dx = stage == 0 ? 0 : (stage == 1 ? rx * 2 : offx + rx), dy = stage == 0 ? 0 : (stage == 1 ? ry_h * 2 : offy + ry_q);
+			uint32_t s[8];
+			lane_round_sads<8>(g, e, ox, oy, gx, gy, size, (best_x << 2) + dx, (best_y << 2) + dy, stage != 0 || lane == 0, s HENC_MEPROF_PASS);
+			if (stage == 0) cur_sad = s[0];
+			else {
+				int bk = -1;
+#pragma unroll
+				for (int k = 0; k < 8; k++)
+					if (s[k] < cur_sad) { cur_sad = s[k]; bk = k; }
+				if (bk >= 0) { offx = HENC_LANE(dx, bk); offy = HENC_LANE(dy, bk); }
+			}
+			HENC_MEPROF_MARK(e, ME_MARK_WALK_SUB);
+		}
+		mvx = (best_x << 2) + offx; mvy = (best_y << 2) + offy; subx = offx; suby = offy;
+		best_sad = cur_sad;
+	}
+#undef HENC_IN_WIN
+#undef HENC_LANE
+#undef HENC_TAKE
+	HENC_MEPROF_MARK(e, ME_MARK_REST);
+	HENC_PROF_ADD(e, PF_ME_SUB);   // includes the integer part; the report subtracts
+	mv_io->x = mvx; mv_io->y = mvy;
+	subpix_out->x = subx; subpix_out->y = suby;
+	return best_sad;
+}
+#else
 template <class G>
 HENC_HD uint32_t motion_estimation(const G g, Enc &__restrict__ e, int ox, int oy, int gx, int gy, int size, const MvCandList &amvp, const MvCandList &search, double corr,
 				   int action, MV *mv_io, MV *subpix_out)
@@ -343,6 +562,7 @@ HENC_HD uint32_t motion_estimation(const G g, Enc &__restrict__ e, int ox, int o
 	subpix_out->x = subx; subpix_out->y = suby;
 	return best_sad;
 }
+#endif
 
 // ---- candidate derivation ---------------------------------------------------------------------------------------------
 struct CornerNodes { int lb, tl, tr; };

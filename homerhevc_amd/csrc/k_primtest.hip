@@ -10,7 +10,7 @@
 #include <vector>
 
 #include "common.h"
-#include "enc/enc_prims.h"
+#include "enc/enc_inter.h"
 
 using namespace henc;
 
@@ -136,6 +136,47 @@ __global__ __launch_bounds__(64) void k_primtest_multi_sad(int maxc, const uint8
 	if (maxc == 4) multi_sad_all<4>(g, src, plane, off, stride, n, out);
 	else if (maxc == 8) multi_sad_all<8>(g, src, plane, off, stride, n, out);
 	else multi_sad_all<9>(g, src, plane, off, stride, n, out);
+}
+
+// The walk's motion search, one case per workgroup.  motion_estimation takes an Enc whose members are fixed places of a worker's LDS (enc_common.h LDS_OFF_*): the
+// kernel lays out what the search reads - the source block in the worker's source window, the picture size and the planes' pitch, the planes, the two lists - and
+// calls it as cu_motion_estimation does, for a block at the window's origin.
+constexpr unsigned ME_LDS_BYTES = LDS_OFF_ENC + LDS_ENC_BYTES;
+static_assert(sizeof(hmr_gpu_prim_me_case) == 80 && sizeof(hmr_gpu_prim_me_out) == 20, "include/homer_gpu.h section 15 states these layouts");
+__global__ __launch_bounds__(64) void k_primtest_motion_search(const hmr_gpu_prim_me_case *cases, const uint8_t *src, const uint8_t *plane0, int size, int stride, int width, int height,
+							       hmr_gpu_prim_me_out *out)
+{
+	extern __shared__ __align__(16) uint8_t lds[];
+	const WaveGrp g{(int)threadIdx.x};
+	const hmr_gpu_prim_me_case &cs = cases[blockIdx.x];
+	for (int i = g.tid; i < (int)(ME_LDS_BYTES / 4); i += 64) ((uint32_t *)lds)[i] = 0;
+	g.sync();
+	Work *lw = (Work *)(lds + LDS_OFF_WORK);
+	Seq *lseq = (Seq *)(lds + LDS_OFF_SEQ);
+	FrameCtx *lframe = (FrameCtx *)(lds + LDS_OFF_FRAME);
+	const uint8_t *blk = src + (size_t)blockIdx.x * size * size;
+	for (int i = g.tid; i < size * size; i += 64) lw->curr_y[(i / size) * 64 + i % size] = blk[i];
+	if (g.tid == 0) {
+		lseq->width = width;
+		lseq->height = height;
+		lseq->stride_y = stride;
+		lframe->sub_y = plane0;
+		lw->amvp.num = cs.n_amvp;
+		for (int i = 0; i < 2; i++) { lw->amvp.mv[i].x = cs.amvp[i][0]; lw->amvp.mv[i].y = cs.amvp[i][1]; }
+		lw->search_cands.num = cs.n_search;
+		for (int i = 0; i < 3; i++) { lw->search_cands.mv[i].x = cs.search[i][0]; lw->search_cands.mv[i].y = cs.search[i][1]; }
+	}
+	g.sync();
+	Enc &e = *(Enc *)(lds + LDS_OFF_ENC);
+	HENC_ENC_IN_LDS(e);
+	MV mv = {cs.start[0], cs.start[1]}, subpix = {0, 0};
+	const uint32_t sad = motion_estimation(g, e, 0, 0, uni(cs.gx), uni(cs.gy), size, lw->amvp, lw->search_cands, cs.corr, uni(cs.action), &mv, &subpix);
+	if (g.tid == 0) {
+		hmr_gpu_prim_me_out &o = out[blockIdx.x];
+		o.mv[0] = mv.x; o.mv[1] = mv.y;
+		o.subpix[0] = subpix.x; o.subpix[1] = subpix.y;
+		o.sad = sad;
+	}
 }
 
 size_t span(int stride, int rows, int cols) { return stride ? (size_t)stride * (rows - 1) + cols : (size_t)cols; }
@@ -289,6 +330,61 @@ int hmr_gpu_prim_multi_sad(int maxc, const uint8_t *src, const uint8_t *plane, s
 	hipLaunchKernelGGL(k_primtest_multi_sad, dim3(ncalls), dim3(64), 0, c->stream, maxc, (const uint8_t *)b.p[0], (const uint8_t *)b.p[1], (const long long *)b.p[2], stride, n, (uint32_t *)b.p[3]);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(out, b.p[3], nres * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return HMR_GPU_OK;
+}
+
+int hmr_gpu_prim_motion_search(const hmr_gpu_prim_me_case *cases, int ncases, int size, const uint8_t *src, const uint8_t *planes, size_t plane_bytes, int64_t origin, int stride,
+			       int width, int height, hmr_gpu_prim_me_out *out)
+{
+	if (!cases || !src || !planes || !out || ncases < 1 || ncases > 65536 || (size != 8 && size != 16 && size != 32 && size != 64) || width < size || height < size || width > 8192 ||
+	    height > 8192 || stride < width || stride > (1 << 16)) {
+		hmr_set_error("hmr_gpu_prim_motion_search: size 8 / 16 / 32 / 64, a picture of size .. 8192 samples each way, a stride of width .. 65536, 1 .. 65536 cases");
+		return HMR_GPU_ERR_ARG;
+	}
+	// every block the search can read: whole-sample positions stay inside the picture (the window), the sub-sample rounds reach one sample further
+	if (origin - 16 * (int64_t)stride - 1 < 0 || (uint64_t)origin + ((uint64_t)height * 16 + 15) * (uint64_t)stride + (uint64_t)width + 1 > (uint64_t)plane_bytes) {
+		hmr_set_error("hmr_gpu_prim_motion_search: the planes do not hold the picture with one sample around it");
+		return HMR_GPU_ERR_ARG;
+	}
+	auto vec_ok = [](const int32_t *v) { return v[0] >= -32768 && v[0] <= 32767 && v[1] >= -32768 && v[1] <= 32767; };
+	for (int i = 0; i < ncases; i++) {
+		const hmr_gpu_prim_me_case &k = cases[i];
+		bool ok = k.gx >= 0 && k.gx <= width - size && k.gy >= 0 && k.gy <= height - size && k.n_amvp >= 0 && k.n_amvp <= 2 && k.n_search >= 0 && k.n_search <= 3 && k.action >= 1 &&
+			  k.action <= 7 && k.corr >= 0. && k.corr <= 1e6 && vec_ok(k.amvp[0]) && vec_ok(k.amvp[1]) && vec_ok(k.search[0]) && vec_ok(k.search[1]) && vec_ok(k.search[2]) &&
+			  vec_ok(k.start);
+		if (ok && !(k.action & ME_PEL)) {
+			const int xlow = (k.gx - SEARCH_RANGE_X) < 0 ? -k.gx : -SEARCH_RANGE_X, xhigh = (k.gx + SEARCH_RANGE_X) > (width - size) ? width - k.gx - size : SEARCH_RANGE_X;
+			const int ylow = (k.gy - SEARCH_RANGE_Y) < 0 ? -k.gy : -SEARCH_RANGE_Y, yhigh = (k.gy + SEARCH_RANGE_Y) > (height - size) ? height - k.gy - size : SEARCH_RANGE_Y;
+			const int x = k.start[0] >> 2, y = k.start[1] >> 2;
+			ok = x >= xlow && x <= xhigh && y >= ylow && y <= yhigh;
+		}
+		if (!ok) {
+			hmr_set_error("hmr_gpu_prim_motion_search: case %d is outside the ranges of include/homer_gpu.h section 15", i);
+			return HMR_GPU_ERR_ARG;
+		}
+	}
+	hmr_gpu_ctx *c = hmr_default_ctx();
+	if (!c) { hmr_set_error("hmr_gpu_prim_motion_search: no device"); return HMR_GPU_ERR_NO_DEVICE; }
+	HIP_TRY(hipSetDevice(c->device));
+	HIP_TRY(hipFuncSetAttribute((const void *)k_primtest_motion_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ME_LDS_BYTES));
+	struct Bufs {
+		void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+		~Bufs() { for (void *q : p) if (q) (void)hipFree(q); }
+	} b;
+	const size_t case_bytes = sizeof(hmr_gpu_prim_me_case) * (size_t)ncases, src_bytes = (size_t)ncases * size * size, out_bytes = sizeof(hmr_gpu_prim_me_out) * (size_t)ncases;
+	HIP_TRY(hipMalloc(&b.p[0], case_bytes));
+	HIP_TRY(hipMalloc(&b.p[1], src_bytes));
+	HIP_TRY(hipMalloc(&b.p[2], plane_bytes));
+	HIP_TRY(hipMalloc(&b.p[3], out_bytes));
+	HIP_TRY(hipMemcpyAsync(b.p[0], cases, case_bytes, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(b.p[1], src, src_bytes, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(b.p[2], planes, plane_bytes, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemsetAsync(b.p[3], 0, out_bytes, c->stream));
+	hipLaunchKernelGGL(k_primtest_motion_search, dim3(ncases), dim3(64), ME_LDS_BYTES, c->stream, (const hmr_gpu_prim_me_case *)b.p[0], (const uint8_t *)b.p[1],
+			   (const uint8_t *)b.p[2] + origin, size, stride, width, height, (hmr_gpu_prim_me_out *)b.p[3]);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, b.p[3], out_bytes, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return HMR_GPU_OK;
 }

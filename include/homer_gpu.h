@@ -1121,6 +1121,34 @@ void hmr_gpu_prim_inv_quant(int16_t *src, int16_t *dst, int depth, int comp, int
  * in the walk: its result is 0); stride: the plane's row pitch; n: 8, 16, 32 or 64; out: ncalls x maxc sums.  One launch, a workgroup per list.  HMR_GPU_ERR_ARG (nothing is
  * launched) for another maxc or n, a stride below 1, or a candidate block that does not lie inside the plane. */
 int hmr_gpu_prim_multi_sad(int maxc, const uint8_t *src, const uint8_t *plane, size_t plane_bytes, const int64_t *cand_off, int ncalls, int stride, int n, uint32_t *out);
+/* The motion search of the walk (motion_estimation<WaveGrp>, homerhevc_amd/csrc/enc/enc_inter.h) - on the device a round's positions, window tests and vector costs are
+ * computed in the lanes, a form the one-lane checker build does not have - once per case, a workgroup per case, one launch.  Every case searches for a block of
+ * size x size samples (8, 16, 32 or 64) of a picture of width x height samples:
+ *   src     ncases source blocks, size x size bytes each at a pitch of `size`;
+ *   planes  plane_bytes bytes that hold the reference picture's sixteen luma phase planes in the addressing of section 13 (row y of plane f starts at
+ *           (y * 16 + f) * stride bytes); origin: the byte offset of sample (0, 0) of plane 0.  The search reads up to one sample beyond the picture on every side
+ *           (the sub-sample rounds at a picture edge): origin - 16 * stride - 1 >= 0 and origin + (height * 16 + 15) * stride + width + 1 <= plane_bytes;
+ *   a case  the block's position (gx, gy: 0 .. width - size, 0 .. height - size), the AMVP list (0 .. 2 vectors in quarter samples) the vector cost is taken against,
+ *           the search list (0 .. 3 predictor vectors in quarter samples), corr (the vector cost is corr x the distance to the nearest AMVP vector, >= 0), action (bit 0
+ *           the integer search, bit 1 the half-sample round, bit 2 the quarter-sample round - which only runs behind the half-sample round) and, for an action without
+ *           the integer search, the vector the sub-sample rounds start from (quarter samples; its whole-sample part must lie inside the search window);
+ *   out     per case the vector (quarter samples), its sub-sample part and the SAD the search returns.
+ * All vector components -32768 .. 32767.  HMR_GPU_ERR_ARG (nothing is launched) for anything outside these ranges. */
+typedef struct hmr_gpu_prim_me_case {
+	int32_t gx, gy;
+	int32_t n_amvp, amvp[2][2];
+	int32_t n_search, search[3][2];
+	int32_t action;
+	int32_t start[2];
+	int32_t reserved;        /* 0 */
+	double corr;
+} hmr_gpu_prim_me_case;      /* 80 bytes */
+typedef struct hmr_gpu_prim_me_out {
+	int32_t mv[2], subpix[2];
+	uint32_t sad;
+} hmr_gpu_prim_me_out;       /* 20 bytes */
+int hmr_gpu_prim_motion_search(const hmr_gpu_prim_me_case *cases, int ncases, int size, const uint8_t *src, const uint8_t *planes, size_t plane_bytes, int64_t origin, int stride,
+			       int width, int height, hmr_gpu_prim_me_out *out);
 
 /* ------------------------------------------------------------------------------------------------
  * 16. Test aid: the device-only forms of the CTU walk, one step at a time on a synthetic worker
