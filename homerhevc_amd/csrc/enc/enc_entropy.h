@@ -23,6 +23,15 @@
 #define HENC_FI inline __attribute__((always_inline))
 #endif
 
+// Checker build only (oracle/enc_cpu.cpp defines HENC_POST_COUNTERS): what the coder met on the way, for the tests that ask whether their input reaches a path at all -
+// [0] a carry that ran through buffered 0xff bytes, [1] a byte the carry changed written right behind an 0xff byte, [2] 0xff bytes written, [4 + r] levels coded with Rice parameter r
+#if defined(HENC_POST_COUNTERS) && !defined(__HIPCC__)
+extern "C" long henc_post_counters[16];
+#define HENC_COUNT(k, n) (henc_post_counters[k] += (n))
+#else
+#define HENC_COUNT(k, n) ((void)0)
+#endif
+
 namespace henc {
 
 // ---- bit writer (MSB first) over a caller-owned buffer -----------------------------------------------------------------------
@@ -146,6 +155,9 @@ struct Cabac {
 			const uint32_t carry = lead >> 8;
 			uint32_t byte = buffered_byte + carry;
 			buffered_byte = lead & 0xff;
+			HENC_COUNT(0, carry && num_buffered > 1);
+			HENC_COUNT(1, carry && bw.bitcnt == 0 && bw.bytecnt > 0 && bw.buf[bw.bytecnt - 1] == 0xff);
+			HENC_COUNT(2, carry ? 0 : num_buffered - 1);
 			bw.write(byte, 8);
 			byte = (0xff + carry) & 0xff;
 			while (num_buffered > 1) { bw.write(byte, 8); num_buffered--; }
@@ -640,6 +652,7 @@ HENC_FI void encode_residual(const G g, Cabac &ee, const EntView &v, EntScratch 
 					if (a >= base_level) {
 						int code = a - base_level;
 						const uint32_t r = go_rice;
+						HENC_COUNT(4 + r, 1);
 						if (code < (3 << r)) {
 							const uint32_t length = code >> r;
 							ee.encode_bins_ep((1u << (length + 1)) - 2, length + 1);

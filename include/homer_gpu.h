@@ -14,6 +14,8 @@
  *   3. batched entries                   hmr_gpu_*_batch(ctx, jobs, n, ...): DEVICE-resident planes addressed by
  *                                        job descriptors; one launch per batch - the performance path
  *      frame-level in-loop passes        hmr_gpu_deblock_frame / sao_* / pad_frame
+ *   test aids (sections 15 - 17)         the walk's primitives one call at a time (15), its device-only forms on a synthetic worker (16),
+ *                                        the post-decision stage of one picture from given CTU records (17: hmr_gpu_enc_post_records)
  *
  * All samples are int16_t and strides are in elements, as in the reference.
  * Every entry returns 0 on success or a negative hmr_gpu_status; nothing falls back to the CPU.
@@ -1196,6 +1198,50 @@ typedef struct hmr_gpu_walk_out {
 	int16_t rec[4][256], lv[4][256];
 } hmr_gpu_walk_out;
 int hmr_gpu_walk_forms(const hmr_gpu_walk_case *cases, int ncases, const uint8_t *arena, size_t arena_bytes, hmr_gpu_walk_out *out);
+
+/* ------------------------------------------------------------------------------------------------
+ * 17. Test aid: the post-decision stage of one picture from given CTU records
+ *     Deblocking, SAO statistics / candidates / decision, the SAO and CTU syntax through the lane-spread CABAC, the offset pass, border padding, the task scheduler
+ *     and (with_planes) the phase-plane task S (homerhevc_amd/csrc/enc/enc_post.h, enc_entropy.h, enc_sao.h, subpel_task.h) run on whatever the CTU decisions of an
+ *     encode happen to leave.  This entry feeds them chosen input instead (tests/test_gpu_post_tasks.py): `records` are nctu CTU records in the layout of
+ *     hmr_gpu_enc_frame_ctus (hmr_gpu_enc_record_bytes() each), of which the side-info, the levels and the reconstruction (cropped to the picture) are uploaded as the
+ *     CTU decisions would have left them; src_y / src_u / src_v is the 8-bit source picture (width x height, width / 2 x height / 2, tightly packed).  The frame is set up
+ *     as an encode call sets it up for slice_type (1 = P, 2 = I) and slice QP qp, and the PRODUCT's own k_post_frame is launched with `groups` workgroups (1 .. 32) on
+ *     `enc` (from hmr_gpu_enc_create or hmr_gpu_enc_create_serial_pool; the encoder's frame counters do not move).  No kernel, and no instantiation of a post task, exists for this entry alone.
+ *     Before the launch every byte of the deblocked picture, the final picture, the five unit arrays, the sub-stream buffer and the phase planes is set to
+ *     HMR_GPU_POST_POISON.  Outputs (host memory, all of them required; planes[] only with with_planes): the caller fills the sizes with hmr_gpu_enc_post_sizes, allocates,
+ *     and sets the pointers; a call whose sizes are not the encoder's is refused.
+ *       dbk, fin      the deblocked and the final picture: the whole padded allocations (stride x (rows + 2 margins) int16 each; sample (0, 0) at margin * stride + margin);
+ *       mvx .. flags  the raster unit arrays (units entries each, units_stride per row);
+ *       sao_recon, sao_coded   [nctu][3][35] int32: mode_idc, type_idc, type_aux, offset[32] of every CTU and component;
+ *       bs, bytecnt   the sub-streams: row r's bytes at bs + r * row_cap, bytecnt[r] of them (without WPP: one sub-stream at bs, bytecnt[0]);
+ *       cumbits       [nctu]; ctx, saved: [rows][ctx_bytes] RowEnt::ctx and RowEnt::saved of every row; errors: [4] PostPic::errors;
+ *       planes        the three phase-plane allocations in the layout of section 13 (phase_bytes[] bytes).
+ *     HMR_GPU_ERR_ARG with a text: a NULL pointer, groups outside 1 .. 32, slice_type, qp outside 0 .. 51, record_bytes != nctu x hmr_gpu_enc_record_bytes(), sizes that
+ *     are not the encoder's.  HMR_GPU_ERR_HIP with a text, the outputs filled in as far as the launch got: a sub-stream that ran out of room (errors[0]) or the
+ *     kernel's 30 s watchdog (errors[2]).
+ * ------------------------------------------------------------------------------------------------ */
+#define HMR_GPU_POST_POISON 0x5a
+typedef struct hmr_gpu_post_out {
+	int64_t plane_elems[3];                          /* sizes: hmr_gpu_enc_post_sizes */
+	int64_t units, phase_bytes[3];
+	int32_t nctu, rows, row_cap, ctx_bytes;
+	int32_t stride_y, stride_c, margin_y, margin_c, units_stride, reserved;
+	int16_t *dbk[3], *fin[3];                        /* outputs */
+	int16_t *mvx, *mvy;
+	int8_t *ref;
+	uint8_t *uqp, *flags;
+	int32_t *sao_recon, *sao_coded;
+	uint8_t *bs;
+	int32_t *bytecnt;
+	uint32_t *cumbits;
+	uint8_t *ctx, *saved;
+	int32_t *errors;
+	uint8_t *planes[3];
+} hmr_gpu_post_out;
+int hmr_gpu_enc_post_sizes(hmr_gpu_enc *enc, hmr_gpu_post_out *out);
+int hmr_gpu_enc_post_records(hmr_gpu_enc *enc, int slice_type, int qp, const uint8_t *records, size_t record_bytes, const uint8_t *src_y, const uint8_t *src_u,
+			     const uint8_t *src_v, int groups, int with_planes, hmr_gpu_post_out *out);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 #define HENC_TRACE_ENABLE 1
 #define HENC_SAO_TRACE 1
 #define HENC_SCHED_CAUSES 1
+#define HENC_POST_COUNTERS 1
 #include <stdio.h>
 static FILE *henc_sao_trace_file = nullptr;
 #include <stddef.h>
@@ -24,7 +25,9 @@ static FILE *henc_sao_trace_file = nullptr;
 #include "../homerhevc_amd/csrc/enc/enc_host.h"
 #include "../homerhevc_amd/csrc/enc/enc_post.h"
 #include "hmr_oracle.h"
+#include "../include/homer_gpu.h"      // (hmr_gpu_post_out: henc_cpu_post_records fills what hmr_gpu_enc_post_records fills)
 
+extern "C" long henc_post_counters[16] = {0};
 extern "C" FILE *henc_trace_file = nullptr;
 extern "C" int henc_sched_causes[8] = {0};
 const DevTables *hmr_host_tables();
@@ -807,6 +810,105 @@ int henc_cpu_scan_mismatches(void)
 				if (scan_position(mode, shift, i, cg) != T->scan[mode][shift][i]) bad++;
 		}
 	return bad;
+}
+
+// ---- the post-decision stage of one picture from given records: the one-lane twin of hmr_gpu_enc_post_records (include/homer_gpu.h section 17) ----
+// Same inputs, same outputs, same poison; groups and with_planes are accepted and have nothing to act on (one lane runs every task; task S is device code).
+int henc_cpu_post_sizes(void *h, hmr_gpu_post_out *o)
+{
+	if (!h || !o) return -3;
+	Cpu &c = *(Cpu *)h;
+	const Seq &s = c.seq;
+	for (int k = 0; k < 3; k++) o->plane_elems[k] = (int64_t)c.pic[0][k].size();
+	o->units = (int64_t)s.wctu * 16 * s.hctu * 16;
+	o->phase_bytes[0] = (int64_t)16 * s.plane_elems_y;
+	o->phase_bytes[1] = o->phase_bytes[2] = (int64_t)64 * s.plane_elems_c;
+	o->nctu = s.nctu; o->rows = s.hctu; o->row_cap = s.wctu * CTU_STREAM_BOUND; o->ctx_bytes = CTX_TOTAL + 5;
+	o->stride_y = s.stride_y; o->stride_c = s.stride_c; o->margin_y = s.margin_y; o->margin_c = s.margin_c; o->units_stride = s.wctu * 16; o->reserved = 0;
+	return 0;
+}
+long *henc_cpu_post_counters(void) { return henc_post_counters; }
+
+int henc_cpu_post_records(void *h, int slice_type, int qp, const uint8_t *records, size_t record_bytes, const uint8_t *src_y, const uint8_t *src_u, const uint8_t *src_v,
+			  int groups, int with_planes, hmr_gpu_post_out *out)
+{
+	if (!h || !records || !src_y || !src_u || !src_v || !out) return -3;
+	Cpu &c = *(Cpu *)h;
+	const Seq &s = c.seq;
+	if (groups < 1 || groups > 32 || (slice_type != SLICE_P && slice_type != SLICE_I) || qp < 0 || qp > 51 || record_bytes != (size_t)REC_BYTES * s.nctu) return -3;
+	(void)with_planes;
+	{
+		HostState hs = c.st;
+		if (slice_type == SLICE_P && hs.poc == 0) hs.poc = 1;
+		begin_frame(s, hs, slice_type == SLICE_I ? IMG_I : IMG_P, c.f);
+	}
+	c.f.qp = qp;
+	const uint8_t *in[3] = {src_y, src_u, src_v};
+	for (int comp = 0; comp < 3; comp++) {
+		const int w = comp ? s.width / 2 : s.width, hh = comp ? s.height / 2 : s.height, ss = comp ? s.src_stride_c : s.src_stride_y;
+		for (int r = 0; r < hh; r++)
+			for (int x = 0; x < w; x++) c.src[comp][(size_t)r * ss + x] = in[comp][(size_t)r * w + x];
+		c.f.src[comp] = c.src[comp].data();
+		c.f.ref[comp] = plane0(c, c.cur ^ 1, comp);
+	}
+	post_begin_frame(c);
+	c.post.ctx_after = nullptr;
+	c.post_errors[0] = c.post_errors[1] = 0;
+	for (int comp = 0; comp < 3; comp++) {
+		c.f.rec[comp] = plane0_of(c, c.rec, comp);
+		std::fill(c.rec[comp].begin(), c.rec[comp].end(), (int16_t)0);
+		memset(c.dbk[comp].data(), HMR_GPU_POST_POISON, c.dbk[comp].size() * 2);
+		memset(c.pic[c.cur][comp].data(), HMR_GPU_POST_POISON, c.pic[c.cur][comp].size() * 2);
+	}
+	const size_t nu = (size_t)s.wctu * 16 * s.hctu * 16;
+	memset(c.u_mvx.data(), HMR_GPU_POST_POISON, nu * 2); memset(c.u_mvy.data(), HMR_GPU_POST_POISON, nu * 2);
+	memset(c.u_ref.data(), HMR_GPU_POST_POISON, nu); memset(c.u_qp.data(), HMR_GPU_POST_POISON, nu); memset(c.u_flags.data(), HMR_GPU_POST_POISON, nu);
+	memset(c.bs.data(), HMR_GPU_POST_POISON, c.bs.size());
+	const size_t side = offsetof(CtuPublic, ctu_number), off_coeff = 32 + side, off_recon = off_coeff + 6144 * 2;
+	for (int n = 0; n < s.nctu; n++) {
+		const uint8_t *r = records + (size_t)n * REC_BYTES;
+		CtuPublic &p = c.ctus[n];
+		memset((void *)&p, 0, sizeof(CtuPublic));
+		memcpy((void *)&p, r + 32, side);
+		const int cx = (n % s.wctu) * 64, cy = (n / s.wctu) * 64;
+		const int ctu_w = cx + 64 > s.width ? s.width - cx : 64, ctu_h = cy + 64 > s.height ? s.height - cy : 64;
+		p.ctu_number = n; p.x = cx; p.y = cy;
+		p.last_valid_partition = (ctu_w != 64 || ctu_h != 64) ? host_raster2abs(((ctu_h >> 2) - 1) * 16 + (ctu_w >> 2) - 1) : NPART - 1;
+		p.has_left = cx > 0; p.has_top = cy > 0; p.has_top_left = cx > 0 && cy > 0; p.has_top_right = cy > 0 && n % s.wctu != s.wctu - 1;
+		uint32_t intra = 0;
+		for (int a = 0; a < NPART; a++) intra += p.pred_mode[a] == PM_INTRA;
+		p.intra_parts = slice_type == SLICE_I ? NPART : intra;
+		memcpy(c.coeff.data() + (size_t)n * 6144, r + off_coeff, 6144 * 2);
+		const int16_t *rr = (const int16_t *)(r + off_recon);
+		for (int comp = 0; comp < 3; comp++) {
+			const int nn = comp ? 32 : 64, px = cx >> (comp ? 1 : 0), py = cy >> (comp ? 1 : 0), pw = comp ? s.width / 2 : s.width, ph = comp ? s.height / 2 : s.height;
+			const int rs = comp ? s.stride_c : s.stride_y;
+			int16_t *d = plane0_of(c, c.rec, comp);
+			for (int yy = 0; yy < nn && py + yy < ph; yy++)
+				memcpy(d + (size_t)(py + yy) * rs + px, rr + (size_t)yy * nn, (size_t)(px + nn <= pw ? nn : pw - px) * 2);
+			rr += nn * nn;
+		}
+	}
+	post_whole_frame(c);
+	for (int comp = 0; comp < 3; comp++) {
+		memcpy(out->dbk[comp], c.dbk[comp].data(), c.dbk[comp].size() * 2);
+		memcpy(out->fin[comp], c.pic[c.cur][comp].data(), c.pic[c.cur][comp].size() * 2);
+	}
+	memcpy(out->mvx, c.u_mvx.data(), nu * 2); memcpy(out->mvy, c.u_mvy.data(), nu * 2);
+	memcpy(out->ref, c.u_ref.data(), nu); memcpy(out->uqp, c.u_qp.data(), nu); memcpy(out->flags, c.u_flags.data(), nu);
+	for (int n = 0; n < s.nctu; n++) {
+		memcpy(out->sao_recon + (size_t)n * 3 * 35, c.ctus[n].sao_recon, sizeof c.ctus[n].sao_recon);
+		memcpy(out->sao_coded + (size_t)n * 3 * 35, c.ctus[n].sao_coded, sizeof c.ctus[n].sao_coded);
+	}
+	memcpy(out->bs, c.bs.data(), c.bs.size());
+	for (int r = 0; r < s.hctu; r++) {
+		out->bytecnt[r] = c.ent[r].bytecnt;
+		memcpy(out->ctx + (size_t)r * out->ctx_bytes, c.ent[r].ctx, CTX_TOTAL + 5);
+		memcpy(out->saved + (size_t)r * out->ctx_bytes, c.ent[r].saved, CTX_TOTAL + 5);
+	}
+	memcpy(out->cumbits, c.cumbits.data(), sizeof(uint32_t) * s.nctu);
+	out->errors[0] = c.post_errors[0]; out->errors[1] = c.post_errors[1]; out->errors[2] = post_finished(s, c.post) ? 0 : 1; out->errors[3] = 0;
+	return out->errors[0] || out->errors[2] ? -2 : 0;
 }
 
 const uint8_t *henc_cpu_records(void *h) { return ((Cpu *)h)->records.data(); }
