@@ -7,6 +7,6 @@ There is no CPU fallback: importing works anywhere, calling a kernel without the
 without a GPU raises.
 """
 from .build import LIB_PATH, build_native  # noqa: F401
-from .encoder import BatchEncoder, Encoder, EncoderConfig, RGBFrame, ScaledFrame, ScaledRGBFrame, YUVFrame, psnr, psnr_rgb, ssim  # noqa: F401  (imports neither torch nor the native library)
+from .encoder import BatchEncoder, Encoder, EncoderConfig, RGBFrame, ScaledFrame, ScaledRGBFrame, ScaledYUVFrame, YUVFrame, psnr, psnr_rgb, ssim  # noqa: F401  (imports neither torch nor the native library)
 
-__all__ = ["LIB_PATH", "build_native", "BatchEncoder", "Encoder", "EncoderConfig", "RGBFrame", "ScaledFrame", "ScaledRGBFrame", "YUVFrame", "psnr", "psnr_rgb", "ssim"]
+__all__ = ["LIB_PATH", "build_native", "BatchEncoder", "Encoder", "EncoderConfig", "RGBFrame", "ScaledFrame", "ScaledRGBFrame", "ScaledYUVFrame", "YUVFrame", "psnr", "psnr_rgb", "ssim"]

@@ -1,12 +1,12 @@
 // Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
-// (include/homer_gpu.h sections 12d .. 12k).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of the job type's kernel (picture_io.hip)
+// (include/homer_gpu.h sections 12d .. 12l).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of the job type's kernel (picture_io.hip)
 // on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
 //   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
 //   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
 //           streams (which may still load the slots); the consumer's stream and all of those streams go on behind it.
 //   ssim:   ordered as export; the final pictures and the slots are read, three sums per encoder are written.
 //   export as RGB: ordered as export; the consumer's stream is also the one that holds the producer of the reference pictures.
-// The five load entries are ONE body (load_sources) over a description of their kind of picture; the four export / metric entries share their refusals
+// The six load entries are ONE body (load_sources) over a description of their kind of picture; the four export / metric entries share their refusals
 // (refuse_encoder), their plane check (check_planes) and their ordering (run_export).  Every job comes from picture_io.h's builders; the host-memory entries of
 // k_encode_object.inc (widen_packed, narrow_packed) build theirs for a packed picture - the staging buffer, a picture between GPUs - and run the same kernels.
 #include <unordered_set>
@@ -54,7 +54,7 @@ int refuse_descriptor(const char *fn, int i, const char *prefix = "")
 	return picture_refuse(fn, i, why.c_str());
 }
 
-// what the load calls of sections 12d, 12f, 12g, 12j and 12k refuse before they look at a picture
+// what the load calls of sections 12d, 12f, 12g, 12j, 12k and 12l refuse before they look at a picture
 int check_load(const char *fn, hmr_gpu_enc **encs, int n, const int *slots, const void *pics)
 {
 	static_assert(PICTURE_MAX_JOBS == BATCH_MAX, "a load call feeds a batch call, an export call follows one");
@@ -131,6 +131,16 @@ struct LoadScaledRgb {      // section 12j
 	static const hmr_gpu_rgb_picture &planes(const hmr_gpu_scaled_rgb_picture &p) { return p.pic; }
 	static Job job(const hmr_gpu_scaled_rgb_picture &p, int16_t *const dst[3], const Seq &s) { return hmr_rgb_scale_job(p.pic, p.width, p.height, dst, s.src_stride_y, s.src_stride_c, s.width, s.height); }
 };
+struct LoadScaledYuv {      // section 12l
+	typedef YuvScaleJob Job;
+	static int check(const hmr_gpu_scaled_yuv_picture &p, const Seq &s)
+	{
+		const int rc = hmr_gpu_yuv_picture_check(&p.pic, p.width, p.height);
+		return rc ? rc : hmr_gpu_scale_check(p.width, p.height, s.width, s.height);
+	}
+	static const hmr_gpu_yuv_picture &planes(const hmr_gpu_scaled_yuv_picture &p) { return p.pic; }
+	static Job job(const hmr_gpu_scaled_yuv_picture &p, int16_t *const dst[3], const Seq &s) { return hmr_yuv_scale_job(p.pic, p.width, p.height, dst, s.src_stride_y, s.src_stride_c, s.width, s.height); }
+};
 
 // A load call of any kind: the refusals in their order, the slots, one job per picture and ONE launch on the first encoder's stream.  The pictures are complete when
 // what the producer's stream holds now has run; every other encoder's stream (an encode call starts there: set-up copies, ev_ready) and the producer's (it may write the
@@ -203,6 +213,16 @@ extern "C" int hmr_gpu_enc_load_sources_scaled_rgb_device(hmr_gpu_enc **encs, in
 extern "C" int hmr_gpu_enc_load_source_scaled_rgb_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_rgb_picture *pic, void *producer_stream)
 {
 	return hmr_gpu_enc_load_sources_scaled_rgb_device(&enc, 1, &slot, pic, producer_stream);
+}
+
+// ---- section 12l: larger Y'CbCr pictures of 8 .. 16 bits in, rounded to 8-bit 4:2:0 and area-averaged down to the encoders' sizes ----
+extern "C" int hmr_gpu_enc_load_sources_scaled_yuv(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_scaled_yuv_picture *pics, void *producer_stream)
+{
+	return load_sources<LoadScaledYuv>("hmr_gpu_enc_load_sources_scaled_yuv", encs, n, slots, pics, producer_stream);
+}
+extern "C" int hmr_gpu_enc_load_source_scaled_yuv(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_yuv_picture *pic, void *producer_stream)
+{
+	return hmr_gpu_enc_load_sources_scaled_yuv(&enc, 1, &slot, pic, producer_stream);
 }
 
 namespace {

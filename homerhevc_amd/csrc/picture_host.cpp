@@ -1,4 +1,4 @@
-// Picture conversion, the part that runs on the host alone (include/homer_gpu.h sections 12d .. 12k): the builders of the kernels' jobs (picture_io.h), the three
+// Picture conversion, the part that runs on the host alone (include/homer_gpu.h sections 12d .. 12l): the builders of the kernels' jobs (picture_io.h), the three
 // descriptor checks, the host twins of the kernels - the loops a caller would write from the arithmetic headers (rgb_yuv.h, yuv_depth.h, scale_area.h, yuv_rgb.h,
 // ssim_window.h), compiled from the very functions the kernels of picture_io.hip compile - and the metric arithmetic on the kernels' sums.  Nothing here touches a device.
 #include <math.h>
@@ -371,6 +371,53 @@ extern "C" int hmr_gpu_scale_rgb_host(const hmr_gpu_scaled_rgb_picture *pic, int
 					const uint32_t w = hmr_scale_weight(ay, (uint32_t)oy, sj) * hmr_scale_weight(ax, (uint32_t)ox, si);
 					sum_u += w * (uint32_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
 					sum_v += w * (uint32_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
+				}
+			const size_t oc = (size_t)oy * (dst_w / 2) + ox;
+			u[oc] = (uint8_t)(sum_u / den);
+			v[oc] = (uint8_t)(sum_v / den);
+		}
+	return HMR_GPU_OK;
+}
+
+// ---- section 12l: the host side of the downscaling deep / 4:2:2 / 4:4:4 ingest ----
+// yuv_depth.h's and scale_area.h's arithmetic over host memory, the loop a caller would write from section 12l: every output sums its taps, and each tap rounds the
+// container (luma) or the 1, 2 or 4 containers (chroma) it stands on; no converted picture in between
+extern "C" int hmr_gpu_scale_yuv_host(const hmr_gpu_scaled_yuv_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v)
+{
+	if (!pic) {
+		hmr_set_error("hmr_gpu_scale_yuv_host: the descriptor is NULL");
+		return HMR_GPU_ERR_ARG;
+	}
+	const int rc = hmr_gpu_yuv_picture_check(&pic->pic, pic->width, pic->height);
+	if (rc) return rc;
+	if (const char *why = hmr_scale_refusal(pic->width, pic->height, dst_w, dst_h, true)) {      // (any ratio: the bound of 8 is the kernel's)
+		hmr_set_error("hmr_gpu_scale_yuv_host: %d x %d -> %d x %d: %s", pic->width, pic->height, dst_w, dst_h, why);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!y || !u || !v) {
+		hmr_set_error("hmr_gpu_scale_yuv_host: needs the three output planes");
+		return HMR_GPU_ERR_ARG;
+	}
+	const hmr_gpu_yuv_picture &p = pic->pic;
+	const YuvForm f = hmr_yuv_form(p.format, p.chroma, p.bits, p.msb_aligned, p.offset);
+	const ScaleAxis ax = hmr_scale_axis(pic->width, dst_w), ay = hmr_scale_axis(pic->height, dst_h);      // (a chroma axis has the same reduced ratio)
+	const uint32_t den = ax.s * ay.s;
+	for (int oy = 0; oy < dst_h; oy++)
+		for (int ox = 0; ox < dst_w; ox++) {
+			uint32_t sum = den >> 1;
+			for (uint32_t sj = (uint32_t)oy * ay.s / ay.d; sj * ay.d < ((uint32_t)oy + 1) * ay.s; sj++)
+				for (uint32_t si = (uint32_t)ox * ax.s / ax.d; si * ax.d < ((uint32_t)ox + 1) * ax.s; si++)
+					sum += hmr_scale_weight(ay, (uint32_t)oy, sj) * hmr_scale_weight(ax, (uint32_t)ox, si) * hmr_yuv_luma<const uint8_t *>(p.plane, p.pitch, f, (int)si, (int)sj);
+			y[(size_t)oy * dst_w + ox] = (uint8_t)(sum / den);
+		}
+	for (int oy = 0; oy < dst_h / 2; oy++)
+		for (int ox = 0; ox < dst_w / 2; ox++) {
+			uint32_t sum_u = den >> 1, sum_v = den >> 1;
+			for (uint32_t sj = (uint32_t)oy * ay.s / ay.d; sj * ay.d < ((uint32_t)oy + 1) * ay.s; sj++)
+				for (uint32_t si = (uint32_t)ox * ax.s / ax.d; si * ax.d < ((uint32_t)ox + 1) * ax.s; si++) {
+					const uint32_t w = hmr_scale_weight(ay, (uint32_t)oy, sj) * hmr_scale_weight(ax, (uint32_t)ox, si);
+					sum_u += w * hmr_yuv_chroma<const uint8_t *>(p.plane, p.pitch, f, 1, (int)si, (int)sj);      // (converted chroma sample (si, sj): its 1, 2 or 4 taps)
+					sum_v += w * hmr_yuv_chroma<const uint8_t *>(p.plane, p.pitch, f, 2, (int)si, (int)sj);
 				}
 			const size_t oc = (size_t)oy * (dst_w / 2) + ox;
 			u[oc] = (uint8_t)(sum_u / den);

@@ -1,11 +1,11 @@
 // Picture conversion on the device (picture_io.hip): 8-bit 4:2:0 pictures in device memory <-> the int16 planes of the frame encoder, a batch of pictures per launch.
 // Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture); RGB pictures (8-bit packed or planar, binary16, binary32) -> the same planes, colour
-// converted in the same pass (rgb_yuv.h); Y'CbCr pictures of 8 .. 16 bits in 4:2:0, 4:2:2 or 4:4:4, planar, semi-planar or packed -> the same planes, rounded to 8-bit 4:2:0 in the same pass (yuv_depth.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h); RGB pictures of a larger size -> the same planes, converted and area-averaged in the same pass.  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
+// converted in the same pass (rgb_yuv.h); Y'CbCr pictures of 8 .. 16 bits in 4:2:0, 4:2:2 or 4:4:4, planar, semi-planar or packed -> the same planes, rounded to 8-bit 4:2:0 in the same pass (yuv_depth.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h); RGB pictures of a larger size -> the same planes, converted and area-averaged in the same pass; Y'CbCr pictures of 8 .. 16 bits of a larger size -> the same planes, rounded and area-averaged in the same pass.  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
 // squared differences against the int16 source planes of a picture slot; the final pictures or the slots' pictures -> RGB pictures in any of the ingest's forms, colour
 // converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  SSIM: the exact window sums between a final picture and a slot (ssim_window.h).
-// What the file holds, in its order: the eight job structs (one picture of a launch each; the kernels read a table of them); hmr_picture_launch, which finds kernel and
+// What the file holds, in its order: the nine job structs (one picture of a launch each; the kernels read a table of them); hmr_picture_launch, which finds kernel and
 // grid size by the job type; one builder per job type (descriptors, planes, strides and sizes in, a job out - no encoder); JobRing, the tables of one job type that one
-// encoder has in flight, and PictureRings, its eight rings; run_jobs, which queues one launch ordered against the caller's stream by events (k_encode_picture_io.inc and
+// encoder has in flight, and PictureRings, its nine rings; run_jobs, which queues one launch ordered against the caller's stream by events (k_encode_picture_io.inc and
 // the host-memory entries of k_encode_object.inc use it).  The host-only part of the module - builders, descriptor checks, host twins, metrics - is picture_host.cpp.
 #pragma once
 #include <algorithm>
@@ -115,6 +115,22 @@ struct RgbScaleJob {
 };
 static_assert(sizeof(RgbScaleJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
+// one picture of a downscaling deep / 4:2:2 / 4:4:4 ingest launch (k_yuv_ladder): the caller's src_w x src_h Y'CbCr picture, rounded to 8-bit 4:2:0 by yuv_depth.h's arithmetic
+// sample by sample in registers and area-averaged by scale_area.h's into the dst_w x dst_h planes (section 12l: the composition of 12k and 12g without the picture in between)
+struct YuvScaleJob {
+	const uint8_t *src[3];       // PLANAR: Y, U, V; SEMIPLANAR: Y, interleaved pairs, unused; PACKED422: src[0] alone
+	int64_t pitch[3];            // bytes from row to row
+	int16_t *dst[3];             // the planes at sample (0, 0); 16-byte aligned
+	int32_t stride_y, stride_c;  // elements, multiples of 8
+	int32_t src_w, src_h, dst_w, dst_h;
+	int32_t tile_rows;           // output rows of a tile, as ScaleJob's (hmr_yuv_scale_job)
+	int32_t reserved;
+	YuvForm f;                   // layout, taps, container, shifts and offsets: a launch mixes forms
+	ScaleAxis ax, ay;            // the reduced ratios (the same for luma and chroma) with the reciprocals of dx, dy
+	uint32_t den, mden;          // sx * sy and its reciprocal (hmr_scale_magic)
+};
+static_assert(sizeof(YuvScaleJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
+
 // one picture of an SSIM launch (k_ssim): the sums of ssim_window.h's window values between the int16 planes a and b
 struct SsimJob {
 	const int16_t *a[3];         // the slot's planes at sample (0, 0); 16-byte aligned, read-only
@@ -126,14 +142,14 @@ struct SsimJob {
 static_assert(sizeof(SsimJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
 // The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of the job
-// type's kernel - k_ingest / k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_egress / k_egress_rgb / k_ssim - handles all n pictures; both on `stream`,
-// nothing is waited for.  Instantiated in picture_io.hip for the eight job types (PictureKernel there names each type's kernel and grid size).
+// type's kernel - k_ingest / k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_yuv_ladder / k_egress / k_egress_rgb / k_ssim - handles all n pictures; both on `stream`,
+// nothing is waited for.  Instantiated in picture_io.hip for the nine job types (PictureKernel there names each type's kernel and grid size).
 template <class Job>
 int hmr_picture_launch(hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n);
 
-// ---- the job of one picture, one builder per job type (picture_host.cpp; the two scale jobs next to scale_tile in picture_io.hip) ----
+// ---- the job of one picture, one builder per job type (picture_host.cpp; the three scale jobs next to scale_tile in picture_io.hip) ----
 // The descriptors have passed their checks.  `dst` and every other int16 plane pointer is the plane at sample (0, 0), with its strides in elements.
-// what the five ingest-side jobs begin with: the caller's planes and pitches, the int16 planes and their strides
+// what the six ingest-side jobs begin with: the caller's planes and pitches, the int16 planes and their strides
 template <class Job, class Picture>
 void hmr_job_planes(Job &j, const Picture &pic, int16_t *const dst[3], int stride_y, int stride_c)
 {
@@ -162,6 +178,8 @@ YuvIngestJob hmr_yuv_ingest_job(const hmr_gpu_yuv_picture &pic, int16_t *const d
 ScaleJob hmr_scale_job(const hmr_gpu_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
 // k_rgb_ladder: the same for an RGB source, whose descriptor has passed hmr_gpu_rgb_picture_check for the source's size
 RgbScaleJob hmr_rgb_scale_job(const hmr_gpu_rgb_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
+// k_yuv_ladder: the same for a Y'CbCr source of any depth and chroma format, whose descriptor has passed hmr_gpu_yuv_picture_check for the source's size
+YuvScaleJob hmr_yuv_scale_job(const hmr_gpu_yuv_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h);
 // k_egress: the planes `rec` (a final picture, a picture slot) into `pic` (NULL: no picture), the sums of their squared differences against the planes `src` of a
 // picture slot (NULL: none) into ssd
 EgressJob hmr_egress_job(int16_t *const rec[3], int stride_y, int stride_c, const hmr_gpu_picture *pic, int16_t *const src[3], int src_stride_y, int src_stride_c, uint64_t *ssd,
@@ -220,7 +238,7 @@ struct JobRing {
 
 // The rings of one encoder, one per job type (a table is reused after PICTURE_RING calls of ITS kind): a new kernel adds its job type here and nowhere else.
 struct PictureRings {
-	std::tuple<JobRing<IngestJob>, JobRing<RgbIngestJob>, JobRing<YuvIngestJob>, JobRing<ScaleJob>, JobRing<RgbScaleJob>, JobRing<EgressJob>, JobRing<RgbEgressJob>, JobRing<SsimJob>> of;
+	std::tuple<JobRing<IngestJob>, JobRing<RgbIngestJob>, JobRing<YuvIngestJob>, JobRing<ScaleJob>, JobRing<RgbScaleJob>, JobRing<YuvScaleJob>, JobRing<EgressJob>, JobRing<RgbEgressJob>, JobRing<SsimJob>> of;
 	void release()
 	{
 		std::apply([](auto &...ring) { (ring.release(), ...); }, of);

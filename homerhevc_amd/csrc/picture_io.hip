@@ -1,7 +1,7 @@
-// Picture conversion on the device (include/homer_gpu.h sections 12d .. 12k): pictures in device memory - any base address, any pitch - to and from the int16 planes of
+// Picture conversion on the device (include/homer_gpu.h sections 12d .. 12l): pictures in device memory - any base address, any pitch - to and from the int16 planes of
 // the frame encoder (sample (x, y) at y * stride + x), and quality sums between such planes.  ONE launch for a batch of pictures; k_ingest and k_egress have no
-// arithmetic to speak of and are bound by HBM.  The file holds the nine kernels, behind each the PictureKernel<Job> that names it and its grid size for
-// hmr_picture_launch, the launch itself and the two scale job builders (they need scale_tile); everything else on the host is picture_host.cpp.
+// arithmetic to speak of and are bound by HBM.  The file holds the ten kernels, behind each the PictureKernel<Job> that names it and its grid size for
+// hmr_picture_launch, the launch itself and the three scale job builders (they need scale_tile); everything else on the host is picture_host.cpp.
 //
 // k_ingest: 8-bit pictures into int16 planes - the source planes of a picture slot, or a reference picture: sample (x, y) at y * stride + x, nothing outside
 // width x height touched.  1.5 W H bytes read, 3 W H written per picture.
@@ -21,6 +21,9 @@
 //
 // k_rgb_ladder (section 12j): RGB pictures of a larger size into the same int16 planes, converted as k_ingest_rgb converts and area-averaged as k_downscale averages
 // in the same pass; described at the kernel.
+//
+// k_yuv_ladder (section 12l): Y'CbCr pictures of 8 .. 16 bits of a larger size, in any of k_ingest_yuv's forms, into the same int16 planes, rounded as k_ingest_yuv
+// rounds and area-averaged as k_downscale averages in the same pass; described at the kernel.
 //
 // Mapping (struct Chunk): blockIdx.y = picture (a record of the job table), blockIdx.x = a chunk of CHUNK_ROWS rows of it - first the luma rows, then the chroma rows (a
 // chroma row is its U and its V part: as many 8-bit bytes as a luma row) - so that one grid covers the three planes of every picture; pictures smaller than the largest
@@ -563,7 +566,7 @@ __host__ __device__ __forceinline__ int scale_tiles(const Job &j)
 {
 	return scale_tiles_x(j.dst_w, true) * scale_tiles_y(j.dst_h, j.tile_rows, true) + scale_tiles_x(j.dst_w, false) * scale_tiles_y(j.dst_h, j.tile_rows, false);
 }
-// (Job: ScaleJob, or RgbScaleJob - whose source is never in pairs, and whose chroma tile's columns are columns of the converted chroma planes)
+// (Job: ScaleJob, or RgbScaleJob / YuvScaleJob - whose source is never read in pairs, and whose chroma tile's columns are columns of the converted chroma planes)
 template <class Job>
 __host__ __device__ __forceinline__ ScaleTile scale_tile(const Job &j, int b, bool nv12)
 {
@@ -591,7 +594,7 @@ __host__ __device__ __forceinline__ ScaleTile scale_tile(const Job &j, int b, bo
 __device__ __forceinline__ int scale_word(int b) { return (b >> 4) * SCALE_SPAN_WORDS + (b & 15); }
 
 // The horizontal pass and the store pass of a tile whose column sums lie in `sums` (every lane of the workgroup comes here, behind the barrier that follows the
-// vertical pass): k_downscale and k_rgb_ladder share them.
+// vertical pass): k_downscale, k_rgb_ladder and k_yuv_ladder share them.
 __device__ __forceinline__ void scale_finish(const ScaleTile &k, const ScaleAxis &ax, uint32_t den, uint32_t mden, const uint32_t *sums, u32x4 *outs4, int row_words, int16_t *dst_y, int16_t *dst_u,
 					     int16_t *dst_v, int stride_y, int stride_c)
 {
@@ -841,6 +844,177 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_rgb_ladder(const RgbScaleJob *job
 	scale_finish(k, j.ax, j.den, j.mden, (const uint32_t *)sums4, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
 }
 template <> struct PictureKernel<RgbScaleJob> { static constexpr auto kernel = k_rgb_ladder; static int chunks(const RgbScaleJob &j) { return scale_tiles(j); } };
+
+// ---- downscaling deep / 4:2:2 / 4:4:4 ingest (section 12l) ----
+// k_yuv_ladder: Y'CbCr pictures of one size, in any of k_ingest_yuv's forms, into the int16 planes of a smaller - or equal - size: every slot sample is section 12g's
+// area average of the 8-bit 4:2:0 picture section 12k makes of the source, and that picture never exists in memory.  12k's luma is a function of one container and its
+// chroma of 1, 2 or 4 containers of one plane, so a lane rounds what it has loaded in registers (yuv_load, yuv_pick, hmr_yuv_value, hmr_yuv_round) and accumulates the
+// weighted 8-bit results: the column sums are k_downscale's, bit for bit, and so are the tiles, the LDS layout, the horizontal pass and the stores (scale_tile with a
+// chroma tile's columns those of the converted 4:2:0 chroma planes, scale_finish).
+// Luma tile: a lane takes ONE output row and a span of 16 source pixels, and walks the row's source rows (at most nine); per source row the loads k_ingest_yuv issues
+// for the layout and the container (16 bytes for 8-bit planes, 32 for 16-bit planes or 8-bit packed, 64 for 16-bit packed), sixteen 8-bit samples (8-bit planes: the
+// bytes themselves), sixteen multiply-adds.  Chroma tile: a lane takes ONE chroma output row and a span of EIGHT converted chroma columns (ladder_chroma's choice:
+// sixteen would hold 32 sums); per converted chroma row it reads one (4:2:0) or two source chroma rows, 8 (4:2:0, 4:2:2) or 16 (4:4:4) columns of U and of V, forms
+// the eight tap sums, rounds them with s + K exactly as yuv_span does and accumulates U and V apart into the two streams of the tile row (two 16-byte LDS stores each).
+// A span that reaches past the end of a row goes sample by sample through yuv_depth.h's own hmr_yuv_luma / hmr_yuv_chroma - the ones the host twin runs - every sample
+// checked against the width.  The vertical pass is specialised as k_ingest_yuv is, on the layout, the container's width and the tap count (14 classes, picked per
+// job: a launch mixes forms; luma does not depend on the taps).
+// Planar and semi-planar sources are read once - luma tiles read the luma plane, chroma tiles the chroma planes: sb (Ws Hs + 2 Wc Hc) bytes read, 3 Wd Hd written per
+// picture; a packed source's single plane is read by both tile classes: 2 x 2 sb Ws Hs read.  No lane reads a byte outside [plane + y * pitch, plane + y * pitch +
+// row bytes) or writes outside dst_w x dst_h.  The weighted sums fit 32 bits as section 12g's do: the converted samples are 8-bit.  No atomics.  LDS: k_downscale's.
+
+// the weighted column sums of a luma tile: (output row, span of 16 source pixels) per lane
+template <int L, int SB>
+__device__ __forceinline__ void yuv_ladder_luma(const YuvScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
+{
+	typedef YuvSpan<L, SB, 0> F;
+	const YuvForm f = j.f;
+	const int bits0 = 8 * SB * f.offset[0], src_w = j.src_w;
+	const ScaleAxis ay = j.ay;
+	const bytes_in plane = (bytes_in)j.src[0];
+	const int64_t pitch = j.pitch[0];
+	for (int i = (int)threadIdx.x; i < k.spans * k.ny; i += HMR_BLOCK) {
+		const int r = i / k.spans, p = i - r * k.spans, x = k.c0 + (p << 4);
+		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
+		uint32_t acc[16];
+#pragma unroll
+		for (int m = 0; m < 16; m++) acc[m] = 0;
+		const bool whole = x + 16 <= src_w;
+		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
+			const uint32_t w = hmr_scale_weight(ay, y, sy);
+			if (whole) {
+				uint32_t la[F::LUMA_BYTES / 4];
+				yuv_load<F::LUMA_BYTES>(plane + (int64_t)sy * pitch + (int64_t)x * (L == YUV_PACKED ? 2 : 1) * SB, la);
+#pragma unroll
+				for (int m = 0; m < 16; m++) {
+					const uint32_t raw = L == YUV_PACKED ? yuv_pick<SB, 2>(la, m, bits0) : yuv_pick<SB, 1>(la, m, 0);
+					acc[m] += w * (SB == 1 ? raw : hmr_yuv_round(hmr_yuv_value(f, raw), f.s));      // (8 bits: the sample itself)
+				}
+			} else {
+#pragma unroll
+				for (int m = 0; m < 16; m++)      // (the row's last pixels: sample by sample)
+					if (x + m < src_w) acc[m] += w * hmr_yuv_luma<bytes_in>(j.src, j.pitch, f, x + m, (int)sy);
+			}
+		}
+		u32x4 *o = &sums4[(r * row_words + p * SCALE_SPAN_WORDS) >> 2];
+#pragma unroll
+		for (int m = 0; m < 4; m++) o[m] = u32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
+	}
+}
+
+// the weighted column sums of a chroma tile: (chroma output row, span of 8 converted chroma columns) per lane; the U sums to the first stream, the V sums to the second
+template <int L, int SB, int K>
+__device__ __forceinline__ void yuv_ladder_chroma(const YuvScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
+{
+	typedef YuvSpan<L, SB, K> F;
+	const YuvForm f = j.f;
+	const int bits1 = 8 * SB * f.offset[1], bits2 = 8 * SB * f.offset[2], t = f.s + K;
+	const ScaleAxis ay = j.ay;
+	const bytes_in first = (bytes_in)j.src[L == YUV_PACKED ? 0 : 1], second = (bytes_in)j.src[L == YUV_PLANAR ? 2 : L == YUV_SEMI ? 1 : 0];
+	const int64_t pitch1 = j.pitch[L == YUV_PACKED ? 0 : 1], pitch2 = j.pitch[L == YUV_PLANAR ? 2 : L == YUV_SEMI ? 1 : 0];
+	const int halves = 2 * k.spans, cw = k.row_bytes;      // (the converted chroma width: src_w / 2)
+	for (int i = (int)threadIdx.x; i < halves * k.ny; i += HMR_BLOCK) {
+		const int r = i / halves, q = i - r * halves, cx = k.c0 + (q << 3);
+		if (cx >= cw) continue;      // (the second half of the last span may lie beyond the plane: no tap reads its sums)
+		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
+		uint32_t au[8], av[8];
+#pragma unroll
+		for (int m = 0; m < 8; m++) au[m] = av[m] = 0;
+		const bool whole = cx + 8 <= cw;
+		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
+			const uint32_t w = hmr_scale_weight(ay, y, sy);
+			if (whole) {
+				uint32_t su[8], sv[8];
+#pragma unroll
+				for (int c = 0; c < 8; c++) su[c] = sv[c] = 0;
+				if (L == YUV_PACKED) {      // group c of a row holds chroma column c: 8 groups are 16 pixels
+#pragma unroll
+					for (int rr = 0; rr < 2; rr++) {
+						uint32_t g[F::LUMA_BYTES / 4];
+						yuv_load<F::LUMA_BYTES>(first + (int64_t)(2 * (int)sy + rr) * pitch1 + (int64_t)cx * 4 * SB, g);
+#pragma unroll
+						for (int c = 0; c < 8; c++) {
+							const uint32_t u = yuv_pick<SB, 4>(g, c, bits1), v = yuv_pick<SB, 4>(g, c, bits2);
+							su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
+							sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
+						}
+					}
+				} else {
+					const int row0 = K == 0 ? (int)sy : 2 * (int)sy, col0 = K == 2 ? 2 * cx : cx;
+#pragma unroll
+					for (int rr = 0; rr < F::ROWS; rr++) {
+						uint32_t cu[F::CHROMA_BYTES / 4], cv[F::CHROMA_BYTES / 4];
+						yuv_load<F::CHROMA_BYTES>(first + (int64_t)(row0 + rr) * pitch1 + (int64_t)col0 * SB * (L == YUV_SEMI ? 2 : 1), cu);
+						if (L == YUV_PLANAR) yuv_load<F::CHROMA_BYTES>(second + (int64_t)(row0 + rr) * pitch2 + (int64_t)col0 * SB, cv);
+#pragma unroll
+						for (int c = 0; c < 8; c++)
+#pragma unroll
+							for (int tap = 0; tap < F::TAPS; tap++) {
+								const int n = c * F::TAPS + tap;
+								const uint32_t u = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, n, bits1) : yuv_pick<SB, 1>(cu, n, 0);
+								const uint32_t v = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, n, bits2) : yuv_pick<SB, 1>(cv, n, 0);
+								su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
+								sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
+							}
+					}
+				}
+#pragma unroll
+				for (int c = 0; c < 8; c++) {      // (8 bits: s = 0, maxv = 255, rs = 0 - hmr_yuv_value is the identity and was left out above)
+					au[c] += w * hmr_yuv_round(su[c], t);
+					av[c] += w * hmr_yuv_round(sv[c], t);
+				}
+			} else {
+#pragma unroll
+				for (int m = 0; m < 8; m++) {      // (the row's last columns: sample by sample)
+					if (cx + m >= cw) continue;
+					au[m] += w * hmr_yuv_chroma<bytes_in>(j.src, j.pitch, f, 1, cx + m, (int)sy);
+					av[m] += w * hmr_yuv_chroma<bytes_in>(j.src, j.pitch, f, 2, cx + m, (int)sy);
+				}
+			}
+		}
+		u32x4 *o = &sums4[(r * row_words + scale_word(q << 3)) >> 2];
+		o[0] = u32x4{au[0], au[1], au[2], au[3]}; o[1] = u32x4{au[4], au[5], au[6], au[7]};
+		o += (k.spans * SCALE_SPAN_WORDS) >> 2;
+		o[0] = u32x4{av[0], av[1], av[2], av[3]}; o[1] = u32x4{av[4], av[5], av[6], av[7]};
+	}
+}
+
+template <int L, int SB>
+__device__ __forceinline__ void yuv_ladder_vertical(const YuvScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
+{
+	if (k.luma) yuv_ladder_luma<L, SB>(j, k, sums4, row_words);
+	else if (L == YUV_PACKED || j.f.k == 1) yuv_ladder_chroma<L, SB, 1>(j, k, sums4, row_words);
+	else if (j.f.k == 0) yuv_ladder_chroma<L, SB, 0>(j, k, sums4, row_words);
+	else yuv_ladder_chroma<L, SB, 2>(j, k, sums4, row_words);
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_yuv_ladder(const YuvScaleJob *jobs)
+{
+	__shared__ u32x4 sums4[SCALE_LDS_WORDS / 4];
+	__shared__ u32x4 outs4[SCALE_MAX_ROWS * SCALE_TILE_W / 8];
+	const YuvScaleJob &j = jobs[blockIdx.y];      // (read where it lies, as k_rgb_ladder's)
+	const ScaleTile k = scale_tile(j, (int)blockIdx.x, false);
+	if (k.empty) return;
+	const int row_words = k.total() * SCALE_SPAN_WORDS;
+	const bool wide = j.f.sb == 2;
+	switch (j.f.format) {
+	case HMR_YUV_PLANAR:
+		if (wide) yuv_ladder_vertical<YUV_PLANAR, 2>(j, k, sums4, row_words);
+		else yuv_ladder_vertical<YUV_PLANAR, 1>(j, k, sums4, row_words);
+		break;
+	case HMR_YUV_SEMIPLANAR:
+		if (wide) yuv_ladder_vertical<YUV_SEMI, 2>(j, k, sums4, row_words);
+		else yuv_ladder_vertical<YUV_SEMI, 1>(j, k, sums4, row_words);
+		break;
+	default:
+		if (wide) yuv_ladder_vertical<YUV_PACKED, 2>(j, k, sums4, row_words);
+		else yuv_ladder_vertical<YUV_PACKED, 1>(j, k, sums4, row_words);
+		break;
+	}
+	__syncthreads();
+	scale_finish(k, j.ax, j.den, j.mden, (const uint32_t *)sums4, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
+}
+template <> struct PictureKernel<YuvScaleJob> { static constexpr auto kernel = k_yuv_ladder; static int chunks(const YuvScaleJob &j) { return scale_tiles(j); } };
 
 // ---- egress ----
 // two dwords of two int16 samples each -> their four low bytes
@@ -1327,7 +1501,7 @@ int hmr_picture_launch(hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n
 }
 #define HMR_PICTURE_LAUNCH(Job) template int hmr_picture_launch<Job>(hipStream_t, const Job *, Job *, int);
 HMR_PICTURE_LAUNCH(IngestJob) HMR_PICTURE_LAUNCH(RgbIngestJob) HMR_PICTURE_LAUNCH(YuvIngestJob) HMR_PICTURE_LAUNCH(ScaleJob)
-HMR_PICTURE_LAUNCH(RgbScaleJob) HMR_PICTURE_LAUNCH(EgressJob) HMR_PICTURE_LAUNCH(RgbEgressJob) HMR_PICTURE_LAUNCH(SsimJob)
+HMR_PICTURE_LAUNCH(RgbScaleJob) HMR_PICTURE_LAUNCH(YuvScaleJob) HMR_PICTURE_LAUNCH(EgressJob) HMR_PICTURE_LAUNCH(RgbEgressJob) HMR_PICTURE_LAUNCH(SsimJob)
 
 // The output rows of a job's tiles: the widest tile row of the picture, in spans (it does not depend on the tile's rows; at most SCALE_MAX_SPANS at the ratios
 // hmr_gpu_scale_check lets through), and the rows the LDS then holds.  The job's sizes and ratios are set.
@@ -1360,6 +1534,19 @@ RgbScaleJob hmr_rgb_scale_job(const hmr_gpu_rgb_picture &pic, int src_w, int src
 	RgbScaleJob j;
 	memset(&j, 0, sizeof j);
 	hmr_rgb_source(j, pic, dst, stride_y, stride_c);
+	j.src_w = src_w; j.src_h = src_h; j.dst_w = dst_w; j.dst_h = dst_h;
+	j.ax = hmr_scale_axis(src_w, dst_w); j.ay = hmr_scale_axis(src_h, dst_h);
+	j.den = j.ax.s * j.ay.s; j.mden = hmr_scale_magic(j.den);
+	j.tile_rows = scale_tile_rows(j, false);
+	return j;
+}
+
+YuvScaleJob hmr_yuv_scale_job(const hmr_gpu_yuv_picture &pic, int src_w, int src_h, int16_t *const dst[3], int stride_y, int stride_c, int dst_w, int dst_h)
+{
+	YuvScaleJob j;
+	memset(&j, 0, sizeof j);
+	hmr_job_planes(j, pic, dst, stride_y, stride_c);
+	j.f = hmr_yuv_form(pic.format, pic.chroma, pic.bits, pic.msb_aligned, pic.offset);
 	j.src_w = src_w; j.src_h = src_h; j.dst_w = dst_w; j.dst_h = dst_h;
 	j.ax = hmr_scale_axis(src_w, dst_w); j.ay = hmr_scale_axis(src_h, dst_h);
 	j.den = j.ax.s * j.ay.s; j.mden = hmr_scale_magic(j.den);

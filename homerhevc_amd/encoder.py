@@ -13,6 +13,8 @@
     ladder.step([frame, ScaledFrame(frame, 1920, 1080), ScaledFrame(frame, 1920, 1080)])      # one 1080p picture, area-averaged down to each rung by ONE launch
     ladder.step([RGBFrame(rgb)] + [ScaledRGBFrame(RGBFrame(rgb), 1920, 1080)] * 2)            # the same from an RGB frame: converted and averaged by ONE launch (and one for the top rung)
     small.encode(ScaledRGBFrame(RGBFrame(render[:, 60:2100, 120:3720]), 3600, 2040))          # a crop of a 2160p render into a smaller encoder: no encoder of the source's size
+    p010 = YUVFrame((y16, uv16), bits=10, msb_aligned=True)                                   # a decoder's 2160p picture
+    ladder.step([ScaledYUVFrame(p010, 3840, 2160)] * 3)                                       # rounded to 8 bits and averaged down to each rung by ONE launch
 
     rec, ssd = enc.export(ssd=True)             # the reconstructed picture as a uint8 CUDA tensor, the sums of squared differences to `frame` as int64 [3]
     y, u, v = psnr(ssd.tolist(), 1920, 1080)    # the reference's PSNR (homer_psnr)
@@ -21,8 +23,8 @@
     out, ssd = enc.export_rgb(dtype=torch.float16, reference=RGBFrame(rgb))     # the reconstructed picture as RGB [3, H, W], the sums of squared differences to `rgb` as int64 [3]
     r, g, b, all3 = psnr_rgb(ssd.tolist(), 1920, 1080)                          # PSNR against the RGB frame that was supplied
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h, 12i, 12j and 12k).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; YUVFrame - more than 8 bits, 4:2:2, 4:4:4, packed -: k_ingest_yuv, which rounds to 8-bit 4:2:0 in the same pass; scaled frames: k_downscale, which area-averages in the same pass; scaled RGB frames: k_rgb_ladder, which does both) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h, 12i, 12j, 12k and 12l).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; YUVFrame - more than 8 bits, 4:2:2, 4:4:4, packed -: k_ingest_yuv, which rounds to 8-bit 4:2:0 in the same pass; scaled frames: k_downscale, which area-averages in the same pass; scaled RGB frames: k_rgb_ladder, which does both; scaled YUVFrames: k_yuv_ladder, which rounds and averages) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
 ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
@@ -92,6 +94,11 @@ class ScaledPicture(C.Structure):
 class ScaledRgbPicture(C.Structure):
     """hmr_gpu_scaled_rgb_picture"""
     _fields_ = [("pic", RgbPicture), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class ScaledYuvPicture(C.Structure):
+    """hmr_gpu_scaled_yuv_picture"""
+    _fields_ = [("pic", YuvPicture), ("width", C.c_int32), ("height", C.c_int32)]
 
 
 class ScaledFrame:
@@ -175,7 +182,7 @@ class YUVFrame:
       bits: 8 .. 16.  uint8 tensors for 8 bits; int16 - or uint16 where torch has it - for more (the 16 bits are read as unsigned either way).
       msb_aligned: the sample lies in the container's high bits (P010, P016's 12-bit form, Y210) rather than in its low bits (yuv420p10le).
     The tensors need unit stride along a row; views and crops of larger tensors are fine.  source(), export(ssd=True), ssim() and export_rgb(source=True) then see the
-    8-bit picture that was encoded.  A ScaledFrame does not take one."""
+    8-bit picture that was encoded.  A ScaledFrame does not take one; a ScaledYUVFrame does."""
 
     def __init__(self, planes, chroma="420", bits=8, msb_aligned=False, order=None):
         chroma = str(chroma)
@@ -255,6 +262,30 @@ def scaled_rgb_picture_of(frame):
     returned."""
     pic, keep = rgb_picture_of(frame.frame, frame.width, frame.height)
     return ScaledRgbPicture(pic=pic, width=frame.width, height=frame.height), keep
+
+
+class ScaledYUVFrame:
+    """A Y'CbCr picture of more than 8 bits, 4:2:2, 4:4:4 or packed that is LARGER than the encoder's, for Encoder.encode / BatchEncoder.step: rounded to 8-bit 4:2:0 and
+    area-averaged down to the encoder's size by ONE launch of the ingest kernel k_yuv_ladder (include/homer_gpu.h section 12l).  No new arithmetic: the slot holds section
+    12g's average of the picture section 12k makes of the frame - what encoding the YUVFrame at its own size, taking source() and giving that to a ScaledFrame would put
+    there in three launches, bit for bit - but no encoder of the source's size is needed and the picture in between never exists (hmr_gpu_scale_yuv_host is the same
+    arithmetic on the host).
+      frame: a YUVFrame of width x height pixels - any of its layouts, depths, alignments and chroma formats; a crop is just a view; width, height: ITS size.
+    The same frame may be given to any number of sequences of a step and the step makes ONE load call for all its ScaledYUVFrames.  Downscaling only, by at most 8 per
+    axis; equal sizes are legal and give what the YUVFrame itself gives.  source() returns the scaled 8-bit 4:2:0 picture, export(ssd=True) and ssim() measure against that
+    picture, and export_rgb(source=True) shows it as RGB."""
+
+    def __init__(self, frame, width, height):
+        if not isinstance(frame, YUVFrame):
+            raise TypeError("ScaledYUVFrame: the frame has to be a YUVFrame (an 8-bit 4:2:0 picture goes into a ScaledFrame, an RGBFrame into a ScaledRGBFrame)")
+        self.frame, self.width, self.height = frame, int(width), int(height)
+
+
+def scaled_yuv_picture_of(frame):
+    """The descriptor (hmr_gpu_scaled_yuv_picture) of a ScaledYUVFrame; nothing is copied.  Returns (ScaledYuvPicture, tensors): keep the tensors until the load call has
+    returned."""
+    pic, keep = yuv_picture_of(frame.frame, frame.width, frame.height)
+    return ScaledYuvPicture(pic=pic, width=frame.width, height=frame.height), keep
 
 
 _lib = None
@@ -346,6 +377,8 @@ def load_library():
         lib.hmr_gpu_enc_load_sources_scaled_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledPicture), P]
         lib.hmr_gpu_enc_load_source_scaled_rgb_device.argtypes = [P, I, C.POINTER(ScaledRgbPicture), P]
         lib.hmr_gpu_enc_load_sources_scaled_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledRgbPicture), P]
+        lib.hmr_gpu_enc_load_source_scaled_yuv.argtypes = [P, I, C.POINTER(ScaledYuvPicture), P]
+        lib.hmr_gpu_enc_load_sources_scaled_yuv.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(ScaledYuvPicture), P]
         lib.hmr_gpu_enc_export_sources_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(Picture), P]
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
         lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
@@ -462,11 +495,12 @@ _FRAME_LOADS = [
     (YUVFrame, (YuvPicture, "hmr_gpu_enc_load_sources_yuv_device", lambda f, cfg: yuv_picture_of(f, cfg.width, cfg.height))),
     (ScaledFrame, (ScaledPicture, "hmr_gpu_enc_load_sources_scaled_device", lambda f, cfg: scaled_picture_of(f))),
     (ScaledRGBFrame, (ScaledRgbPicture, "hmr_gpu_enc_load_sources_scaled_rgb_device", lambda f, cfg: scaled_rgb_picture_of(f))),
+    (ScaledYUVFrame, (ScaledYuvPicture, "hmr_gpu_enc_load_sources_scaled_yuv", lambda f, cfg: scaled_yuv_picture_of(f))),
 ]
 
 
 def _load(lib, device, encs, cfgs, slot, frames):
-    """the frames (what picture_of takes, RGBFrame, YUVFrame, ScaledFrame or ScaledRGBFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
+    """the frames (what picture_of takes, RGBFrame, YUVFrame, ScaledFrame, ScaledRGBFrame or ScaledYUVFrame) into slot `slot` of their encoders: ONE load call per kind of frame"""
     members = {load: [] for load in [_PLAIN_LOAD] + [load for _, load in _FRAME_LOADS]}      # (in the order the calls are made)
     for k, f in enumerate(frames):
         members[next((load for cls, load in _FRAME_LOADS if isinstance(f, cls)), _PLAIN_LOAD)].append(k)
@@ -570,7 +604,7 @@ class Encoder:
         self.slot_used = None            # the slot of the last encoded frame (export)
 
     def encode(self, frame, image_type=IMAGE_AUTO):
-        """frame: what picture_of takes, an RGBFrame, a YUVFrame, a ScaledFrame or a ScaledRGBFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
+        """frame: what picture_of takes, an RGBFrame, a YUVFrame, a ScaledFrame, a ScaledRGBFrame or a ScaledYUVFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
         2 for I)."""
         lib = self.lib
         keep = _load(lib, self.device, [self.enc], [self.cfg], self.slot, [frame])
@@ -585,7 +619,7 @@ class Encoder:
 
     def export(self, picture=True, ssd=False, out=None, nv12=False):
         """The reconstructed picture of the frame the last encode() encoded (the final picture: after deblocking and SAO, what a decoder makes of the access unit) and / or
-        the three exact sums of squared differences between it and the picture that frame was encoded from (for a ScaledFrame or ScaledRGBFrame: the SCALED picture in the slot, what source() returns).  Returns (picture, ssd); whichever was not asked for is None.
+        the three exact sums of squared differences between it and the picture that frame was encoded from (for a ScaledFrame, ScaledRGBFrame or ScaledYUVFrame: the SCALED picture in the slot, what source() returns).  Returns (picture, ssd); whichever was not asked for is None.
         picture: `out` written in place (anything picture_of takes: views into larger tensors are fine, only the rows' bytes are written), else a new contiguous uint8
         tensor [H * 3 // 2, W] (I420), with nv12=True a (y, uv) pair [H, W], [H / 2, W / 2, 2].  ssd: an int64 CUDA tensor [3] (Y, U, V); psnr(ssd.tolist(), W, H) gives dB.
         One launch of the egress kernel, ordered on torch's current stream: what is queued there afterwards sees the results, nothing waits on the host."""
@@ -623,7 +657,7 @@ class Encoder:
         return (pics[0], sums[0]) if sums is not None else pics[0]
 
     def source(self, out=None, nv12=False):
-        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a YUVFrame the 8-bit 4:2:0 picture the rounding made, for a ScaledFrame or a ScaledRGBFrame the scaled 4:2:0 picture.  `out` and nv12 as in
+        """The picture the last encode() encoded, as it lies in the encoder's picture slot: for an RGBFrame the 4:2:0 samples the conversion made, for a YUVFrame the 8-bit 4:2:0 picture the rounding made, for a ScaledFrame, a ScaledRGBFrame or a ScaledYUVFrame the scaled 4:2:0 picture.  `out` and nv12 as in
         export(); one launch of the egress kernel, ordered on torch's current stream."""
         if self.slot_used is None:
             raise RuntimeError("Encoder.source: nothing has been encoded yet")
@@ -648,7 +682,7 @@ class BatchEncoder:
     """Several sequences (configurations with wfpp_num_threads > 1: the batch schedule), one picture of each per step(): ONE ingest launch for all their pictures and ONE
     launch for all their CTU stages.  Every sequence has a context - a stream - of its own.
 
-    step(frames): frames[i] is sequence i's next picture (what picture_of takes, an RGBFrame, a YUVFrame, a ScaledFrame or a ScaledRGBFrame; a step that has several kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
+    step(frames): frames[i] is sequence i's next picture (what picture_of takes, an RGBFrame, a YUVFrame, a ScaledFrame, a ScaledRGBFrame or a ScaledYUVFrame; a step that has several kinds makes one load call per kind) or None when it has none this step.  Returns a list with one entry per sequence.
     Not pipelined: entry i is the access unit of frames[i] (b"" for None).
     Pipelined (the default): access units are delivered ONE STEP LATE, as by hmr_gpu_enc_encode_batch_pipelined - entry i is the access unit of the picture sequence i was
     given in the previous step (b"" if it was given none), whose download and entropy coding ran beside this step's launch; flush() returns those of the last step.  When

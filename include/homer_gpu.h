@@ -1051,7 +1051,7 @@ int hmr_gpu_scale_rgb_host(const hmr_gpu_scaled_rgb_picture *pic, int dst_w, int
  *     to every encode call, from one filled by hmr_gpu_enc_load_sources_device with the converted I420 picture.  hmr_gpu_enc_export_sources_device (12f) returns
  *     what the slot holds.  Refused as in 12d, plus whatever hmr_gpu_yuv_picture_check refuses for the encoder's picture size.
  *     Out of scope: upsampling chroma; other sitings or filters; dithering; range, matrix or transfer conversion; big-endian samples; the 10:10:10:2 packings (v210,
- *     Y410); float Y'CbCr; high-depth or 4:2:2 / 4:4:4 OUTPUT (12e writes 8-bit 4:2:0); scaled deep sources (12g takes 8-bit 4:2:0); anything that changes what the
+ *     Y410); float Y'CbCr; high-depth or 4:2:2 / 4:4:4 OUTPUT (12e writes 8-bit 4:2:0); scaled deep sources HERE (12g takes 8-bit 4:2:0; 12l rounds and scales them in one launch); anything that changes what the
  *     encoder itself encodes.
  * ------------------------------------------------------------------------------------------------ */
 enum { HMR_GPU_YUV_PLANAR = 0, HMR_GPU_YUV_SEMIPLANAR = 1, HMR_GPU_YUV_PACKED422 = 2 };
@@ -1066,6 +1066,49 @@ int hmr_gpu_yuv_picture_check(const hmr_gpu_yuv_picture *pic, int width, int hei
 int hmr_gpu_yuv_convert_host(const hmr_gpu_yuv_picture *pic, int width, int height, uint8_t *y, uint8_t *u, uint8_t *v);
 int hmr_gpu_enc_load_source_yuv_device(hmr_gpu_enc *enc, int slot, const hmr_gpu_yuv_picture *pic, void *producer_stream);
 int hmr_gpu_enc_load_sources_yuv_device(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_yuv_picture *pics, void *producer_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 12l. A resolution ladder from Y'CbCr pictures of more than 8 bits, 4:2:2 and 4:4:4 in device memory: rounding and downscaling inside the ingest (no counterpart
+ *      in the reference)
+ *     A hardware decoder leaves P010, a mezzanine is 10-bit 4:2:2, a capture card hands over UYVY or Y210 - and the picture is wanted at several smaller sizes, or
+ *     at one smaller size only, or as a crop.  hmr_gpu_enc_load_sources_scaled_yuv fills picture slots of n encoders (1 .. 512) from Y'CbCr pictures in any of 12k's
+ *     forms that are LARGER than (or as large as) the encoders' pictures with ONE launch of a kernel (k_yuv_ladder, picture_io.hip).  No new formula: the slot is the
+ *     composition of two sections above, bit for bit,
+ *       out = 12g's area average (source size -> encoder size, every plane on its own, one rounding) of the 8-bit 4:2:0 picture that 12k's rounding makes of the
+ *             source at the source's size
+ *     so that for every entry  slot == hmr_gpu_scale_host(hmr_gpu_yuv_convert_host(yuv)) : what loading a source-sized encoder with 12k, exporting its slot and loading
+ *     that picture with 12g gives in three launches, and a ladder whose top rung is loaded through 12k stays consistent with its lower rungs.  The 8-bit picture in
+ *     between never exists in memory: 12k's luma sample is a function of one container and its chroma sample of 1, 2 or 4 containers of one plane, so the kernel
+ *     rounds each source sample in registers and accumulates 12g's weighted sums directly.  Planar and semi-planar sources are read once per entry (luma and chroma
+ *     are produced by different workgroups, each of which reads its own planes); a packed source's single plane is read by both: twice per entry.
+ *     With x the real-valued average of v / 2^s over a 12k sample's taps, every 12k sample is within 0.5 of min(255, x): the rounding gives at most 0.5 below 255,
+ *     the clamp gives exactly 255 above it.  An average with weights that sum to 1 cannot enlarge that, and 12g's single rounding adds at most 0.5: every output is
+ *     within 1.0 of the real-valued area average of the min(255, x) planes.
+ *     Forms, depths, alignments, chroma formats, sizes and ratios may be mixed freely within a call, and the same source may appear in any number of entries.  An
+ *     entry whose source has the encoder's size is legal and gives exactly what hmr_gpu_enc_load_sources_yuv_device gives.  The source is any of 12k's forms at any
+ *     base address and pitch (16-bit containers: multiples of 2), so a crop is just a view.
+ *     The two load entries take device pictures like their siblings; their names deliberately do not end in _device.
+ *     It carries the contract of 12d word for word: the launch runs on the first encoder's stream behind what producer_stream holds now, producer_stream and the
+ *     other encoders' streams go on behind it, the host waits for nothing (but for a slot that has to be allocated first); only the bytes of the source's rows are
+ *     read, nothing outside width x height of the slot is written; a slot filled this way is indistinguishable, to every encode call, from one filled by
+ *     hmr_gpu_enc_load_sources_device with the host-made I420 picture.  hmr_gpu_enc_export_sources_device (12f) returns what the slot holds.
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is queued, every encoder left working: what 12d refuses; what
+ *     hmr_gpu_yuv_picture_check refuses for the SOURCE's size (hmr_gpu_scaled_yuv_picture.width, .height); what hmr_gpu_scale_check refuses for (source size ->
+ *     encoder size); a plane that hipPointerGetAttributes does not report as device memory of the encoders' device.
+ *     hmr_gpu_scale_yuv_host: the same arithmetic in a plain loop over HOST memory - the descriptor's planes are host pointers here - into tightly packed I420 planes
+ *     (y: dst_w x dst_h; u, v: dst_w / 2 x dst_h / 2): every output sums its taps and rounds the container or the 1, 2 or 4 containers under each tap, no picture in
+ *     between.  No device, no context.  It refuses what hmr_gpu_yuv_picture_check and hmr_gpu_scale_check refuse and NULL arguments, except that it takes any ratio,
+ *     as hmr_gpu_scale_rgb_host does: the bound of 8 is the kernel's.  A utility; it is not a fallback for encoding.
+ *     Out of scope: a single rounding from the deep samples (within 0.5 instead of 1.0, but a new arithmetic that no longer equals the three-launch path or a top
+ *     rung loaded through 12k); range, matrix or transfer conversion and tone mapping; deep or 4:2:2 output; upscaling; ratios above 8 on the device.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct hmr_gpu_scaled_yuv_picture {
+	hmr_gpu_yuv_picture pic;       /* the SOURCE picture, as in 12k */
+	int32_t width, height;         /* the SOURCE's size */
+} hmr_gpu_scaled_yuv_picture;      /* 88 bytes; width at 80, height at 84 */
+int hmr_gpu_enc_load_sources_scaled_yuv(hmr_gpu_enc **encs, int n, const int *slots, const hmr_gpu_scaled_yuv_picture *pics, void *producer_stream);
+int hmr_gpu_enc_load_source_scaled_yuv(hmr_gpu_enc *enc, int slot, const hmr_gpu_scaled_yuv_picture *pic, void *producer_stream);
+int hmr_gpu_scale_yuv_host(const hmr_gpu_scaled_yuv_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v);
 
 /* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
