@@ -965,9 +965,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 }
 
 // the host side: the encoder object and the per-frame entry points, then the calls that put several pictures into one launch, then pictures from and to device memory,
-// then the test aids: single steps of the walk on a synthetic worker, the post-decision stage of a picture from given CTU records
+// then the test aids: single steps of the walk on a synthetic worker, the post-decision stage of a picture from given CTU records, single steps of the walk on a worker
+// with its real helper wavefront
 #include "k_encode_object.inc"
 #include "k_encode_batch.inc"
 #include "k_encode_picture_io.inc"
 #include "k_encode_walktest.inc"
 #include "k_encode_posttest.inc"
+#include "k_encode_helpertest.inc"

@@ -1286,6 +1286,83 @@ int hmr_gpu_enc_post_sizes(hmr_gpu_enc *enc, hmr_gpu_post_out *out);
 int hmr_gpu_enc_post_records(hmr_gpu_enc *enc, int slice_type, int qp, const uint8_t *records, size_t record_bytes, const uint8_t *src_y, const uint8_t *src_u,
 			     const uint8_t *src_v, int groups, int with_planes, hmr_gpu_post_out *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * 18. Test aid: the worker / helper-wavefront protocol and what runs behind it, one step at a time with real helper wavefronts
+ *     Every `if (HENC_HELPERS(e))` branch of the walk, helper_serve / helper_loop / helper_bg_search (k_encode.hip) and the background intra search
+ *     (bg_post / bg_take / bg_quiesce) exist on the device only.  This entry launches workgroups of a worker wavefront and its helper wavefront, as k_encode_pool does
+ *     (the same threads per workgroup, the same LDS size and places, entered through rows_enter); the worker builds its context as encode_row does, and for every case
+ *     of its share fills what the step reads, posts HJOB_NEW_CTU, runs the step - the walk's own statements, jobs posted to and waited for on the real mailbox - and
+ *     copies out what the step left; then it releases the helper (tests/test_gpu_helper_forms.py).  Host pointers, synchronous, default context: one upload, one
+ *     download, and one launch for the cases of the plain helper loop plus one (the latency kernel's loop: rows_enter<true>) for the INTRA_SEARCH_BG cases.
+ *     The worker's walk runs under group types of the harness's own derived from WaveGrp / WaveGrpLat, and so does the plain helper loop (section 16 says why); the
+ *     latency loop, helper_serve_out and helper_bg_search are the product's own out-of-line functions.
+ *     arena: every byte the cases read, addressed by byte offsets (multiples of 4; -1: none, where a step does not read it):
+ *       curr, pred   6144 bytes each: the worker's source / prediction windows as in section 16;
+ *       nbr          int16: the decoded samples around the block - the 2 N of the column left of it top to bottom, the corner, the 2 N of the row above it left to
+ *                    right (4 N + 1) - written into the decoded window the step reads (luma: window depth + 1; chroma: the auxiliary window) before the step.  A luma
+ *                    step: one array for the node's N x N block; a chroma step: one for U, then one for V, of the chroma block's size;
+ *       sync         int16, a SYNC_UV step or SYNC job: the levels of U, the levels of V, the reconstruction of U, of V (Nc x Nc each, row by row) put into the source windows.
+ *     node: the partition node (breadth first, children in z-order); ctu_x / ctu_y / width / height: CtuPublic::x / y and the picture size (bl_size / tr_size clip by
+ *     them); nb: the node's left_nb, top_nb, left_bottom_nb, top_right_nb.  Steps:
+ *       INTRA_SEARCH     intra_mode_search(g, e, node, depth of the node) as encode_intra_luma calls it, rounds of two candidates with HJOB_INTRA_SAD on the helper.
+ *                        strong_intra, rd_mode (0 or 2 = RD_FAST), sqrt_lambda.  The neighbour directions: nb_dir[0] (left) / nb_dir[1] (top), 0 .. 34, go into
+ *                        Work::intra_mode_buffs of the node's depth where the neighbour unit lies inside the CTU (the search reads them when seen_intra = 1:
+ *                        Work::thread_seen_intra); a node on the CTU's left / top edge has no such neighbour (Enc::nb_ctus = 0: DC) and its nb_dir is -1.
+ *                        out: mode, bits, cost_bits (the double best_cost as its 8 bytes), last_slog, srch_modes / srch_sads (the last round), adi, adi_f (4 N + 1).
+ *       INTRA_SEARCH_BG  bg_variant TAKE: bg_post(node), the ordinary jobs[] (0 = none, SSD / INTER_TU / SYNC: HJOB_SSD, HJOB_INTER_TU (PART_2Nx2N at the node's
+ *                        depth), HJOB_SYNC_CU for both chroma planes, posted and waited for one after the other as the inter evaluation does), bg_take(node): taken = 1,
+ *                        mode, bits (cost_bits 0: the background search hands no cost over).  TAKE_OTHER: bg_post(bg_node), the jobs, bg_take(node) - taken = 0 -
+ *                        then the worker's own search of node.  QUIESCE: bg_post(node), bg_quiesce, the worker's own search (taken = -1).  out as INTRA_SEARCH, and
+ *                        job_r[k][0 .. 5]: HelperBox::r after job k (SSD: U, V; INTER_TU: distortion, level sum, no-residual distortion of U, then of V); a SYNC job
+ *                        copies window 0 to window NWND - 1, whose blocks are returned in lv / rec.
+ *       CHROMA_SEARCH    the candidate search of encode_intra_chroma: HJOB_CHROMA_SEARCH (U, candidates cand[0 .. 4] packed as there) on the helper,
+ *                        chroma_search_comp for V on the worker.  out: sad_u, sad_v.
+ *       CHROMA_TU        HJOB_CHROMA_TU for U on the helper (its own scratch), chroma_tu_comp for V on the worker, direction cu_mode, the scan by find_scan_mode,
+ *                        cbf_shift[0 .. 1] the two cbf bit positions, QP from qp and chroma_qp_offset.  out per plane: pred, lv, rec, tu_dist, tu_sum, cbf_chroma.
+ *       SSD_UV           HJOB_SSD for both planes as the skip evaluation posts it, the worker's luma SSD meanwhile.  out: ssd[0 .. 2] = U, V, luma.
+ *       SYNC_UV          sync_motion_buffers(node, wnd[0 .. 3] = q_src, q_dst, d_src, d_dst): HJOB_SYNC_CU for both planes, the worker's luma copy meanwhile.
+ *                        out: lv / rec = the destination windows' chroma blocks.
+ *     pred / lv / rec hold plane U at [0], V at [1], Nc x Nc row by row.
+ *     stray (every step): before a step every int16 of the worker's windows in HBM (WorkSlow) holds 0x1234.  After it the harness puts that value back over what it
+ *     wrote itself (the nbr samples, a SYNC step's source blocks) and over the blocks the step is meant to write (a TU's levels and reconstruction, a SYNC step's
+ *     destination chroma blocks; the luma blocks a SYNC_UV step copies hold that value on both sides); stray is the number of 32-bit words of WorkSlow that then hold anything else.
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is launched: "step"; "step (the library was built with a helper per chroma plane)"
+ *     (HENC_NHELP = 2: every step); "node"; "node (a chroma step needs a CU of 8 or more)"; "node (an INTER_TU job: a CU of 8 to 32)"; "bg_variant"; "bg_node"
+ *     (TAKE_OTHER: another node of the same depth; else equal to node); "jobs"; "ctu_x / ctu_y"; "width / height" (the node's block inside the picture); "nb";
+ *     "strong_intra / rd_mode / seen_intra"; "nb_dir"; "sqrt_lambda"; "qp"; "chroma_qp_offset"; "slice_type"; "sign_hiding"; "avg_dist / chroma_weight"; "cand";
+ *     "cu_mode"; "cbf_shift"; "wnd"; "curr"; "pred"; "nbr"; "sync".
+ * ------------------------------------------------------------------------------------------------ */
+enum hmr_gpu_helper_step { HMR_GPU_HELPER_INTRA_SEARCH = 1, HMR_GPU_HELPER_INTRA_SEARCH_BG, HMR_GPU_HELPER_CHROMA_SEARCH, HMR_GPU_HELPER_CHROMA_TU, HMR_GPU_HELPER_SSD_UV,
+			   HMR_GPU_HELPER_SYNC_UV };
+enum hmr_gpu_helper_bg { HMR_GPU_HELPER_BG_TAKE = 0, HMR_GPU_HELPER_BG_TAKE_OTHER, HMR_GPU_HELPER_BG_QUIESCE };
+enum hmr_gpu_helper_job { HMR_GPU_HELPER_JOB_NONE = 0, HMR_GPU_HELPER_JOB_SSD, HMR_GPU_HELPER_JOB_INTER_TU, HMR_GPU_HELPER_JOB_SYNC };
+typedef struct hmr_gpu_helper_case {
+	int32_t step, node, bg_node, bg_variant;
+	int32_t ctu_x, ctu_y, width, height;
+	int32_t strong_intra, rd_mode, seen_intra, slice_type;
+	int32_t nb[4];
+	int32_t nb_dir[2], qp, chroma_qp_offset;
+	int32_t sign_hiding, cu_mode, cbf_shift[2];
+	int32_t cand[5], jobs[4], wnd[4], reserved[3];
+	double sqrt_lambda, chroma_weight, avg_dist;
+	int64_t curr, pred, nbr, sync;
+} hmr_gpu_helper_case;
+typedef struct hmr_gpu_helper_out {
+	int32_t mode, bits, taken, last_slog;
+	uint64_t cost_bits;
+	int64_t srch_sads[5];
+	int32_t srch_modes[6];
+	uint32_t sad_u[5], sad_v[5];
+	uint32_t job_r[4][6];
+	int32_t tu_dist[2], tu_sum[2];
+	uint32_t ssd[3], stray;
+	uint8_t cbf_chroma[2][256];
+	int16_t adi[264], adi_f[264];
+	uint8_t pred[2][1024];
+	int16_t lv[2][1024], rec[2][1024];
+} hmr_gpu_helper_out;
+int hmr_gpu_walk_helper_forms(const hmr_gpu_helper_case *cases, int ncases, const uint8_t *arena, size_t arena_bytes, hmr_gpu_helper_out *out);
+
 #ifdef __cplusplus
 }
 #endif
