@@ -95,35 +95,19 @@ struct GeoTable {
 #endif
 
 constexpr int NHELP_MAX = 3;
-// the fixed part of a worker's LDS (k_encode.hip checks that its layout agrees)
-// Of the CTU's 341 partition nodes a worker keeps the 21 of depths 0 .. 2 and the depth-3 and depth-4 nodes (16 + 64) of ONE quadrant (the 32 x 32 area of a
-// depth-1 node) in its fast memory: the walks are depth first, so while a depth-1 node and what hangs below it is evaluated no deeper node of another quadrant is
-// touched (the checker build verifies exactly that at every access; the one exception, the corner units of the 64 x 64 CU, is handled where it occurs); the other
-// three quadrants' nodes wait in the CTU's record in HBM (nodes_select_quad).
-constexpr int NODES_RESIDENT = 21, NODES_D3 = 85, NODE_QUAD_D3 = 16, NODE_QUAD_D4 = 64, NODE_SLOTS = NODES_RESIDENT + NODE_QUAD_D3 + NODE_QUAD_D4;
+// the worker's fast copy of the CTU's partition nodes (enc_lds.h NODE_SLOTS): which quadrant a node belongs to, which slot it takes
 HENC_INLINE int node_quadrant(int idx) { return idx < NODES_D3 ? (idx - NODES_RESIDENT) >> 4 : (idx - NODES_D3) >> 6; }      // of a node of depth 3 or 4
 HENC_INLINE int node_slot(int idx)
 {
 	return idx < NODES_RESIDENT ? idx : (idx < NODES_D3 ? NODES_RESIDENT + ((idx - NODES_RESIDENT) & (NODE_QUAD_D3 - 1)) : NODES_RESIDENT + NODE_QUAD_D3 + ((idx - NODES_D3) & (NODE_QUAD_D4 - 1)));
 }
-constexpr int NHELP_ = 1
-#if defined(HENC_NHELP)
-	+ (HENC_NHELP) - 1
-#endif
-	;
-constexpr int HSCRATCH_ELEMS = 2048 + 144;   // int16 per helper wavefront (its scratch sits between the nodes and the sequence parameters: k_encode.hip)
-constexpr int LDS_OFF_WORK = 0, LDS_OFF_NODES = (int)((sizeof(Work) + 15) & ~(size_t)15), LDS_OFF_SEQ = LDS_OFF_NODES + (int)((sizeof(Node) * NODE_SLOTS + 15) & ~(size_t)15) + NHELP_ * HSCRATCH_ELEMS * 2,
-	      LDS_OFF_FRAME = LDS_OFF_SEQ + (int)((sizeof(Seq) + 15) & ~(size_t)15), LDS_OFF_BOX = LDS_OFF_SEQ + (int)((sizeof(Seq) + sizeof(FrameCtx) + 31) & ~(size_t)15);
-// (LDS_OFF_RD, the RD_FULL arrays behind the mailbox: below HelperBox)
+// a member of Enc that is a fixed place of the worker's LDS on the device (enc_lds.h), a pointer the checker sets elsewhere
 #if defined(__HIP_DEVICE_COMPILE__)
 #define HENC_AT(T, OFFSET) LdsAt<T, OFFSET>
 #else
 #define HENC_AT(T, OFFSET) FastPtr<T>
 #endif
 
-constexpr int LDS_BOX_BYTES = 160, LDS_ENC_BYTES = 272;      // what the mailbox and a context may take (checked behind HelperBox / Enc)
-constexpr int LDS_OFF_ENC = LDS_OFF_BOX + LDS_BOX_BYTES;      // the worker's context, then one per helper
-constexpr int LDS_OFF_RD = LDS_OFF_ENC + (1 + NHELP_) * LDS_ENC_BYTES;
 struct Enc {
 	unsigned long long *prof;   // PF_COUNT accumulators of this worker (profiling build), else unused
 	HENC_AT(const Seq, LDS_OFF_SEQ) seq;
@@ -132,14 +116,14 @@ struct Enc {
 	FastPtr<const FastTables> ft;   // the tables a TU reads, in the worker's fast memory (enc_prims.h)
 	GeoTable geo;
 	CtuInfo *ctus;         // all CTUs of the picture (persistent across frames)
-	CtuPublic *ctu;           // the side-info record of the CTU being encoded: ctu_g's (HBM), or the worker's fast copy of it (ctu_fast != nullptr) while the CTU is encoded -
-	                          // a plain pointer: FastPtr promises the compiler LDS, which is only true for the copy
+	CtuPublic *ctu;           // the side-info record of the CTU being encoded: ctu_g's (HBM)
 	CtuInfo *ctu_g;        // its home in the picture array (logs, nodes; neighbours are ctu_g - 1, ctu_g - wctu ...)
-	CtuPublic *ctu_fast;
+	void *unused0_;        // (8 bytes that keep every member behind at its place within a 16-byte line of LDS, as nodes_unused_ below does: without the two the compiler pairs
+	                       // the members' loads differently and k_encode_ctus spills 7 vector registers instead of 1 - profiles/worker_lds_refactor.md)
 	HENC_AT(Work, LDS_OFF_WORK) w;
 	HENC_AT(WorkRd, LDS_OFF_RD) wrd;      // RD_FULL only
 	int amvp_node;            // the node whose vector predictor list w.amvp holds, straight from motion estimation (-1: none)
-	int on_helper;            // 0: the worker's context; 1 + h: helper wavefront h's copy (which slot of the level buffer a TU takes: enc_types.h iq_slot)
+	int on_helper;            // 0: the worker's context; 1: the helper wavefront's copy (which slot of the level buffer a TU takes: enc_types.h iq_slot)
 	int16_t *coeff;        // the CTU's coefficient output: 4096 luma + 2 x 1024 chroma, linear per TU in z-order
 	// speculative inputs of a P-frame CTU (enc_ctu.h)
 	uint32_t total_intra_partitions, total_partitions;
@@ -158,37 +142,38 @@ struct Enc {
 	int rd_luma_depth;
 	uint32_t rd_chroma_state;
 	HENC_AT(Node, LDS_OFF_NODES) nodes;      // the CTU's partition nodes while the CTU is encoded: the worker's fast copy (NODE_SLOTS of them, see node_of)
-	Node *nodes_fast;
-	int node_quad;            // the quadrant whose depth-4 nodes are in the fast copy (-1: none yet)
-	// helper wavefronts of the worker (device only; nullptr = everything runs on the group itself)
+	void *nodes_unused_;
+	int node_quad;           // the quadrant whose depth-4 nodes are in the fast copy (-1: none yet)
+	// the helper wavefront of the worker (device only; nullptr = everything runs on the group itself)
 	HENC_AT(struct HelperBox, LDS_OFF_BOX) box;
-	FastPtr<int16_t> adi_c;              // neighbour array of a chroma block: Work::adi, or a helper's own
-	FastPtr<int16_t> mc_tmp_y;           // first-stage buffer of a two-stage luma interpolation (and its row pitch): Work::sub_tmp / 72, or a helper's own
+	FastPtr<int16_t> adi_c;              // neighbour array of a chroma block: Work::adi, or the helper's own
+	FastPtr<int16_t> mc_tmp_y;           // first-stage buffer of a two-stage luma interpolation (and its row pitch): Work::sub_tmp / 72, or the helper's own
 	int mc_tmp_y_stride;
-	FastPtr<int16_t> mc_tmp_c;           // first-stage buffer of a two-stage chroma interpolation: Work::sub_tmp, or a helper's own
-	FastPtr<int16_t> scratch_a, scratch_b;   // transform coefficients / rounding remainders of the TU in flight: Work::pred_aux / delta_u, or a helper's own
+	FastPtr<int16_t> mc_tmp_c;           // first-stage buffer of a two-stage chroma interpolation: Work::sub_tmp, or the helper's own
+	FastPtr<int16_t> scratch_a, scratch_b;   // transform coefficients / rounding remainders of the TU in flight: Work::pred_aux / delta_u, or the helper's own
 	int hseq[NHELP_MAX];
-	int bgseq, bg_node;       // the helper's background intra search (bg_post ... bg_take / bg_quiesce below): jobs posted so far, the node of the one outstanding (-1: none)
+	int bgseq, bg_node;      // the helper's background intra search (bg_post ... bg_take / bg_quiesce below): jobs posted so far, the node of the one outstanding (-1: none)
 };
 
-// Two helper wavefronts per row worker take the chroma components of a step whose three components are independent (motion compensation, the
-// transform chain of a TU) and single candidates of the intra mode search, while the worker itself does luma / the first candidate.  The worker
-// posts a job in LDS and goes on; a helper runs the same SPMD code on its own 64 lanes with its own scratch and reports back.
+// One helper wavefront per row worker takes the chroma components of a step whose three components are independent (motion compensation, the
+// transform chain of a TU) and single candidates of the intra mode search, while the worker itself does luma / the other candidate.  The worker
+// posts a job in LDS and goes on; the helper runs the same SPMD code on its own 64 lanes with its own scratch and reports back.
 enum { HJOB_NONE = 0, HJOB_NEW_CTU, HJOB_INTER_TU, HJOB_INTRA_SAD, HJOB_SYNC_CU, HJOB_SSD, HJOB_CHROMA_SEARCH, HJOB_CHROMA_TU, HJOB_QUAD_C, HJOB_QUIT };
-// One helper per worker: it takes BOTH chroma planes of a step, one after the other, while the worker does luma (a workgroup of two wavefronts, so that more
-// workers fit a CU: k_encode.hip).  HENC_NHELP=2 builds the round-4 arrangement, a helper per chroma plane (a third was measured then: 3 % slower).
+// It takes BOTH chroma planes of a step, one after the other, while the worker does luma (a workgroup of two wavefronts, so that four workers fit a CU:
+// k_encode.hip workers_per_cu).  The helper index below is round 4's arrangement, a helper per chroma plane (a third was measured then: 3 % slower); the layout of a
+// worker's LDS (enc_lds.h LDS_WAVES) is for one helper, and no build with another number exists.
 #if !defined(HENC_NHELP)
 #define HENC_NHELP 1
 #endif
 constexpr int NHELP = HENC_NHELP;
-static_assert(NHELP == NHELP_ && (NHELP == 1 || NHELP == 2), "one helper for both chroma planes, or one per plane");
+static_assert(1 + NHELP == LDS_WAVES, "enc_lds.h lays a worker's LDS out for one helper wavefront");
 constexpr int COMP_UV = 3;   // a helper job's component argument: U, then V
 struct HelperBox {
 	int cmd[NHELP], done[NHELP];   // sequence numbers: helper h runs its next job when cmd[h] moves on, and sets done[h] = cmd[h] when finished
 	int job[NHELP];
 	int a[NHELP][8];
 	uint32_t r[NHELP][8];
-	// a second, background slot (one helper): the intra mode search of the CU the worker is evaluating, run between the helper's ordinary jobs
+	// a second, background slot: the intra mode search of the CU the worker is evaluating, run between the helper's ordinary jobs
 	int bg_cmd, bg_done, bg_cancel, bg_ni, bg_depth, bg_mode, bg_bits;
 };
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -285,8 +270,8 @@ HENC_HD bool bg_take(const G g, Enc &__restrict__ e, int ni, int *mode, int *bit
 #endif
 }
 
-// Does the group that runs the decision walk have helper wavefronts?  On the device always (every worker of k_encode_pool / k_encode_ctus has its two helpers;
-// the helpers themselves only run leaf jobs: a TU chain, a SAD, a copy), on the CPU never - a constant, so that each build carries one of the two paths (as a
+// Does the group that runs the decision walk have a helper wavefront?  On the device always (every worker of k_encode_pool / k_encode_ctus has its helper;
+// the helper itself only runs leaf jobs: a TU chain, a SAD, a copy), on the CPU never - a constant, so that each build carries one of the two paths (as a
 // run-time test of Enc::box both were compiled into the worker's code, and the decision code is several times the instruction cache).
 #if defined(__HIP_DEVICE_COMPILE__)
 #define HENC_HELPERS(e) true
@@ -570,7 +555,7 @@ HENC_HD void sync_motion_buffers_chroma(const G g, Enc &__restrict__ e, int ni, 
 	sync_cu_comp(g, e, ni, q_src, q_dst, d_src, d_dst, COMP_V);
 }
 
-// both: with helper wavefronts the chroma planes are copied while the worker copies luma
+// both: with a helper wavefront the chroma planes are copied while the worker copies luma
 template <class G>
 HENC_HD void sync_motion_buffers(const G g, Enc &__restrict__ e, int ni, int q_src, int q_dst, int d_src, int d_dst)
 {

@@ -822,17 +822,13 @@ HENC_HD void ctu_begin(const G g, Enc &__restrict__ e, int ctu_num)
 	const Seq &S = *e.seq;
 	Work &w = *e.w;
 	e.ctu_g = e.ctus + ctu_num;
-	// the side-info record and the partition nodes are read and written all through the walk: a worker with fast memory of its own works on copies
-	if (e.ctu_fast) {
-		lin_copy_words(g, (const uint32_t *)(const CtuPublic *)e.ctu_g, (uint32_t *)e.ctu_fast, (int)(sizeof(CtuPublic) / 4));
-		e.ctu = e.ctu_fast;
-	} else e.ctu = e.ctu_g;
+	// the partition nodes are read and written all through the walk: the worker works on a copy in its fast memory (the side-info record stays where it is)
+	e.ctu = e.ctu_g;
 #if !defined(__HIPCC__)
-	e.nodes_fast = (Node *)(((uintptr_t)w.nodes_fast_store + 15) & ~(uintptr_t)15);
+	e.nodes = (Node *)(((uintptr_t)w.nodes_fast_store + 15) & ~(uintptr_t)15);
 	e.wrd = w.rd_store;
 #endif
-	lin_copy_words(g, (const uint32_t *)e.ctu_g->nodes, (uint32_t *)e.nodes_fast, (int)(sizeof(Node) * NODES_RESIDENT / 4));
-	e.nodes = e.nodes_fast;
+	lin_copy_words(g, (const uint32_t *)e.ctu_g->nodes, (uint32_t *)&e.nodes[0], (int)(sizeof(Node) * NODES_RESIDENT / 4));
 	e.node_quad = -1;
 	CtuPublic &c = *e.ctu;
 	e.scratch_a = w.pred_aux;
@@ -935,7 +931,6 @@ HENC_HD void ctu_end(const G g, Enc &__restrict__ e)
 	e.ctu_g->n_stale_pred = e.n_stale_pred;
 	e.ctu_g->n_ratio_cmp = e.n_ratio_cmp;
 	g.sync();
-	if (e.ctu_fast) lin_copy_words(g, (const uint32_t *)e.ctu_fast, (uint32_t *)(CtuPublic *)e.ctu_g, (int)(sizeof(CtuPublic) / 4));
 	nodes_write_back(g, e);
 	PRIM_END(PP_CTU_IO);
 }

@@ -20,8 +20,8 @@
 #define HENC_PRIM __device__   // block primitives: the compiler decides (forcing them out of line does not pay: all of them +3 %, only the large ones - intra prediction, SSD, reference fill - +2 %)
 #endif
 #define HENC_INLINE __host__ __device__ __forceinline__   // the small helpers are also used by the host entropy stage
-// Are the TU tables (FastTables, enc_prims.h) kept in the worker's fast memory?  Not on the device since two workers share a CU's LDS (k_encode.hip:
-// LDS_KEEPS_TU_TABLES must agree) - a constant, so that the transform / quantiser primitives carry one table source instead of a run-time choice of two.
+// Are the TU tables (FastTables, enc_prims.h) kept in the worker's fast memory?  Not on the device since two workers share a CU's LDS (enc_lds.h)
+// - a constant, so that the transform / quantiser primitives carry one table source instead of a run-time choice of two.
 #define HENC_TU_TABLES_IN_LDS 0
 #define HENC_FT(e) ((const FastTables *)nullptr)
 #else
@@ -140,8 +140,8 @@ using PairGrp = PairGrpOf<WaveGrp>;
 
 #endif
 
-// The row worker's state - its Work, the CTU's nodes and record, the geometry, the sequence / frame parameters, the helper mailbox and scratch - lives in
-// LDS on the device (k_encode.hip).  The pointers to it travel through Enc as generic pointers, which the compiler can only serve with flat_* instructions:
+// The row worker's state - its Work, the CTU's nodes, the sequence / frame parameters, the helper mailbox and scratch - lives in
+// LDS on the device (enc_lds.h).  The pointers to it travel through Enc as generic pointers, which the compiler can only serve with flat_* instructions:
 // 64-bit address arithmetic, and a wait on every outstanding store before any load result is used.  FastPtr says where they point (a cast to the LDS address
 // space and back, which address-space inference propagates into everything derived from the pointer), so these accesses become ds_* instructions.
 // On the CPU (checker build, host pass) it is an ordinary pointer.
@@ -226,9 +226,9 @@ struct FastPtr {
 };
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// A member that IS a fixed place in the workgroup's LDS (the worker's Work, the CTU's nodes, the sequence / frame parameters, the helper mailbox: k_encode.hip lays
+// A member that IS a fixed place in the workgroup's LDS (the worker's Work, the CTU's nodes, the sequence / frame parameters, the helper mailbox: enc_lds.h lays
 // them out at constant offsets).  As FastPtr members of Enc these pointers were data - and Enc, whose address goes to every out-of-line function of the walk, lives
-// in private memory: each `e.w->` began with a scratch load.  An LdsAt holds nothing; assignments to it are accepted and ignored (the kernels still "set" them).
+// in private memory: each `e.w->` began with a scratch load.  An LdsAt holds nothing, and nothing can be assigned to it.
 extern __shared__ __align__(16) unsigned char henc_lds_base[];
 template <class T, int OFFSET>
 struct LdsAt {
@@ -238,8 +238,6 @@ struct LdsAt {
 	HENC_INLINE T &operator[](int i) const { return get()[i]; }
 	HENC_INLINE operator T *() const { return get(); }
 	HENC_INLINE explicit operator bool() const { return true; }
-	HENC_INLINE LdsAt &operator=(T *) { return *this; }
-	HENC_INLINE LdsAt &operator=(decltype(nullptr)) { return *this; }
 };
 #endif
 

@@ -4,16 +4,13 @@
 // Convention: inputs must be visible to the group on entry (caller synced), outputs are visible on return.
 #pragma once
 #include "enc_types.h"
+#include "enc_lds.h"
 #include "../tables_layout.h"
 
-// Primitive-level timers of the profiling build (-DHENC_PROFILE, device only): lane 0 adds s_memtime ticks and a call count per primitive class
-// to a small table at the end of the worker's LDS; k_encode_ctus folds it into the per-row profile.
-enum { PP_SAD = 0, PP_SSD, PP_BLK, PP_FILLREF, PP_ADIFILT, PP_INTRAPRED, PP_INTERP, PP_TRF, PP_TRI, PP_QUANT, PP_DEQUANT, PP_CAND, PP_SYNC, PP_INFO, PP_CTU_IO, PP_HWAIT, PP_COUNT };
+// the profiling build's primitive timers (enc_lds.h: PP_*, the timer table behind the worker's state - that build holds three workers per CU where the product holds four)
 #if defined(__HIPCC__) && defined(HENC_PROFILE)
-extern __shared__ __align__(16) unsigned char henc_lds[];
-#define HENC_LDS_PROF_OFFSET 43008      // (behind the worker state: the profiling build holds three workers per CU where the product holds four; k_encode.hip checks the place)
 #define PRIM_T0() const unsigned long long prim_t0_ = __builtin_amdgcn_s_memtime()
-#define PRIM_END(cat) do { if (threadIdx.x == 0) { unsigned long long *pp_ = (unsigned long long *)(henc_lds + HENC_LDS_PROF_OFFSET); pp_[cat] += __builtin_amdgcn_s_memtime() - prim_t0_; pp_[PP_COUNT + (cat)]++; } } while (0)
+#define PRIM_END(cat) do { if (threadIdx.x == 0) { unsigned long long *pp_ = henc::lds_prof(); pp_[cat] += __builtin_amdgcn_s_memtime() - prim_t0_; pp_[PP_COUNT + (cat)]++; } } while (0)
 #else
 #define PRIM_T0() do { } while (0)
 #define PRIM_END(cat) do { } while (0)

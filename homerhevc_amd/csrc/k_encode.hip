@@ -2,7 +2,7 @@
 //
 // Row-per-thread schedule (wfpp_num_threads > 1, the product's mode): the reference's WPP threads (wfpp_encoder_thread, hmr_encoder_lib.c:2849-2975)
 // pinned to the synchronous wavefront - CTU (row, c) belongs to step c + 2 row, and a step may start when the step before it is complete.
-// k_encode_pool runs that as a task pool: persistent workgroups (a worker wavefront + NHELP helper wavefronts, two workgroups per CU) claim the next
+// k_encode_pool runs that as a task pool: persistent workgroups (a worker wavefront + NHELP helper wavefronts, four workgroups per CU) claim the next
 // CTU of ANY picture of the launch whose step is open, load the owning WPP thread's state (mode buffers, "seen intra"), encode, store the state and
 // close the step with a release store when they were its last CTU.  No workgroup waits for work that is not already running.
 //
@@ -99,54 +99,29 @@ constexpr int PRED_STATE_BYTES = (64 * 64 + 2 * 32 * 32) * (int)sizeof(pred_t), 
 static_assert(offsetof(Work, pred_c) == offsetof(Work, pred_y) + 64 * 64 * sizeof(pred_t) && sizeof(((Work *)nullptr)->pred_c) == 2 * 32 * 32 * sizeof(pred_t), "the prediction windows are one block of Work");
 static_assert(MODE_STATE_BYTES % 16 == 0 && offsetof(Work, pred_y) % 16 == 0, "wave_copy_quads alignment");
 
-// LDS of a row worker: its Work, a copy of the CTU's partition nodes and of the partition geometry
-constexpr size_t LDS_WORK = (sizeof(Work) + 15) & ~(size_t)15, LDS_NODES = (sizeof(Node) * NODE_SLOTS + 15) & ~(size_t)15,
-		 LDS_GEO = NHELP * HSCRATCH_ELEMS * 2;   // the helpers' scratch (per helper: 2 x 1024 coefficients - a 32 x 32 chroma TU - and a chroma neighbour array): behind Work and the nodes, so
-		                                         // that the post-decision stage, which runs between two CTUs when the helpers have no job, can use the three as one scratch area.
-		                                         // (The partition geometry, whose place this was, is in constant memory: enc_common.h GeoTable.)
 namespace henc { __constant__ Geo henc_geo_table[NNODES]; }
-// Two things that used to sit in LDS do not any more, so that TWO row workers fit a CU (80 KB each): the CTU's side-info record (the worker reads and writes
-// it in HBM: measured in round 2 to make no difference) and the TU tables (FastTables: transform bases, scans, quantiser cells - from DevTables through L2
-// instead: 1-2 % per worker, against twice the workers).  Set to true to get them back (one worker per CU).
-constexpr bool LDS_KEEPS_CTU_RECORD = false, LDS_KEEPS_TU_TABLES = false;
-static_assert(LDS_KEEPS_TU_TABLES == (HENC_TU_TABLES_IN_LDS != 0), "enc_platform.h: HENC_FT");
-constexpr size_t LDS_SEQ = (sizeof(Seq) + sizeof(FrameCtx) + 31) & ~(size_t)15, LDS_CTU = LDS_KEEPS_CTU_RECORD ? (sizeof(CtuPublic) + 15) & ~(size_t)15 : 0,
-		 LDS_FT = LDS_KEEPS_TU_TABLES ? (sizeof(FastTables) + 15) & ~(size_t)15 : 0;
-#if defined(HENC_PROFILE)
-constexpr size_t LDS_BOX = LDS_BOX_BYTES + (1 + NHELP) * LDS_ENC_BYTES, LDS_HSCRATCH = 0, LDS_RD = (sizeof(WorkRd) + 15) & ~(size_t)15;
-constexpr size_t LDS_BYTES = HENC_LDS_PROF_OFFSET + 2 * PP_COUNT * 8;   // the primitive timers sit at HENC_LDS_PROF_OFFSET
-constexpr size_t LDS_FT_OFFSET = LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU + LDS_BOX + LDS_HSCRATCH;
-static_assert(LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU + LDS_BOX + LDS_HSCRATCH + LDS_FT + LDS_RD <= HENC_LDS_PROF_OFFSET, "profile table overlaps the worker state");
-#else
-constexpr size_t LDS_BOX = LDS_BOX_BYTES + (1 + NHELP) * LDS_ENC_BYTES, LDS_HSCRATCH = 0, LDS_RD = (sizeof(WorkRd) + 15) & ~(size_t)15;
-constexpr size_t LDS_BYTES = LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU + LDS_BOX + LDS_HSCRATCH + LDS_FT + LDS_RD;
-constexpr size_t LDS_FT_OFFSET = LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU + LDS_BOX + LDS_HSCRATCH;
-#endif
-static_assert(sizeof(SubpelScratch) <= LDS_WORK + LDS_NODES + LDS_GEO, "task S works where the post stage does");
-static_assert(sizeof(PostScratch) <= LDS_WORK + LDS_NODES + LDS_GEO, "the post stage works in what is idle between two CTUs: the worker's Work area, the CTU's partition nodes, the helpers' scratch");
-#if !defined(HENC_PROFILE)
-static_assert(LDS_OFF_RD == (int)(LDS_BYTES - LDS_RD), "the RD_FULL arrays are the tail of a worker's LDS");
-#endif
-static_assert(LDS_OFF_ENC == (int)(LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU + LDS_BOX_BYTES) || LDS_FT != 0 || LDS_CTU != 0, "the RD_FULL arrays are the tail of a worker's LDS: launches without RD_FULL pictures leave them out");
-static_assert(LDS_OFF_NODES == (int)LDS_WORK && LDS_OFF_SEQ == (int)(LDS_WORK + LDS_NODES + LDS_GEO) && LDS_OFF_BOX == (int)(LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU),
-	      "enc_common.h: the fixed places of Enc's LDS members");
+// A row worker's LDS is laid out in enc/enc_lds.h.  What this file adds are the constraints of what runs in it:
+static_assert(sizeof(SubpelScratch) <= LDS_OFF_SEQ, "task S works where the post stage does");
+static_assert(sizeof(PostScratch) <= LDS_OFF_SEQ, "the post stage works in what is idle between two CTUs: the worker's Work area, the CTU's partition nodes, the helper's scratch");
 #if !defined(HENC_WAVES_PER_EU)
 #define HENC_WAVES_PER_EU 2      // wavefronts per SIMD the pool kernel's register budget allows (512 / this registers per lane)
 #endif
-constexpr int ENC_THREADS = 64 * (1 + NHELP);   // the row worker + its helper wavefronts: one wavefront per SIMD of the CU
-static_assert(LDS_BYTES <= 160 * 1024, "a workgroup has 160 KiB of LDS on gfx950");
-// workers a CU holds: by LDS (160 KiB in 1280-byte granules on gfx950) and by wavefront slots; a launch without RD_FULL pictures asks for LDS_BYTES - LDS_RD
+constexpr int ENC_THREADS = 64 * LDS_WAVES;   // the row worker + its helper wavefront
+// workers a CU holds: by LDS (160 KiB in 1280-byte granules on gfx950) and by wavefront slots; a launch without RD_FULL pictures asks for LDS_LEAN_BYTES
 constexpr int workers_per_cu(size_t lds_bytes)
 {
-	const int by_lds = (int)((160 * 1024) / ((lds_bytes + 1279) / 1280 * 1280)), by_waves = 4 * HENC_WAVES_PER_EU / (1 + NHELP);
+	const int by_lds = (int)((160 * 1024) / ((lds_bytes + 1279) / 1280 * 1280)), by_waves = 4 * HENC_WAVES_PER_EU / LDS_WAVES;
 	return by_lds < by_waves ? by_lds : by_waves;
 }
-constexpr int WORKERS_PER_CU = workers_per_cu(LDS_BYTES - LDS_RD);
-#if !defined(HENC_PROFILE) && HENC_WAVES_PER_EU == 2 && HENC_NHELP == 1
+constexpr int WORKERS_PER_CU = workers_per_cu(lds_request(false));
+#if !defined(HENC_PROFILE) && HENC_WAVES_PER_EU == 2
 static_assert(WORKERS_PER_CU == 4, "a worker's LDS (without the RD_FULL arrays) has to stay within a quarter of the CU's: 32 granules of 1280 bytes");
 #endif
-#if defined(HENC_PRINT_LDS)
-static_assert(LDS_BYTES - LDS_RD == 0 && LDS_WORK == 0 && LDS_NODES == 0 && LDS_BOX == 0 && sizeof(PostScratch) == 0 && WORKERS_PER_CU == 0, "sizes");
+#if defined(HENC_PRINT_LDS)      // (-DHENC_PRINT_LDS -fsyntax-only: the compiler prints each figure in the note behind its assertion)
+#define HENC_PRINT_(x) static_assert((long)(x) == -1, #x)
+HENC_PRINT_(LDS_OFF_WORK); HENC_PRINT_(LDS_OFF_NODES); HENC_PRINT_(LDS_OFF_HSCRATCH); HENC_PRINT_(LDS_OFF_SEQ); HENC_PRINT_(LDS_OFF_FRAME); HENC_PRINT_(LDS_OFF_BOX); HENC_PRINT_(LDS_OFF_ENC); HENC_PRINT_(LDS_OFF_RD);
+HENC_PRINT_(LDS_OFF_PROF); HENC_PRINT_(LDS_FULL_BYTES); HENC_PRINT_(LDS_LEAN_BYTES); HENC_PRINT_(LDS_PROF_BYTES); HENC_PRINT_(lds_request(false)); HENC_PRINT_(lds_request(true));
+HENC_PRINT_(sizeof(HelperBox)); HENC_PRINT_(sizeof(Enc)); HENC_PRINT_(sizeof(PostScratch)); HENC_PRINT_(sizeof(SubpelScratch)); HENC_PRINT_(WORKERS_PER_CU);
 #endif
 
 // a helper wavefront: run the jobs the worker posts (HelperBox, enc_common.h) until it says quit
@@ -156,18 +131,16 @@ static_assert(LDS_BYTES - LDS_RD == 0 && LDS_WORK == 0 && LDS_NODES == 0 && LDS_
 template <class G>
 __device__ __forceinline__ bool helper_serve(HelperBox *box, int h, int16_t *scratch, const G g, int seq)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
-	Enc &e = *(Enc *)(lds + LDS_OFF_ENC + (1 + h) * LDS_ENC_BYTES);      // (this helper's own context; LDS starts zeroed)
+	Enc &e = lds_helper_enc(h);      // (this helper's own context; LDS starts zeroed)
 	HENC_ENC_IN_LDS(e);
-	const Enc &worker = *(const Enc *)(lds + LDS_OFF_ENC);
+	const Enc &worker = lds_enc();
 	{
 		const int job = box->job[h];
 		if (job == HJOB_QUIT) return false;
 		if (job == HJOB_NEW_CTU) {
 			wave_copy_words(&e, &worker, (int)sizeof(Enc), g.tid);
 			g.sync();
-			e.box = nullptr;
-			e.on_helper = 1 + h;      // (its own slot of the chroma level buffer: enc_types.h iq_slot)
+			e.on_helper = 1 + h;     // (its own slot of the chroma level buffer: enc_types.h iq_slot)
 			e.scratch_a = scratch;
 			e.scratch_b = scratch + 1024;
 			e.adi_c = scratch + 2048;
@@ -268,8 +241,7 @@ __device__ __attribute__((noinline)) bool helper_serve_out(HelperBox *box, int h
 // pool's schedules do not read it) - every candidate on this wavefront, an ordinary job served before each of them.  false: HJOB_QUIT was among those.
 __device__ __attribute__((noinline)) bool helper_bg_search(HelperBox *box, int h, int16_t *scratch, const WaveGrp g, int &seq, int bgseq)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
-	Enc &e = *(Enc *)(lds + LDS_OFF_ENC + (1 + h) * LDS_ENC_BYTES);
+	Enc &e = lds_helper_enc(h);
 	HENC_ENC_IN_LDS(e);
 	const int ni = uni(box->bg_ni), depth = uni(box->bg_depth);
 	const Geo &q = e.geo[ni];
@@ -332,27 +304,49 @@ __device__ __attribute__((noinline)) void helper_loop(HelperBox *box, int h, int
 	}
 }
 
-// A workgroup is a row worker (wavefront 0) and its two helpers.  rows_enter sets the mailbox up and sends the helper wavefronts into their service loop; it
-// returns true on the worker only.  release_helpers lets them go (without it the workgroup never ends).
+// A workgroup is a row worker (wavefront 0) and its helper.  rows_enter sets the mailbox up and sends the helper wavefront into its service loop; it
+// returns true on the worker only.  release_helpers lets it go (without it the workgroup never ends).
 template <bool LAT = false, class G = WaveGrp>
 __device__ __forceinline__ bool rows_enter(unsigned lds_bytes)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
-	HelperBox *box = (HelperBox *)(lds + LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU);
 	const int wave = (int)(threadIdx.x >> 6);
-	// LDS keeps what the last workgroup on this CU left in it: everything starts from zero (the helpers' scratch included), whatever ran here before
-	for (int i = (int)threadIdx.x; i < (int)(lds_bytes / 4); i += ENC_THREADS) ((uint32_t *)lds)[i] = 0;
+	// LDS keeps what the last workgroup on this CU left in it: everything starts from zero (the helper's scratch included), whatever ran here before
+	lds_zero(lds_bytes, (int)threadIdx.x, ENC_THREADS);
 	__syncthreads();
 	if (wave > 0) {
-		helper_loop<LAT, G>(box, wave - 1, (int16_t *)(lds + LDS_WORK + LDS_NODES) + (wave - 1) * HSCRATCH_ELEMS);
+		helper_loop<LAT, G>(lds_box(), wave - 1, lds_helper_scratch() + (wave - 1) * HSCRATCH_ELEMS);
 		return false;
 	}
 	return true;
 }
+// ... and between the two the worker prepares its context, once: what differs between the kernels is given (the tables and the CTU array, which the pool sets per
+// picture instead, and the profile row), the sequence numbers start where rows_enter's zeroes left the mailbox.  In line in every kernel: as a function of its own it
+// would be compiled for the loosest register budget among the kernels that share it.
+__device__ __forceinline__ void enc_prepare(Enc &__restrict__ e, const DevTables *tables, CtuInfo *ctus, unsigned long long *prof)
+{
+	HENC_ENC_IN_LDS(e);      // (the context lives in LDS: enc_platform.h)
+	e.T = tables;
+	e.geo.p = nullptr;
+	e.ctus = ctus;
+	e.ctu = nullptr;
+	e.ctu_g = nullptr;
+	e.node_quad = -1;
+	e.on_helper = 0;
+	for (int h = 0; h < NHELP; h++) e.hseq[h] = 0;
+	e.bgseq = 0;
+	e.bg_node = -1;
+	e.prof = prof;
+	e.timeline = nullptr;
+}
+// the sequence and frame parameters of a picture into the worker's copies: they are read all through the control code
+__device__ __forceinline__ void params_load(int tid, const Seq *seq, const FrameCtx *frame)
+{
+	for (int i = tid; i < (int)(sizeof(Seq) / 4); i += 64) ((uint32_t *)lds_seq())[i] = ((const uint32_t *)seq)[i];
+	for (int i = tid; i < (int)(sizeof(FrameCtx) / 4); i += 64) ((uint32_t *)lds_frame())[i] = ((const uint32_t *)frame)[i];
+}
 __device__ __forceinline__ void release_helpers(int *hseq)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
-	HelperBox *box = (HelperBox *)(lds + LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU);
+	HelperBox *box = lds_box();
 	if ((threadIdx.x & 63) == 0)
 		for (int h = 0; h < NHELP; h++) {
 			box->job[h] = HJOB_QUIT;
@@ -362,51 +356,19 @@ __device__ __forceinline__ void release_helpers(int *hseq)
 // the work of one row worker on one picture: `row` of the picture described by d (hseq: the helpers' job counters, which live as long as the workgroup)
 __device__ __forceinline__ void encode_row(const EncDev &d, int pass, int row, int *hseq)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
 	const Seq &S = *d.seq;
 	const int W = S.wctu, H = S.hctu;
 	WaveGrp g{(int)(threadIdx.x & 63)};
-	Work *lw = (Work *)lds;
-	HelperBox *box = (HelperBox *)(lds + LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU);
-	for (int i = g.tid; i < (int)(LDS_WORK / 4); i += 64) ((uint32_t *)lds)[i] = 0;
-	g.sync();
-	// the sequence and frame parameters are read all through the control code: a copy next to the worker
-	Seq *lseq = (Seq *)(lds + LDS_WORK + LDS_NODES + LDS_GEO);
-	FrameCtx *lframe = (FrameCtx *)((uint8_t *)lseq + ((sizeof(Seq) + 15) & ~(size_t)15));
-	for (int i = g.tid; i < (int)(sizeof(Seq) / 4); i += 64) ((uint32_t *)lseq)[i] = ((const uint32_t *)d.seq)[i];
-	for (int i = g.tid; i < (int)(sizeof(FrameCtx) / 4); i += 64) ((uint32_t *)lframe)[i] = ((const uint32_t *)d.frame)[i];
+	Work *lw = lds_work();
+	FrameCtx *lframe = lds_frame();
+	params_load(g.tid, d.seq, d.frame);
 	if (g.tid == 0) lw->slow = (HENC_GLOBAL_PTR(WorkSlow))(d.work_slow + row);
 	g.sync();
 	if (g.tid == 0) lframe->scene_cut_ctu = d.counters[2];
-	// the transform bases, scans and this frame's quantiser lists next to the worker (enc_prims.h: FastTables)
-	FastTables *lft = LDS_KEEPS_TU_TABLES ? (FastTables *)(lds + LDS_FT_OFFSET) : nullptr;
-	if (lft) fast_tables_fill(g, *lft, d.tables, lframe->qp % 6, chroma_qp_table(lframe->qp + S.chroma_qp_offset) % 6);
-#if defined(HENC_PROFILE)
-	if (g.tid < 2 * PP_COUNT) ((unsigned long long *)(lds + HENC_LDS_PROF_OFFSET))[g.tid] = 0;
-#endif
 	g.sync();
-	Enc &e = *(Enc *)(lds + LDS_OFF_ENC);      // (the context lives in LDS: enc_platform.h HENC_ENC_IN_LDS)
+	Enc &e = lds_enc();
 	HENC_ENC_IN_LDS(e);
-	e.seq = lseq;
-	e.f = lframe;
-	e.T = d.tables;
-	e.ft = lft;
-	e.geo.p = nullptr;
-	e.ctus = d.ctus;
-	e.ctu = nullptr;
-	e.w = lw;
-	e.nodes = nullptr;
-	e.nodes_fast = (Node *)(lds + LDS_WORK);
-	e.node_quad = -1;
-	e.on_helper = 0;
-	e.ctu_g = nullptr;
-	e.ctu_fast = LDS_KEEPS_CTU_RECORD ? (CtuPublic *)(lds + LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ) : nullptr;
-	e.box = box;
-	for (int h = 0; h < NHELP; h++) e.hseq[h] = hseq[h];
-	e.bgseq = 0;
-	e.bg_node = -1;
-	e.prof = d.prof ? d.prof + (size_t)row * PF_COUNT : nullptr;
-	e.timeline = nullptr;
+	enc_prepare(e, d.tables, d.ctus, d.prof ? d.prof + (size_t)row * PF_COUNT : nullptr);
 	uint32_t *my_prefix = d.prefix + (size_t)row * (W + 1);
 	if (pass <= 0 && g.tid == 0) my_prefix[0] = 0;
 	int encodes = 0;
@@ -483,7 +445,7 @@ __device__ __forceinline__ void encode_row(const EncDev &d, int pass, int row, i
 	if (g.tid == 0 && encodes) atomicAdd(&d.counters[1], encodes);
 #if defined(HENC_PROFILE)
 	if (g.tid == 0 && e.prof) {
-		const unsigned long long *pp = (const unsigned long long *)(lds + HENC_LDS_PROF_OFFSET);
+		const unsigned long long *pp = lds_prof();
 		for (int k = 0; k < 2 * PP_COUNT; k++) e.prof[PF_PRIM0 + k] += pp[k];
 	}
 #endif
@@ -515,7 +477,7 @@ __device__ __forceinline__ void pool_step_rows(int t, int W, int H, int *r_lo, i
 }
 
 template <class G>
-__device__ void pool_encode_ctu(const EncDev &d, Enc &__restrict__ e, const G g, Seq *lseq, FrameCtx *lframe, FastTables *lft, int t, int row, int *cached_rem, const int *abort_flag)
+__device__ void pool_encode_ctu(const EncDev &d, Enc &__restrict__ e, const G g, Seq *lseq, FrameCtx *lframe, int t, int row, const int *abort_flag)
 {
 	HENC_ENC_IN_LDS(e);
 	const Seq &S = *lseq;
@@ -540,11 +502,6 @@ __device__ void pool_encode_ctu(const EncDev &d, Enc &__restrict__ e, const G g,
 		// the zeroes it was created with before (the worker's fast memory is not the thread's: enc_rdo.h)
 		const int seen = d.thread_seen[me];
 		for (int i = g.tid; i < NPART; i += 64) e.wrd->rd_pred_mode[i] = seen ? PM_INTRA : PM_INTER;
-	}
-	const int rem_y = lframe->qp % 6, rem_c = chroma_qp_table(lframe->qp + S.chroma_qp_offset) % 6;
-	if (lft && (cached_rem[0] != rem_y || cached_rem[1] != rem_c)) {
-		fast_tables_fill(g, *lft, d.tables, rem_y, rem_c);
-		cached_rem[0] = rem_y; cached_rem[1] = rem_c;
 	}
 	g.sync();
 	const int hrow = raster ? row : t / (2 * T) * T;   // thread 0's row that is inside the picture at this step, if any
@@ -601,7 +558,7 @@ __device__ void pool_encode_ctu(const EncDev &d, Enc &__restrict__ e, const G g,
 		HENC_PROF_ADD(e, PF_TOTAL);
 	}
 	if (g.tid == 0 && e.prof) {
-		unsigned long long *pp = (unsigned long long *)(henc_lds + HENC_LDS_PROF_OFFSET);
+		unsigned long long *pp = lds_prof();
 		for (int k = 0; k < 2 * PP_COUNT; k++) { e.prof[PF_PRIM0 + k] += pp[k]; pp[k] = 0; }
 	}
 #else
@@ -691,39 +648,16 @@ __device__ __forceinline__ void encode_pool_body(const EncDev *devs, int nseq, i
 	unsigned long long t_start = wall_clock64();      // when this worker last had something to do (the watchdog's clock)
 	constexpr bool LAT = G::bg;
 	if (!rows_enter<LAT, typename std::conditional<LAT, WaveGrp, G>::type>(lds_bytes)) return;      // (the latency kernel's helpers: the plain group, its loop has the background search)
-	extern __shared__ __align__(16) uint8_t lds[];
 	G g{(int)(threadIdx.x & 63)};
-	Work *lw = (Work *)lds;
-	HelperBox *box = (HelperBox *)(lds + LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ + LDS_CTU);
-	Seq *lseq = (Seq *)(lds + LDS_WORK + LDS_NODES + LDS_GEO);
-	FrameCtx *lframe = (FrameCtx *)((uint8_t *)lseq + ((sizeof(Seq) + 15) & ~(size_t)15));
-	FastTables *lft = LDS_KEEPS_TU_TABLES ? (FastTables *)(lds + LDS_FT_OFFSET) : nullptr;
+	Work *lw = lds_work();
+	Seq *lseq = lds_seq();
+	FrameCtx *lframe = lds_frame();
 	if (g.tid == 0) lw->slow = (HENC_GLOBAL_PTR(WorkSlow))(slow + blockIdx.x);
-#if defined(HENC_PROFILE)
-	if (g.tid < 2 * PP_COUNT) ((unsigned long long *)(lds + HENC_LDS_PROF_OFFSET))[g.tid] = 0;
-#endif
 	g.sync();
-	Enc &e = *(Enc *)(lds + LDS_OFF_ENC);      // (the context lives in LDS: enc_platform.h HENC_ENC_IN_LDS)
+	Enc &e = lds_enc();
 	HENC_ENC_IN_LDS(e);
-	e.seq = lseq;
-	e.f = lframe;
-	e.ft = lft;
-	e.geo.p = nullptr;
-	e.ctu = nullptr;
-	e.w = lw;
-	e.nodes = nullptr;
-	e.nodes_fast = (Node *)(lds + LDS_WORK);
-	e.node_quad = -1;
-	e.on_helper = 0;
-	e.ctu_g = nullptr;
-	e.ctu_fast = LDS_KEEPS_CTU_RECORD ? (CtuPublic *)(lds + LDS_WORK + LDS_NODES + LDS_GEO + LDS_SEQ) : nullptr;
-	e.box = box;
-	for (int h = 0; h < NHELP; h++) e.hseq[h] = 0;
-	e.bgseq = 0;
-	e.bg_node = -1;
-	e.prof = nullptr;
-	e.timeline = nullptr;
-	int cached_rem[2] = {-1, -1}, cached_q = -1, idle_rounds = 0;
+	enc_prepare(e, nullptr, nullptr, nullptr);      // (the tables and the CTUs: of the picture whose CTU is claimed, below)
+	int cached_q = -1, idle_rounds = 0;
 	int start = (int)(blockIdx.x % (unsigned)nseq);
 	for (;;) {
 		// look for a picture with an open step that still has CTUs to hand out: 64 pictures at a time, one per lane
@@ -825,8 +759,7 @@ __device__ __forceinline__ void encode_pool_body(const EncDev *devs, int nseq, i
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // (the step was opened with a release store after its predecessors' results)
 		const EncDev &d = devs[q];      // (by reference: a copy of the 480-byte descriptor is thirty stores to private memory per CTU, and every d.member a load from there)
 		if (q != cached_q) {
-			for (int i = g.tid; i < (int)(sizeof(Seq) / 4); i += 64) ((uint32_t *)lseq)[i] = ((const uint32_t *)d.seq)[i];
-			for (int i = g.tid; i < (int)(sizeof(FrameCtx) / 4); i += 64) ((uint32_t *)lframe)[i] = ((const uint32_t *)d.frame)[i];
+			params_load(g.tid, d.seq, d.frame);
 			cached_q = q;
 			g.sync();
 		}
@@ -842,7 +775,7 @@ __device__ __forceinline__ void encode_pool_body(const EncDev *devs, int nseq, i
 		if (d.raster) row = t / W;
 		else if (hvalid) row = k == 0 ? hrow : (r_lo + k - 1 < hrow ? r_lo + k - 1 : r_lo + k);
 		else row = r_lo + k;
-		pool_encode_ctu(d, e, g, lseq, lframe, lft, t, row, cached_rem, finished + 1);
+		pool_encode_ctu(d, e, g, lseq, lframe, t, row, finished + 1);
 		// close the step when this was its last CTU (the CTU's results were published by the release fence at the end of pool_encode_ctu)
 		if (g.tid == 0) {
 			int *st = state + (size_t)q * POOL_STRIDE;
@@ -939,7 +872,7 @@ struct SrcSlot {
 
 __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void k_encode_ctus(EncDev d, int pass)
 {
-	if (!rows_enter((unsigned)LDS_BYTES)) return;
+	if (!rows_enter((unsigned)lds_request(true))) return;
 	int hseq[NHELP_MAX] = {0, 0, 0};
 	encode_row(d, pass, (int)blockIdx.x, hseq);
 	release_helpers(hseq);
@@ -948,13 +881,12 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(2))
 // passes, so the stage cannot run along with them): one wavefront per workgroup, each runs whatever task is ready until the picture's last task is done.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_post_frame(EncDev d)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
 	WaveGrp g{(int)threadIdx.x};
 	for (int r = (int)blockIdx.x * 64 + g.tid; r < d.seq->hctu; r += (int)gridDim.x * 64) d.post.rows[r].dec = d.seq->wctu;
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 	PostCtx x;
 	x.seq = d.seq; x.f = d.frame; x.T = d.tables; x.geo.p = nullptr; x.ctus = d.ctus; x.coeff = d.coeff; x.pic = &d.post;
-	PostScratch &sc = *(PostScratch *)in_fast_memory((uint8_t *)lds);
+	PostScratch &sc = *(PostScratch *)in_fast_memory((uint8_t *)lds_work());      // (where a worker's post stage has it: the functions behind it then get one address from every caller)
 	const unsigned long long t_start = wall_clock64();
 	while (!post_finished(*d.seq, d.post)) {
 		if (!post_drain(g, x, sc)) {

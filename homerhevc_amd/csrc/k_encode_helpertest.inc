@@ -15,7 +15,6 @@ namespace {
 static_assert(sizeof(hmr_gpu_helper_case) == 216 && sizeof(hmr_gpu_helper_out) == 12064, "include/homer_gpu.h section 18 states these layouts");
 static_assert(sizeof(((Work *)nullptr)->cbf_chroma) == 512 && sizeof(((Work *)nullptr)->adi) == 528 && sizeof(((Work *)nullptr)->srch_sads) == 40 && sizeof(((Work *)nullptr)->srch_modes) == 24,
 	      "hmr_gpu_helper_out mirrors these members of Work");
-static_assert(LDS_OFF_BOX % 4 == 0, "the worker's LDS below the mailbox is cleared in words");
 // The groups of the steps: types of the harness's own, as WalkGrp is one (k_encode_walktest.inc says why) - the worker's walk of the plain launch, the worker's walk of
 // the launch with the latency kernel's helper loop (G::bg: compiled with the background-search hooks), and the plain helper loop with everything helper_serve calls.
 struct HelpGrp : WaveGrp {};
@@ -32,11 +31,10 @@ __device__ __forceinline__ int16_t *help_nbr_place(int16_t *blk, int st, int n, 
 template <class G>
 __device__ __forceinline__ void help_run_case(const G g, Enc &__restrict__ e, const hmr_gpu_helper_case &cs, hmr_gpu_helper_out &o, const uint8_t *arena, WorkSlow *my_slow)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
 	HENC_ENC_IN_LDS(e);
-	Work *lw = (Work *)(lds + LDS_OFF_WORK);
-	Seq *lseq = (Seq *)(lds + LDS_OFF_SEQ);
-	FrameCtx *lframe = (FrameCtx *)(lds + LDS_OFF_FRAME);
+	Work *lw = lds_work();
+	Seq *lseq = lds_seq();
+	FrameCtx *lframe = lds_frame();
 	const int step = uni(cs.step), ni = uni(cs.node);
 	const bool luma_step = step == HMR_GPU_HELPER_INTRA_SEARCH || step == HMR_GPU_HELPER_INTRA_SEARCH_BG;
 	int job[4];
@@ -48,7 +46,7 @@ __device__ __forceinline__ void help_run_case(const G g, Enc &__restrict__ e, co
 	}
 	// the worker's LDS below the mailbox starts from zero, as rows_enter left it (the helper is idle: every job has been waited for, no background search is outstanding);
 	// the mailbox and the contexts keep their sequence numbers
-	for (int i = g.tid; i < LDS_OFF_BOX / 4; i += 64) ((uint32_t *)lds)[i] = 0;
+	lds_zero(LDS_OFF_BOX, g.tid, 64);
 	g.sync();
 	if (cs.curr >= 0) wave_copy_words(lw->curr_y, arena + cs.curr, WALK_WINDOW_BYTES, g.tid);
 	if (cs.pred >= 0) wave_copy_words(lw->pred_y, arena + cs.pred, WALK_WINDOW_BYTES, g.tid);
@@ -243,36 +241,18 @@ __device__ __forceinline__ void walk_helpers_body(const hmr_gpu_helper_case *cas
 						  hmr_gpu_helper_out *out, unsigned lds_bytes)
 {
 	if (!rows_enter<LAT, typename std::conditional<LAT, WaveGrp, HelpGrp>::type>(lds_bytes)) return;      // (the helper wavefront: through its loop until release_helpers)
-	extern __shared__ __align__(16) uint8_t lds[];
 	const G g{(int)(threadIdx.x & 63)};
 	WorkSlow *const my_slow = slow + blockIdx.x;
 	CtuInfo *const my_ctu = ctus + blockIdx.x;
 	uint32_t *const slow_words = (uint32_t *)my_slow;
 	for (int i = g.tid; i < (int)(sizeof(WorkSlow) / 4); i += 64) slow_words[i] = WALK_POISON;
 	g.sync();
-	// the worker's context, as encode_row builds it
-	Enc &e = *(Enc *)(lds + LDS_OFF_ENC);
+	// the worker's context, as encode_row builds it, on the workgroup's one CTU record
+	Enc &e = lds_enc();
 	HENC_ENC_IN_LDS(e);
-	e.seq = (Seq *)(lds + LDS_OFF_SEQ);
-	e.f = (FrameCtx *)(lds + LDS_OFF_FRAME);
-	e.T = tables;
-	e.ft = nullptr;
-	e.geo.p = nullptr;
-	e.ctus = my_ctu;
+	enc_prepare(e, tables, my_ctu, nullptr);
 	e.ctu = my_ctu;
-	e.w = (Work *)lds;
-	e.nodes = nullptr;
-	e.nodes_fast = (Node *)(lds + LDS_WORK);
-	e.node_quad = -1;
-	e.on_helper = 0;
 	e.ctu_g = my_ctu;
-	e.ctu_fast = nullptr;
-	e.box = (HelperBox *)(lds + LDS_OFF_BOX);
-	for (int h = 0; h < NHELP; h++) e.hseq[h] = 0;
-	e.bgseq = 0;
-	e.bg_node = -1;
-	e.prof = nullptr;
-	e.timeline = nullptr;
 	e.coeff = nullptr;
 	g.sync();
 	for (int k = (int)blockIdx.x; k < nlist; k += (int)gridDim.x) {
@@ -390,7 +370,7 @@ extern "C" int hmr_gpu_walk_helper_forms(const hmr_gpu_helper_case *cases, int n
 	}
 	HIP_TRY(hipSetDevice(c->device));
 	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(henc_geo_table), geo.data(), sizeof(Geo) * NNODES));
-	const unsigned lds_bytes = (unsigned)(LDS_BYTES - LDS_RD);
+	const unsigned lds_bytes = (unsigned)lds_request(false);
 	HIP_TRY(hipFuncSetAttribute((const void *)k_walk_helpers, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
 	HIP_TRY(hipFuncSetAttribute((const void *)k_walk_helpers_lat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
 	const int groups = ncases < HELP_MAX_GROUPS ? ncases : HELP_MAX_GROUPS;

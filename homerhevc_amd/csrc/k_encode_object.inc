@@ -299,11 +299,7 @@ int launch_pool(hmr_gpu_enc *lead, const EncDev *host, int n, int rows_total, bo
 {
 	if (!lead->n_cus) HIP_TRY(hipDeviceGetAttribute(&lead->n_cus, hipDeviceAttributeMultiprocessorCount, lead->ctx->device));
 	// a worker's LDS: without RD_FULL pictures in the launch the RD arrays at its end are left out (a fourth worker then fits a CU)
-#if defined(HENC_PROFILE)
-	const size_t lds_default = LDS_BYTES + (needs_rd ? 0 : 0);      // (the primitive timers sit behind everything else)
-#else
-	const size_t lds_default = needs_rd ? LDS_BYTES : LDS_BYTES - LDS_RD;
-#endif
+	const size_t lds_default = (size_t)lds_request(needs_rd);
 	const size_t lds_bytes = getenv("HENC_LDS_BYTES") && (size_t)atoi(getenv("HENC_LDS_BYTES")) > lds_default ? (size_t)atoi(getenv("HENC_LDS_BYTES")) : lds_default;   // (experiment: a larger request keeps a CU to fewer workers)
 	if (lds_bytes > 160 * 1024) {
 		hmr_set_error("k_encode_pool: a worker's LDS request of %zu bytes (HENC_LDS_BYTES) is more than a CU has", lds_bytes);
@@ -376,7 +372,7 @@ int run_ctu_passes(hmr_gpu_enc *e)
 			EncDev dd = e->d;
 			int pp = pass;
 			void *args[] = {&dd, &pp};
-			const hipError_t launched = hipLaunchCooperativeKernel((const void *)k_encode_ctus, dim3(s.hctu), dim3(ENC_THREADS), args, (unsigned)LDS_BYTES, st);
+			const hipError_t launched = hipLaunchCooperativeKernel((const void *)k_encode_ctus, dim3(s.hctu), dim3(ENC_THREADS), args, (unsigned)lds_request(true), st);
 			if (launched != hipSuccess) {
 				hmr_set_error("k_encode_ctus (%d row workers, cooperative): %s", s.hctu, hipGetErrorString(launched));
 				return HMR_GPU_ERR_HIP;
@@ -587,7 +583,7 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 		}
 	}
 	if (e->cfg.wfpp_num_threads <= 1) DEV_ALLOC(e->d.work_slow, s.hctu);      // (the pool has its workers' windows: lead->d_pool_slow)
-	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_ctus, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_ctus, hipFuncAttributeMaxDynamicSharedMemorySize, lds_request(true)));
 	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_pool, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_pool_lat, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	HIP_TRY(hipFuncSetAttribute((const void *)k_encode_full, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -26,7 +26,6 @@ constexpr int WALK_WINDOW_BYTES = 64 * 64 + 2 * 32 * 32, WALK_MAX_GROUPS = 96;
 
 __global__ __launch_bounds__(64) void k_walk_forms(const hmr_gpu_walk_case *cases, int ncases, const uint8_t *arena, const DevTables *tables, WorkSlow *slow, hmr_gpu_walk_out *out, unsigned lds_bytes)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
 	const WalkGrp g{{(int)threadIdx.x}};
 	WorkSlow *const my_slow = slow + blockIdx.x;
 	uint32_t *const slow_words = (uint32_t *)my_slow;
@@ -39,11 +38,11 @@ __global__ __launch_bounds__(64) void k_walk_forms(const hmr_gpu_walk_case *case
 		const int step = uni(cs.step), ni = uni(cs.node), comp = uni(cs.comp);
 		const bool on_helper = step == HMR_GPU_WALK_QUAD8_C || step == HMR_GPU_WALK_QUAD16_C || step == HMR_GPU_WALK_TU_PAIR || (step == HMR_GPU_WALK_TU && comp != COMP_Y);
 		// a worker's LDS starts from zero (rows_enter); then what the step reads
-		for (int i = g.tid; i < (int)(lds_bytes / 4); i += 64) ((uint32_t *)lds)[i] = 0;
+		lds_zero(lds_bytes, g.tid, 64);
 		g.sync();
-		Work *lw = (Work *)(lds + LDS_OFF_WORK);
-		Seq *lseq = (Seq *)(lds + LDS_OFF_SEQ);
-		FrameCtx *lframe = (FrameCtx *)(lds + LDS_OFF_FRAME);
+		Work *lw = lds_work();
+		Seq *lseq = lds_seq();
+		FrameCtx *lframe = lds_frame();
 		wave_copy_words(lw->curr_y, arena + cs.curr, WALK_WINDOW_BYTES, g.tid);
 		if (cs.pred >= 0) wave_copy_words(lw->pred_y, arena + cs.pred, WALK_WINDOW_BYTES, g.tid);
 		if (g.tid == 0) {
@@ -61,11 +60,11 @@ __global__ __launch_bounds__(64) void k_walk_forms(const hmr_gpu_walk_case *case
 			lframe->sub_c[1] = arena + cs.sub_c[1];
 		}
 		// the context of the wavefront that runs the step in the walk: the worker's, or its helper's (helper_serve, HJOB_NEW_CTU)
-		Enc &e = *(Enc *)(lds + LDS_OFF_ENC + (on_helper ? LDS_ENC_BYTES : 0));
+		Enc &e = on_helper ? lds_helper_enc(0) : lds_enc();
 		HENC_ENC_IN_LDS(e);
-		int16_t *const hscratch = (int16_t *)(lds + LDS_WORK + LDS_NODES);
+		int16_t *const hscratch = lds_helper_scratch();
+		// (the members the steps read, and no more: everything else is zero, and a step's kernel keeps the register budget it was pinned with)
 		e.T = tables;
-		e.ft = nullptr;
 		e.geo.p = nullptr;
 		e.on_helper = on_helper ? 1 : 0;
 		e.scratch_a = on_helper ? hscratch : lw->pred_aux;
@@ -234,7 +233,7 @@ extern "C" int hmr_gpu_walk_forms(const hmr_gpu_walk_case *cases, int ncases, co
 	HIP_TRY(hipSetDevice(c->device));
 	// the partition geometry, as hmr_gpu_enc_create leaves it (the same tree for every encoder)
 	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(henc_geo_table), geo.data(), sizeof(Geo) * NNODES));
-	const unsigned lds_bytes = (unsigned)(LDS_BYTES - LDS_RD);
+	const unsigned lds_bytes = (unsigned)lds_request(false);
 	HIP_TRY(hipFuncSetAttribute((const void *)k_walk_forms, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
 	const int groups = ncases < WALK_MAX_GROUPS ? ncases : WALK_MAX_GROUPS;
 	struct Bufs {

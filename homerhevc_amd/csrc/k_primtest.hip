@@ -138,7 +138,7 @@ __global__ __launch_bounds__(64) void k_primtest_multi_sad(int maxc, const uint8
 	else multi_sad_all<9>(g, src, plane, off, stride, n, out);
 }
 
-// The walk's motion search, one case per workgroup.  motion_estimation takes an Enc whose members are fixed places of a worker's LDS (enc_common.h LDS_OFF_*): the
+// The walk's motion search, one case per workgroup.  motion_estimation takes an Enc whose members are fixed places of a worker's LDS (enc_lds.h): the
 // kernel lays out what the search reads - the source block in the worker's source window, the picture size and the planes' pitch, the planes, the two lists - and
 // calls it as cu_motion_estimation does, for a block at the window's origin.
 constexpr unsigned ME_LDS_BYTES = LDS_OFF_ENC + LDS_ENC_BYTES;
@@ -146,14 +146,13 @@ static_assert(sizeof(hmr_gpu_prim_me_case) == 80 && sizeof(hmr_gpu_prim_me_out) 
 __global__ __launch_bounds__(64) void k_primtest_motion_search(const hmr_gpu_prim_me_case *cases, const uint8_t *src, const uint8_t *plane0, int size, int stride, int width, int height,
 							       hmr_gpu_prim_me_out *out)
 {
-	extern __shared__ __align__(16) uint8_t lds[];
 	const WaveGrp g{(int)threadIdx.x};
 	const hmr_gpu_prim_me_case &cs = cases[blockIdx.x];
-	for (int i = g.tid; i < (int)(ME_LDS_BYTES / 4); i += 64) ((uint32_t *)lds)[i] = 0;
+	lds_zero(ME_LDS_BYTES, g.tid, 64);
 	g.sync();
-	Work *lw = (Work *)(lds + LDS_OFF_WORK);
-	Seq *lseq = (Seq *)(lds + LDS_OFF_SEQ);
-	FrameCtx *lframe = (FrameCtx *)(lds + LDS_OFF_FRAME);
+	Work *lw = lds_work();
+	Seq *lseq = lds_seq();
+	FrameCtx *lframe = lds_frame();
 	const uint8_t *blk = src + (size_t)blockIdx.x * size * size;
 	for (int i = g.tid; i < size * size; i += 64) lw->curr_y[(i / size) * 64 + i % size] = blk[i];
 	if (g.tid == 0) {
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(64) void k_primtest_motion_search(const hmr_gpu_pri
 		for (int i = 0; i < 3; i++) { lw->search_cands.mv[i].x = cs.search[i][0]; lw->search_cands.mv[i].y = cs.search[i][1]; }
 	}
 	g.sync();
-	Enc &e = *(Enc *)(lds + LDS_OFF_ENC);
+	Enc &e = lds_enc();
 	HENC_ENC_IN_LDS(e);
 	MV mv = {cs.start[0], cs.start[1]}, subpix = {0, 0};
 	const uint32_t sad = motion_estimation(g, e, 0, 0, uni(cs.gx), uni(cs.gy), size, lw->amvp, lw->search_cands, cs.corr, uni(cs.action), &mv, &subpix);
