@@ -1,10 +1,11 @@
 // Host side of the frame encoder, part 3 (included by k_encode.hip): pictures that already lie in device memory, and pictures and quality left there
-// (include/homer_gpu.h sections 12d .. 12l).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of the job type's kernel (picture_io.hip)
+// (include/homer_gpu.h sections 12d .. 12m).  One call handles the pictures of up to PICTURE_MAX_JOBS encoders with one launch of the job type's kernel (picture_io.hip)
 // on the FIRST encoder's stream; run_jobs (picture_io.h) orders it by events and the host waits for nothing.
 //   load:   behind the producer's stream; the other encoders' streams and whatever the producer queues next go on behind it.
 //   export: behind the consumer's stream (which may still use the output memory), behind the streams that wrote the final pictures and behind the encoders' own
 //           streams (which may still load the slots); the consumer's stream and all of those streams go on behind it.
 //   ssim:   ordered as export; the final pictures and the slots are read, three sums per encoder are written.
+//   cut stats: ordered as export, without the final pictures' writers; two slots are read, eight values per encoder are written.
 //   export as RGB: ordered as export; the consumer's stream is also the one that holds the producer of the reference pictures.
 // The six load entries are ONE body (load_sources) over a description of their kind of picture; the four export / metric entries share their refusals
 // (refuse_encoder), their plane check (check_planes) and their ordering (run_export).  Every job comes from picture_io.h's builders; the host-memory entries of
@@ -387,6 +388,59 @@ extern "C" int hmr_gpu_enc_ssim_device(hmr_gpu_enc **encs, int n, const int *slo
 extern "C" int hmr_gpu_enc_ssim_one_device(hmr_gpu_enc *enc, int slot, int64_t *dev_ssim, void *consumer_stream)
 {
 	return hmr_gpu_enc_ssim_device(&enc, 1, &slot, dev_ssim, consumer_stream);
+}
+
+// ---- section 12m: scene-cut statistics between two picture slots ----
+extern "C" int hmr_gpu_enc_cut_stats(hmr_gpu_enc **encs, int n, const int *slots, const int *prev_slots, int64_t *dev_stats, void *consumer_stream)
+{
+	static const char *const fn = "hmr_gpu_enc_cut_stats";
+	if (!encs || !slots || !prev_slots || !dev_stats || n < 1 || n > PICTURE_MAX_JOBS) {
+		hmr_set_error("%s: needs 1 .. %d encoders with their slots, previous slots and dev_stats (n = %d)", fn, PICTURE_MAX_JOBS, n);
+		return HMR_GPU_ERR_ARG;
+	}
+	int rc;
+	for (int i = 0; i < n; i++) {
+		if ((rc = refuse_encoder(fn, encs, i, ENCODER | HAS_SLOT, slots[i]))) return rc;
+		if (prev_slots[i] < 0 || prev_slots[i] >= (int)encs[i]->src.size()) return picture_refuse(fn, i, "the previous slot does not exist");
+		if (slots[i] == prev_slots[i]) return picture_refuse(fn, i, "the slot and the previous slot are the same");
+		if (const char *why = hmr_cut_refusal(encs[i]->seq.width, encs[i]->seq.height)) return picture_refuse(fn, i, why);
+	}
+	const int device = encs[0]->ctx->device;
+	HIP_TRY(hipSetDevice(device));
+	if (!on_device(dev_stats, device) || !on_device(dev_stats + HMR_CUT_VALUES * (size_t)n - 1, device)) return not_device(fn, 0, "dev_stats", device);
+	hipStream_t st = encs[0]->ctx->stream, consumer = (hipStream_t)consumer_stream;
+	// the histogram bins of the call's pictures belong to the encoder that leads it (as the job tables do); made at the first call, or a larger one
+	PictureRings &rings = encs[0]->rings;
+	if (n > rings.cut_bins_cap) {
+		HIP_TRY(hipStreamSynchronize(st));      // (a launch that still counts in the old bins)
+		if (rings.cut_bins) (void)hipFree(rings.cut_bins);
+		rings.cut_bins = nullptr;
+		rings.cut_bins_cap = 0;
+		const int want = n == 1 ? 1 : PICTURE_MAX_JOBS;
+		HIP_TRY(hipMalloc((void **)&rings.cut_bins, (size_t)want * 512 * sizeof(uint32_t)));
+		rings.cut_bins_cap = want;
+	}
+	std::vector<CutJob> jobs(n);
+	for (int i = 0; i < n; i++) {
+		const Seq &s = encs[i]->seq;
+		jobs[i] = hmr_cut_job(encs[i]->src[slots[i]].p, encs[i]->src[prev_slots[i]].p, s.src_stride_y, s.src_stride_c, dev_stats + HMR_CUT_VALUES * (size_t)i, rings.cut_bins + 512 * (size_t)i,
+				      s.width, s.height);
+	}
+	// ordered as 12h's call, but the final pictures are not read: behind the consumer and what the encoders' own streams hold (a load into a slot); the values and the
+	// bins are zeroed on the launch's stream behind all of them
+	auto behind_the_loads = [&](std::vector<hipStream_t> &behind) -> int {
+		const int rc = wait_for_writers(encs, n, st, consumer, behind, false);
+		if (rc) return rc;
+		HIP_TRY(hipMemsetAsync(dev_stats, 0, HMR_CUT_VALUES * (size_t)n * sizeof(int64_t), st));
+		HIP_TRY(hipMemsetAsync(rings.cut_bins, 0, (size_t)n * 512 * sizeof(uint32_t), st));
+		return HMR_GPU_OK;
+	};
+	return run_jobs(rings, st, jobs.data(), n, consumer, std::vector<hipStream_t>(1, consumer), behind_the_loads);
+}
+
+extern "C" int hmr_gpu_enc_cut_stats_one(hmr_gpu_enc *enc, int slot, int prev_slot, int64_t *dev_stats, void *consumer_stream)
+{
+	return hmr_gpu_enc_cut_stats(&enc, 1, &slot, &prev_slot, dev_stats, consumer_stream);
 }
 
 // ---- section 12i: the final pictures or the slots' pictures out as RGB, and their distance to the caller's RGB pictures ----

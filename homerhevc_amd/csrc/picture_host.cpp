@@ -1,6 +1,6 @@
 // Picture conversion, the part that runs on the host alone (include/homer_gpu.h sections 12d .. 12l): the builders of the kernels' jobs (picture_io.h), the three
 // descriptor checks, the host twins of the kernels - the loops a caller would write from the arithmetic headers (rgb_yuv.h, yuv_depth.h, scale_area.h, yuv_rgb.h,
-// ssim_window.h), compiled from the very functions the kernels of picture_io.hip compile - and the metric arithmetic on the kernels' sums.  Nothing here touches a device.
+// ssim_window.h, cut_stats.h), compiled from the very functions the kernels of picture_io.hip compile - and the metric arithmetic on the kernels' sums.  Nothing here touches a device.
 #include <math.h>
 #include <string.h>
 #include "picture_io.h"
@@ -89,6 +89,19 @@ SsimJob hmr_ssim_job(int16_t *const a[3], int stride_a_y, int stride_a_c, int16_
 	j.sum = sum;
 	j.stride_a_y = stride_a_y; j.stride_a_c = stride_a_c;
 	j.stride_b_y = stride_b_y; j.stride_b_c = stride_b_c;
+	j.width = width; j.height = height;
+	return j;
+}
+
+CutJob hmr_cut_job(int16_t *const cur[3], int16_t *const prev[3], int stride_y, int stride_c, int64_t *stats, uint32_t *bins, int width, int height)
+{
+	CutJob j;
+	for (int c = 0; c < 3; c++) {
+		j.cur[c] = cur[c];
+		j.prev[c] = prev[c];
+	}
+	j.stats = stats; j.bins = bins;
+	j.stride_y = stride_y; j.stride_c = stride_c;
 	j.width = width; j.height = height;
 	return j;
 }
@@ -551,5 +564,62 @@ extern "C" int hmr_gpu_ssim_host(const hmr_gpu_picture *a, const hmr_gpu_picture
 		const View va = view(*a, c), vb = view(*b, c);
 		sums[c] = hmr_ssim_plane_host(va.p, va.pitch, va.step, vb.p, vb.pitch, vb.step, c ? width / 2 : width, c ? height / 2 : height);
 	}
+	return HMR_GPU_OK;
+}
+
+// ---- section 12m: the host side of the scene-cut statistics ----
+// cut_stats.h's arithmetic over host memory: the loops a caller would write from the header's definition
+extern "C" int hmr_gpu_cut_stats_host(const hmr_gpu_picture *cur, const hmr_gpu_picture *prev, int width, int height, int64_t stats[8])
+{
+	int rc;
+	if ((rc = hmr_gpu_picture_check(cur, width, height)) || (rc = hmr_gpu_picture_check(prev, width, height))) return rc;
+	if (const char *why = hmr_cut_refusal(width, height)) {
+		hmr_set_error("hmr_gpu_cut_stats_host: %d x %d: %s", width, height, why);
+		return HMR_GPU_ERR_ARG;
+	}
+	if (!stats) {
+		hmr_set_error("hmr_gpu_cut_stats_host: needs the eight values");
+		return HMR_GPU_ERR_ARG;
+	}
+	struct View { const uint8_t *p; int64_t pitch; int step; };
+	auto view = [](const hmr_gpu_picture &pic, int c) {
+		if (c == 0 || pic.format == HMR_GPU_PIC_I420) return View{pic.plane[c], pic.pitch[c], 1};
+		return View{pic.plane[1] + (c - 1), pic.pitch[1], 2};
+	};
+	for (int c = 0; c < 3; c++) {
+		const View a = view(*cur, c), b = view(*prev, c);
+		stats[HMR_CUT_SAD_Y + c] = hmr_cut_sad_plane_host(a.p, a.pitch, a.step, b.p, b.pitch, b.step, c ? width / 2 : width, c ? height / 2 : height);
+	}
+	hmr_cut_luma_host(cur->plane[0], cur->pitch[0], prev->plane[0], prev->pitch[0], width, height, stats);
+	return HMR_GPU_OK;
+}
+
+// the four scores from the eight values: correctly rounded double quotients of exact integers, pure host
+extern "C" int hmr_gpu_cut_score(const int64_t stats[8], int width, int height, double score[4])
+{
+	if (!stats || !score) {
+		hmr_set_error("hmr_gpu_cut_score: needs eight values and four results");
+		return HMR_GPU_ERR_ARG;
+	}
+	if (const char *why = hmr_cut_refusal(width, height)) {
+		hmr_set_error("hmr_gpu_cut_score: %d x %d: %s", width, height, why);
+		return HMR_GPU_ERR_ARG;
+	}
+	const int64_t samples = (int64_t)width * height, blocks = samples / 64;
+	const int64_t most[HMR_CUT_VALUES] = {255 * samples, 255 * (samples / 4), 255 * (samples / 4), 2 * samples, HMR_CUT_MAX_ACT * blocks, HMR_CUT_MAX_ACT * blocks, blocks, 255 * samples};
+	for (int k = 0; k < HMR_CUT_VALUES; k++)
+		if (stats[k] < 0 || stats[k] > most[k]) {
+			hmr_set_error("hmr_gpu_cut_score: stats[%d] = %lld is outside 0 .. %lld of a %d x %d picture", k, (long long)stats[k], (long long)most[k], width, height);
+			return HMR_GPU_ERR_ARG;
+		}
+	if (stats[HMR_CUT_INTER] > stats[HMR_CUT_INTRA]) {
+		hmr_set_error("hmr_gpu_cut_score: INTER = %lld is above INTRA = %lld", (long long)stats[HMR_CUT_INTER], (long long)stats[HMR_CUT_INTRA]);
+		return HMR_GPU_ERR_ARG;
+	}
+	// (every operand is exact in a double: below 2^53 - 255 x 8192 x 8192 = 1.7e10 - so each quotient is rounded ONCE)
+	score[0] = (double)stats[HMR_CUT_SAD_Y] / (double)samples;
+	score[1] = (double)stats[HMR_CUT_HIST] / (double)(2 * samples);
+	score[2] = (double)stats[HMR_CUT_NINTRA] / (double)blocks;
+	score[3] = stats[HMR_CUT_INTRA] ? (double)stats[HMR_CUT_INTER] / (double)stats[HMR_CUT_INTRA] : 1.0;
 	return HMR_GPU_OK;
 }

@@ -2,10 +2,10 @@
 // Ingest: 8-bit pictures -> int16 planes (a picture slot, a reference picture); RGB pictures (8-bit packed or planar, binary16, binary32) -> the same planes, colour
 // converted in the same pass (rgb_yuv.h); Y'CbCr pictures of 8 .. 16 bits in 4:2:0, 4:2:2 or 4:4:4, planar, semi-planar or packed -> the same planes, rounded to 8-bit 4:2:0 in the same pass (yuv_depth.h); 8-bit pictures of another, larger size -> the same planes, area-averaged in the same pass (scale_area.h); RGB pictures of a larger size -> the same planes, converted and area-averaged in the same pass; Y'CbCr pictures of 8 .. 16 bits of a larger size -> the same planes, rounded and area-averaged in the same pass.  Egress: the final pictures (int16, padded) -> 8-bit pictures, and the exact sums of
 // squared differences against the int16 source planes of a picture slot; the final pictures or the slots' pictures -> RGB pictures in any of the ingest's forms, colour
-// converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  SSIM: the exact window sums between a final picture and a slot (ssim_window.h).
-// What the file holds, in its order: the nine job structs (one picture of a launch each; the kernels read a table of them); hmr_picture_launch, which finds kernel and
+// converted in the same pass (yuv_rgb.h), and the exact sums of squared differences against the caller's RGB pictures.  SSIM: the exact window sums between a final picture and a slot (ssim_window.h).  Scene-cut statistics: exact sums between two slots of an encoder (cut_stats.h).
+// What the file holds, in its order: the ten job structs (one picture of a launch each; the kernels read a table of them); hmr_picture_launch, which finds kernel and
 // grid size by the job type; one builder per job type (descriptors, planes, strides and sizes in, a job out - no encoder); JobRing, the tables of one job type that one
-// encoder has in flight, and PictureRings, its nine rings; run_jobs, which queues one launch ordered against the caller's stream by events (k_encode_picture_io.inc and
+// encoder has in flight, and PictureRings, its ten rings; run_jobs, which queues one launch ordered against the caller's stream by events (k_encode_picture_io.inc and
 // the host-memory entries of k_encode_object.inc use it).  The host-only part of the module - builders, descriptor checks, host twins, metrics - is picture_host.cpp.
 #pragma once
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "yuv_rgb.h"
 #include "scale_area.h"
 #include "ssim_window.h"
+#include "cut_stats.h"
 
 #define PICTURE_MAX_JOBS 512         // pictures per launch (the batch calls' limit)
 #define PICTURE_RING 4               // job tables of one direction in flight
@@ -141,9 +142,21 @@ struct SsimJob {
 };
 static_assert(sizeof(SsimJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
 
+// one picture of a scene-cut launch (k_cut, then k_cut_finish): cut_stats.h's eight values between the int16 planes cur and prev, two slots of one encoder
+struct CutJob {
+	const int16_t *cur[3];       // the slot just loaded: planes at sample (0, 0); 16-byte aligned, read-only
+	const int16_t *prev[3];      // the slot of the frame before
+	int64_t *stats;              // HMR_CUT_VALUES values (zeroed in front of the launch)
+	uint32_t *bins;              // 2 x 256 counts, the luma histograms of cur and of prev (library-owned: PictureRings::cut_bins; zeroed in front of the launch)
+	int32_t stride_y, stride_c;  // elements, multiples of 8 (both slots have the same)
+	int32_t width, height;       // multiples of 8
+};
+static_assert(sizeof(CutJob) % 8 == 0, "a table of jobs keeps its pointers aligned");
+static_assert(HMR_CUT_VALUES == HMR_GPU_CUT_VALUES && HMR_CUT_RANGE == HMR_GPU_CUT_RANGE, "cut_stats.h and the public header agree");
+
 // The job table goes from page-locked host memory (`h_jobs`, which must stay untouched until the work queued here has run) to `d_jobs`, then ONE launch of the job
-// type's kernel - k_ingest / k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_yuv_ladder / k_egress / k_egress_rgb / k_ssim - handles all n pictures; both on `stream`,
-// nothing is waited for.  Instantiated in picture_io.hip for the nine job types (PictureKernel there names each type's kernel and grid size).
+// type's kernel - k_ingest / k_ingest_rgb / k_ingest_yuv / k_downscale / k_rgb_ladder / k_yuv_ladder / k_egress / k_egress_rgb / k_ssim / k_cut (with k_cut_finish behind it) - handles all n pictures; both on `stream`,
+// nothing is waited for.  Instantiated in picture_io.hip for the ten job types (PictureKernel there names each type's kernel and grid size).
 template <class Job>
 int hmr_picture_launch(hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n);
 
@@ -188,6 +201,8 @@ EgressJob hmr_egress_job(int16_t *const rec[3], int stride_y, int stride_c, cons
 RgbEgressJob hmr_rgb_egress_job(int16_t *const yuv[3], int stride_y, int stride_c, const hmr_gpu_rgb_picture *out, const hmr_gpu_rgb_picture *ref, uint64_t *ssd, int width, int height);
 // k_ssim: the window sums between the planes a (a picture slot) and b (a final picture) into sum
 SsimJob hmr_ssim_job(int16_t *const a[3], int stride_a_y, int stride_a_c, int16_t *const b[3], int stride_b_y, int stride_b_c, int64_t *sum, int width, int height);
+// k_cut: cut_stats.h's values of the planes cur against prev (two slots of one encoder: one pair of strides) into stats, the luma histograms through bins
+CutJob hmr_cut_job(int16_t *const cur[3], int16_t *const prev[3], int stride_y, int stride_c, int64_t *stats, uint32_t *bins, int width, int height);
 
 // The job tables of the calls one encoder leads, in one direction: a ring of tables in page-locked memory (a table is written again only when the launch that read it
 // is known to be over: ev_turn), their copy on the device, the events towards the outside stream (producer or consumer) and towards the streams that go on behind a launch.
@@ -238,10 +253,13 @@ struct JobRing {
 
 // The rings of one encoder, one per job type (a table is reused after PICTURE_RING calls of ITS kind): a new kernel adds its job type here and nowhere else.
 struct PictureRings {
-	std::tuple<JobRing<IngestJob>, JobRing<RgbIngestJob>, JobRing<YuvIngestJob>, JobRing<ScaleJob>, JobRing<RgbScaleJob>, JobRing<YuvScaleJob>, JobRing<EgressJob>, JobRing<RgbEgressJob>, JobRing<SsimJob>> of;
+	std::tuple<JobRing<IngestJob>, JobRing<RgbIngestJob>, JobRing<YuvIngestJob>, JobRing<ScaleJob>, JobRing<RgbScaleJob>, JobRing<YuvScaleJob>, JobRing<EgressJob>, JobRing<RgbEgressJob>, JobRing<SsimJob>, JobRing<CutJob>> of;
+	uint32_t *cut_bins = nullptr;      // k_cut's histogram bins, 2 x 256 words per picture of a call this encoder leads (hmr_gpu_enc_cut_stats)
+	int cut_bins_cap = 0;              // pictures
 	void release()
 	{
 		std::apply([](auto &...ring) { (ring.release(), ...); }, of);
+		if (cut_bins) (void)hipFree(cut_bins);
 	}
 };
 

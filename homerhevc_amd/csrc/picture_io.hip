@@ -1,6 +1,6 @@
-// Picture conversion on the device (include/homer_gpu.h sections 12d .. 12l): pictures in device memory - any base address, any pitch - to and from the int16 planes of
-// the frame encoder (sample (x, y) at y * stride + x), and quality sums between such planes.  ONE launch for a batch of pictures; k_ingest and k_egress have no
-// arithmetic to speak of and are bound by HBM.  The file holds the ten kernels, behind each the PictureKernel<Job> that names it and its grid size for
+// Picture conversion on the device (include/homer_gpu.h sections 12d .. 12m): pictures in device memory - any base address, any pitch - to and from the int16 planes of
+// the frame encoder (sample (x, y) at y * stride + x), and quality and scene-cut sums between such planes.  ONE launch for a batch of pictures; k_ingest and k_egress have no
+// arithmetic to speak of and are bound by HBM.  The file holds the twelve kernels, behind each the PictureKernel<Job> that names it and its grid size for
 // hmr_picture_launch, the launch itself and the three scale job builders (they need scale_tile); everything else on the host is picture_host.cpp.
 //
 // k_ingest: 8-bit pictures into int16 planes - the source planes of a picture slot, or a reference picture: sample (x, y) at y * stride + x, nothing outside
@@ -1478,6 +1478,226 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ssim(const SsimJob *jobs)
 }
 template <> struct PictureKernel<SsimJob> { static constexpr auto kernel = k_ssim; static int chunks(const SsimJob &j) { return ssim_tiles(j.width, j.height); } };
 
+// ---- scene-cut statistics (section 12m) ----
+// k_cut: cut_stats.h's values of a picture slot (cur) against the slot of the frame before (prev).  Both pictures are read as int16 planes, nothing is written but eight
+// 64-bit values and 2 x 256 histogram bins a picture.  blockIdx.y = picture; blockIdx.x = first the luma tiles of CUT_TW x CUT_TH = 16 x 8 blocks of 8 x 8 samples
+// (128 x 64 samples), row by row, then chunks of CHUNK_ROWS chroma rows (U and V); smaller pictures leave their last blocks empty.
+// A luma tile.  Stage 1, a lane per 16-byte span of 8 samples (tiles start at multiples of 128 samples: every span is 16-byte aligned): prev's search window - the
+// tile and a rim of 8 samples, 144 x 80 samples, 18 x 80 spans, and a row of zeros behind them - and cur's tile, 16 x 64 spans, go to LDS as BYTES (the slots hold 0 .. 255: v_perm_b32 packs the low
+// bytes of four dwords into two).  A span outside W x H is not loaded - its bytes are 0 and no valid vector reads them.  A window row is 38 words: 36 of the window
+// and two of padding that the last vector group reads and discards.  12 312 + 8 192 bytes.  2.20 times the tile's 2 x 2 x 8192 bytes of cur and prev leave the
+// caches (the rim: 144 x 80 / (128 x 64) = 1.41 of prev), the re-read part from tiles that neighbouring workgroups read at about the same time.
+// Stage 2, a lane per word of cur's tile (8 words a lane): SAD_Y and LUMA by v_sad_u8 against prev's word and against 0, and the two histograms by eight ds_add_u32
+// on 2 x 256 counts in LDS; behind a barrier each lane adds two counts to the picture's bins with vector atomics (global_atomic_add; a zero count is skipped).
+// Stage 3, a wavefront per block, the tile's blocks dealt round robin: act(b) with a sample per lane (two wave sums); then the 289 vectors as 9 x 5 = 45 TASKS, one
+// per lane - two adjacent vertical offsets, dy = 2 m - 8 and 2 m - 7, and a group of four adjacent horizontal ones, dx = 4 g - 8 .. 4 g - 5.  A task reads nine
+// rows of three aligned words of the window (12 bytes: the group starts at a multiple of 4 bytes; rows 1 .. 7 serve both offsets) and runs v_qsad_pk_u16_u8 - the
+// unmasked sliding form: four SADs of four bytes at byte offsets 0 .. 3, accumulated in 16 bits each (a block's SAD is at most 16 320) - 2 x 16 times, against cur's
+// two words of each row, which every lane holds in registers (16 words, one LDS broadcast read per block).  Per block and wavefront: 32 v_qsad_pk_u16_u8, 27 LDS
+// words a lane, and 360 candidate slots for 289 vectors (the fifth group has one vector, dx = 8; the ninth pair one offset, dy = 8, its other reads the window's
+// padding row); per picture W H / 64 x 32 quad-SAD wave instructions for 289 x W H candidate-sample differences.  Vectors that leave the picture or the range
+// (hmr_cut_valid) are dropped when the lane takes its minimum; the wavefront's minimum comes by six ds_bpermute steps.  INTRA, INTER and NINTRA stay in registers,
+// uniform over the wavefront; no private memory, no loop-carried state in memory.  (One offset a task, 85 tasks in two rounds, issues the same 32 quad SADs but
+// reads 48 LDS words a lane: measured 4.82 ms against this mapping's 4.39 ms over 256 x 1080p.)
+// Sums: the workgroup's four wavefronts through LDS, then ONE 64-bit vector atomic per value (global_atomic_add_x2) - five for a luma tile, two for a chroma chunk.
+// A chroma chunk: a lane per span of 8 samples of U or V of both pictures, packed as above, two v_sad_u8; a row's last four samples, where the width is no multiple of 16, come
+// by an 8-byte load.  No load touches a sample outside W x H of any plane.
+// HIST needs the finished bins of the whole picture: k_cut_finish, a second small kernel in the same call (a workgroup per picture, a lane per histogram value),
+// forms it.  Chosen over the last workgroup of the picture doing it: that needs a device-wide count of finished workgroups and release / acquire fences around it in
+// every workgroup, to save a launch of a few microseconds behind a kernel of milliseconds.
+// Why 16 x 8 blocks: 22.6 KB of LDS lets seven workgroups share a CU, the rim costs 1.41 reads of prev (8 x 4 blocks: 1.88; 16 x 16: 1.27 at 40 KB), and 128 blocks
+// are 32 per wavefront, so the staging is a small part of a workgroup's time.  What binds: the issue of the quad SADs, not the bytes - 256 x 1080p take 4.39 ms
+// (tools/cut_bench.py), in which the 2.2 x 6 W H bytes pass at 1.6 TB/s, a quarter of what HBM gives, while 32 quad SADs per block are 259 000 per SIMD, 40 cycles
+// each at 2.4 GHz; nearly halving the LDS words of the search (48 to 27 a lane and block) gained 9 %.
+constexpr int CUT_TW = 16, CUT_TH = 8, CUT_ROWS = 8 * CUT_TH, CUT_CUR_WORDS = 2 * CUT_TW, CUT_WIN_SPANS = CUT_TW + 3, CUT_WIN_WORDS = 2 * CUT_WIN_SPANS;
+constexpr int CUT_WIN_ROWS = CUT_ROWS + 2 * HMR_CUT_RANGE + 1, CUT_GROUPS = (2 * HMR_CUT_RANGE + 1 + 3) / 4, CUT_TASKS = (2 * HMR_CUT_RANGE + 1 + 1) / 2 * CUT_GROUPS;
+static_assert(HMR_CUT_RANGE == 8 && HMR_CUT_BLOCK == 8 && HMR_WAVE == 64, "a sample per lane, window rims of one span, groups that start at multiples of 4 bytes");
+static_assert(2 * (CUT_TW - 1) + (CUT_GROUPS - 1) + 2 < CUT_WIN_WORDS && CUT_TASKS <= HMR_WAVE, "the last group's three words lie inside a window row; a task per lane");
+static_assert((CUT_WIN_ROWS * CUT_WIN_WORDS + CUT_ROWS * CUT_CUR_WORDS + 2 * 256 + 5 * HMR_WAVES_PER_BLOCK) * 4 <= 40 * 1024, "four workgroups a CU at least");
+static_assert((uint64_t)CUT_TW * CUT_TH * HMR_CUT_MAX_ACT < (1ull << 32) && (uint64_t)CHUNK_ROWS * EGRESS_MAX_WIDTH * 255 < (1ull << 32), "a workgroup's partial sums fit 32 bits");
+
+__host__ __device__ __forceinline__ int cut_tiles_x(int W) { return ((W >> 3) + CUT_TW - 1) / CUT_TW; }
+__host__ __device__ __forceinline__ int cut_tiles_y(int H) { return ((H >> 3) + CUT_TH - 1) / CUT_TH; }
+__host__ __device__ __forceinline__ int cut_chroma_chunks(int H) { return ((H >> 1) + CHUNK_ROWS - 1) / CHUNK_ROWS; }
+__host__ __device__ __forceinline__ int cut_chunks(int W, int H) { return cut_tiles_x(W) * cut_tiles_y(H) + cut_chroma_chunks(H); }
+
+// the 8 samples at p (16-byte aligned) as bytes
+__device__ __forceinline__ u32x2 cut_load(samples_in p)
+{
+	const u32x4 v = *(const GLOBAL_AS u32x4 *)p;
+	return u32x2{__builtin_amdgcn_perm(v.y, v.x, 0x06040200u), __builtin_amdgcn_perm(v.w, v.z, 0x06040200u)};
+}
+// the 4 samples at p (8-byte aligned) as bytes: a chroma row's last half span
+__device__ __forceinline__ u32x2 cut_load_half(samples_in p)
+{
+	const u32x2 v = *(const GLOBAL_AS u32x2 *)p;
+	return u32x2{__builtin_amdgcn_perm(v.y, v.x, 0x06040200u), 0u};
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v)
+{
+#pragma unroll
+	for (int m = HMR_WAVE / 2; m >= 1; m >>= 1) {
+		const uint32_t o = (uint32_t)__shfl_xor((int)v, m, HMR_WAVE);
+		v = o < v ? o : v;
+	}
+	return v;
+}
+// the workgroup's sums of `count` values (each lane of a wavefront holds its wavefront's) added to stats[index[k]]: one 64-bit atomic per value
+template <int COUNT>
+__device__ __forceinline__ void cut_add(uint32_t (*part)[5], const uint32_t (&v)[COUNT], const int (&index)[COUNT], int64_t *stats)
+{
+	if (lane_id() == 0)
+#pragma unroll
+		for (int k = 0; k < COUNT; k++) part[wave_in_block()][k] = v[k];
+	__syncthreads();
+	const int t = (int)threadIdx.x;
+	if (t < COUNT) {
+		uint64_t total = 0;
+		for (int i = 0; i < HMR_WAVES_PER_BLOCK; i++) total += part[i][t];
+		int at = index[0];
+#pragma unroll
+		for (int k = 1; k < COUNT; k++) at = t == k ? index[k] : at;
+		if (total) __hip_atomic_fetch_add((GLOBAL_AS uint64_t *)stats + at, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_cut(const CutJob *jobs)
+{
+	__shared__ u32x2 win2[CUT_WIN_ROWS * CUT_WIN_SPANS];
+	__shared__ u32x2 cur2[CUT_ROWS * CUT_TW];
+	__shared__ uint32_t hist[2 * 256];
+	__shared__ uint32_t part[HMR_WAVES_PER_BLOCK][5];
+	const CutJob &j = jobs[blockIdx.y];
+	const int W = j.width, H = j.height, t = (int)threadIdx.x;
+	const int across = cut_tiles_x(W), luma_tiles = across * cut_tiles_y(H);
+	if ((int)blockIdx.x >= luma_tiles) {
+		// a chunk of chroma rows: SAD_U, SAD_V
+		const int y0 = ((int)blockIdx.x - luma_tiles) * CHUNK_ROWS, ch = H >> 1, cw = W >> 1;
+		if (y0 >= ch) return;
+		const int rows = ch - y0 < CHUNK_ROWS ? ch - y0 : CHUNK_ROWS, spans = (cw + 7) >> 3, stride = j.stride_c;
+		uint32_t sad[2] = {0, 0};
+		for (int i = t; i < 2 * rows * spans; i += HMR_BLOCK) {
+			const int plane = i / (rows * spans), k = i - plane * rows * spans, r = k / spans, x = (k - r * spans) << 3;
+			const size_t at = (size_t)(y0 + r) * stride + x;
+			const bool half = x + 8 > cw;      // (a row's last four samples)
+			const u32x2 a = half ? cut_load_half((samples_in)j.cur[1 + plane] + at) : cut_load((samples_in)j.cur[1 + plane] + at);
+			const u32x2 b = half ? cut_load_half((samples_in)j.prev[1 + plane] + at) : cut_load((samples_in)j.prev[1 + plane] + at);
+			const uint32_t d = __builtin_amdgcn_sad_u8(a.x, b.x, __builtin_amdgcn_sad_u8(a.y, b.y, 0u));
+			sad[0] += plane ? 0u : d;
+			sad[1] += plane ? d : 0u;
+		}
+		const uint32_t sums[2] = {wave_sum(sad[0]), wave_sum(sad[1])};
+		const int index[2] = {HMR_CUT_SAD_U, HMR_CUT_SAD_V};
+		cut_add(part, sums, index, j.stats);
+		return;
+	}
+	uint32_t *win = (uint32_t *)win2, *cur = (uint32_t *)cur2;
+	const int ty = (int)blockIdx.x / across, tx = (int)blockIdx.x - ty * across, x0 = tx * (8 * CUT_TW), y0 = ty * CUT_ROWS, stride = j.stride_y;
+	const int nbx = (W - x0) >> 3 < CUT_TW ? (W - x0) >> 3 : CUT_TW, nby = (H - y0) >> 3 < CUT_TH ? (H - y0) >> 3 : CUT_TH;      // the tile's blocks
+
+	// stage 1: prev's window and cur's tile as bytes
+	hist[t] = 0; hist[t + 256] = 0;
+	for (int i = t; i < CUT_WIN_ROWS * CUT_WIN_SPANS; i += HMR_BLOCK) {
+		const int r = i / CUT_WIN_SPANS, p = i - r * CUT_WIN_SPANS, x = x0 - HMR_CUT_RANGE + 8 * p, y = y0 - HMR_CUT_RANGE + r;
+		u32x2 v = {0u, 0u};
+		if (p < CUT_TW + 2 && r < CUT_WIN_ROWS - 1 && x >= 0 && x < W && y >= 0 && y < H) v = cut_load((samples_in)j.prev[0] + (size_t)y * stride + x);
+		win2[i] = v;
+	}
+	for (int i = t; i < CUT_ROWS * CUT_TW; i += HMR_BLOCK) {
+		const int r = i / CUT_TW, p = i - r * CUT_TW, x = x0 + 8 * p, y = y0 + r;
+		u32x2 v = {0u, 0u};
+		if (x < W && y < H) v = cut_load((samples_in)j.cur[0] + (size_t)y * stride + x);
+		cur2[i] = v;
+	}
+	__syncthreads();
+
+	// stage 2: SAD_Y, LUMA and the histograms of the tile's samples, a word per lane and pass
+	uint32_t sad = 0, luma = 0;
+	for (int i = t; i < CUT_ROWS * CUT_CUR_WORDS; i += HMR_BLOCK) {
+		const int r = i / CUT_CUR_WORDS, q = i - r * CUT_CUR_WORDS;
+		if (q >= 2 * nbx || r >= 8 * nby) continue;
+		const uint32_t c = cur[i], p = win[(r + HMR_CUT_RANGE) * CUT_WIN_WORDS + 2 + q];
+		sad = __builtin_amdgcn_sad_u8(c, p, sad);
+		luma = __builtin_amdgcn_sad_u8(c, 0u, luma);
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			__hip_atomic_fetch_add(&hist[(c >> (8 * k)) & 255u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			__hip_atomic_fetch_add(&hist[256 + ((p >> (8 * k)) & 255u)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		}
+	}
+	__syncthreads();
+#pragma unroll
+	for (int k = 0; k < 2; k++)
+		if (const uint32_t n = hist[t + 256 * k]) __hip_atomic_fetch_add((GLOBAL_AS uint32_t *)j.bins + t + 256 * k, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+
+	// stage 3: a block per wavefront
+	const int l = lane_id();
+	const uint8_t *cur8 = (const uint8_t *)cur;
+	uint32_t intra = 0, inter = 0, nintra = 0;
+	for (int k = wave_in_block(); k < nbx * nby; k += HMR_WAVES_PER_BLOCK) {
+		const int by = k / nbx, bx = k - by * nbx;
+		const uint32_t x = cur8[(8 * by + (l >> 3)) * (4 * CUT_CUR_WORDS) + 8 * bx + (l & 7)];
+		const uint32_t S = wave_sum(x), act = wave_sum(hmr_cut_deviation(x, S));
+		uint32_t c[16];
+#pragma unroll
+		for (int r = 0; r < 8; r++) {
+			const u32x2 v = cur2[(8 * by + r) * CUT_TW + bx];
+			c[2 * r] = v.x; c[2 * r + 1] = v.y;
+		}
+		uint32_t best = ~0u;
+		if (l < CUT_TASKS) {
+			const int m = l / CUT_GROUPS, g = l - m * CUT_GROUPS;      // dy = 2 m - 8 and 2 m - 7, dx = 4 g - 8 + i
+			const uint32_t *p = win + (8 * by + 2 * m) * CUT_WIN_WORDS + 2 * bx + g;
+			uint32_t w[9][3];
+#pragma unroll
+			for (int r = 0; r < 9; r++) {
+				w[r][0] = p[r * CUT_WIN_WORDS]; w[r][1] = p[r * CUT_WIN_WORDS + 1]; w[r][2] = p[r * CUT_WIN_WORDS + 2];
+			}
+			uint64_t acc[2] = {0, 0};
+#pragma unroll
+			for (int r = 0; r < 8; r++)
+#pragma unroll
+				for (int k = 0; k < 2; k++) {
+					acc[k] = __builtin_amdgcn_qsad_pk_u16_u8((uint64_t)w[r + k][1] << 32 | w[r + k][0], c[2 * r], acc[k]);
+					acc[k] = __builtin_amdgcn_qsad_pk_u16_u8((uint64_t)w[r + k][2] << 32 | w[r + k][1], c[2 * r + 1], acc[k]);
+				}
+#pragma unroll
+			for (int k = 0; k < 2; k++)
+#pragma unroll
+				for (int i = 0; i < 4; i++) {
+					const uint32_t s = (uint32_t)(acc[k] >> (16 * i)) & 0xffffu;
+					if (hmr_cut_valid(x0 + 8 * bx, y0 + 8 * by, 4 * g - HMR_CUT_RANGE + i, 2 * m + k - HMR_CUT_RANGE, W, H)) best = s < best ? s : best;
+				}
+		}
+		const CutBlock b = hmr_cut_block(act, wave_min(best));
+		intra += b.intra; inter += b.inter; nintra += b.nintra;
+	}
+	const uint32_t sums[5] = {wave_sum(sad), intra, inter, nintra, wave_sum(luma)};
+	const int index[5] = {HMR_CUT_SAD_Y, HMR_CUT_INTRA, HMR_CUT_INTER, HMR_CUT_NINTRA, HMR_CUT_LUMA};
+	cut_add(part, sums, index, j.stats);
+}
+template <> struct PictureKernel<CutJob> { static constexpr auto kernel = k_cut; static int chunks(const CutJob &j) { return cut_chunks(j.width, j.height); } };
+
+// HIST of picture blockIdx.x from its finished bins, a histogram value per lane: the only writer of that value
+__global__ __launch_bounds__(HMR_BLOCK) void k_cut_finish(const CutJob *jobs)
+{
+	__shared__ uint32_t part[HMR_WAVES_PER_BLOCK];
+	const CutJob &j = jobs[blockIdx.x];
+	const int t = (int)threadIdx.x;
+	const uint32_t hc = ((GLOBAL_AS const uint32_t *)j.bins)[t], hp = ((GLOBAL_AS const uint32_t *)j.bins)[256 + t];
+	const uint32_t w = wave_sum(hc < hp ? hp - hc : hc - hp);      // (at most 2 W H < 2^32)
+	if (lane_id() == 0) part[wave_in_block()] = w;
+	__syncthreads();
+	if (t == 0) {
+		int64_t total = 0;
+		for (int i = 0; i < HMR_WAVES_PER_BLOCK; i++) total += part[i];
+		((GLOBAL_AS int64_t *)j.stats)[HMR_CUT_HIST] = total;
+	}
+}
+// what a job type launches behind its kernel: nothing, but for k_cut
+template <class Job> void picture_finish(hipStream_t, const Job *, int) {}
+void picture_finish(hipStream_t stream, const CutJob *d_jobs, int n) { hipLaunchKernelGGL(k_cut_finish, dim3(n), dim3(HMR_BLOCK), 0, stream, d_jobs); }
+
 // ---- launches ----
 // a job table from page-locked host memory to the device by a kernel, `words` 32-bit words per job: a host-to-device copy would queue on the copy engines behind a
 // batch's multi-megabyte download (k_encode_batch.inc, k_batch_stage)
@@ -1496,12 +1716,13 @@ int hmr_picture_launch(hipStream_t stream, const Job *h_jobs, Job *d_jobs, int n
 	for (int i = 0; i < n; i++) chunks = std::max(chunks, PictureKernel<Job>::chunks(h_jobs[i]));
 	hipLaunchKernelGGL(k_picture_jobs, dim3(n), dim3(64), 0, stream, (const uint32_t *)h_jobs, (uint32_t *)d_jobs, (int)(sizeof(Job) / 4));
 	hipLaunchKernelGGL(PictureKernel<Job>::kernel, dim3(chunks, n), dim3(HMR_BLOCK), 0, stream, (const Job *)d_jobs);
+	picture_finish(stream, (const Job *)d_jobs, n);
 	HIP_TRY(hipGetLastError());
 	return HMR_GPU_OK;
 }
 #define HMR_PICTURE_LAUNCH(Job) template int hmr_picture_launch<Job>(hipStream_t, const Job *, Job *, int);
 HMR_PICTURE_LAUNCH(IngestJob) HMR_PICTURE_LAUNCH(RgbIngestJob) HMR_PICTURE_LAUNCH(YuvIngestJob) HMR_PICTURE_LAUNCH(ScaleJob)
-HMR_PICTURE_LAUNCH(RgbScaleJob) HMR_PICTURE_LAUNCH(YuvScaleJob) HMR_PICTURE_LAUNCH(EgressJob) HMR_PICTURE_LAUNCH(RgbEgressJob) HMR_PICTURE_LAUNCH(SsimJob)
+HMR_PICTURE_LAUNCH(RgbScaleJob) HMR_PICTURE_LAUNCH(YuvScaleJob) HMR_PICTURE_LAUNCH(EgressJob) HMR_PICTURE_LAUNCH(RgbEgressJob) HMR_PICTURE_LAUNCH(SsimJob) HMR_PICTURE_LAUNCH(CutJob)
 
 // The output rows of a job's tiles: the widest tile row of the picture, in spans (it does not depend on the tile's rows; at most SCALE_MAX_SPANS at the ratios
 // hmr_gpu_scale_check lets through), and the rows the LDS then holds.  The job's sizes and ratios are set.

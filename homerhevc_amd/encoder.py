@@ -23,9 +23,15 @@
     out, ssd = enc.export_rgb(dtype=torch.float16, reference=RGBFrame(rgb))     # the reconstructed picture as RGB [3, H, W], the sums of squared differences to `rgb` as int64 [3]
     r, g, b, all3 = psnr_rgb(ssd.tolist(), 1920, 1080)                          # PSNR against the RGB frame that was supplied
 
-ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h, 12i, 12j, 12k and 12l).  The pictures go from the tensors into the encoder's picture slots by one launch of
-the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; YUVFrame - more than 8 bits, 4:2:2, 4:4:4, packed -: k_ingest_yuv, which rounds to 8-bit 4:2:0 in the same pass; scaled frames: k_downscale, which area-averages in the same pass; scaled RGB frames: k_rgb_ladder, which does both; scaled YUVFrames: k_yuv_ladder, which rounds and averages) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
-ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host.
+    policy = SceneCut(share=0.5, min_gap=20, groups=[[0, 1, 2]])                # one ladder: its rungs get their intra pictures on the same frame
+    ladder.step(frames, scene_cut=policy)                                       # one launch of k_cut over this step's and the last step's pictures decides; ladder.last_cuts
+    stats = enc.cut_stats()                                                     # the eight exact statistics of the last frame against the one before, int64 [8]
+    sad, hist, share, ratio = cut_score(stats.tolist(), 1920, 1080)             # share: the part of the 8 x 8 blocks that the previous frame does not explain
+
+ctypes on the C ABI of libhomer_gpu.so (include/homer_gpu.h sections 12, 12d, 12e, 12f, 12g, 12h, 12i, 12j, 12k, 12l and 12m).  The pictures go from the tensors into the encoder's picture slots by one launch of
+the ingest kernel (k_ingest, csrc/picture_io.hip; RGB frames: k_ingest_rgb, which converts colour in the same pass; YUVFrame - more than 8 bits, 4:2:2, 4:4:4, packed -: k_ingest_yuv, which rounds to 8-bit 4:2:0 in the same pass; scaled frames: k_downscale, which area-averages in the same pass; scaled RGB frames: k_rgb_ladder, which does both; scaled YUVFrames: k_yuv_ladder, which rounds and averages) and the reconstructed pictures and their quality sums come back by one launch of the egress kernel (k_egress, same file), the SSIM sums by one launch of k_ssim (same file), the scene-cut statistics of a slot against the slot of the frame before by one launch of k_cut (same file), RGB pictures and the sums against an RGB reference by one launch of k_egress_rgb (same file), all
+ordered against torch's current stream by events: nothing is copied to the host, and neither side waits for the other on the host (a SceneCut policy reads its
+statistics on the host before the encode call: the one wait it adds).
 Importing this module needs neither torch nor a GPU; constructing an encoder without a GPU raises with the library's error text.
 """
 import ctypes as C
@@ -42,6 +48,7 @@ MATRICES = {"bt601": 0, "bt709": 1}
 ORDERS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0)), "argb": (4, (1, 2, 3)), "abgr": (4, (3, 2, 1))}      # pixel bytes, byte of R, G, B
 SLICE_P, SLICE_I = 1, 2
 IMAGE_AUTO, IMAGE_I = 0, 3          # encoder_in_out_t.image_type
+CUT_VALUES = 8                      # HMR_GPU_CUT_VALUES: SAD_Y, SAD_U, SAD_V, HIST, INTRA, INTER, NINTRA, LUMA
 
 
 class EncoderConfig(C.Structure):
@@ -297,11 +304,12 @@ def _declare_metrics(lib):
     lib.hmr_gpu_psnr.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
     lib.hmr_gpu_psnr_rgb.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_double)]
     lib.hmr_gpu_ssim.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib.hmr_gpu_cut_score.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_double)]
     return lib
 
 
 def _metric_library():
-    """the handle psnr, psnr_rgb and ssim call through: load_library()'s once it has run, else one cached handle that needs neither torch nor a GPU"""
+    """the handle psnr, psnr_rgb, ssim and cut_score call through: load_library()'s once it has run, else one cached handle that needs neither torch nor a GPU"""
     global _host_lib
     if _lib is not None:
         return _lib
@@ -350,6 +358,84 @@ def ssim(sums, width, height):
     return tuple(out)
 
 
+def cut_score(stats, width, height):
+    """The four scores of a frame against its predecessor from the eight scene-cut statistics - Python ints, e.g. Encoder.cut_stats().tolist() - of a width x height
+    picture, through hmr_gpu_cut_score (include/homer_gpu.h section 12m): (SAD_Y / (W H), HIST / (2 W H), NINTRA / blocks, INTER / INTRA or 1.0 when INTRA is 0), each
+    the correctly rounded quotient.  Pure host arithmetic: needs neither torch nor a GPU."""
+    lib = _metric_library()
+    values = [int(v) for v in stats]
+    if len(values) != CUT_VALUES or not all(-(1 << 63) <= v < 1 << 63 for v in values):
+        raise ValueError(f"cut_score: eight 64-bit values, got {values}")
+    out = (C.c_double * 4)()
+    if lib.hmr_gpu_cut_score((C.c_int64 * CUT_VALUES)(*values), int(width), int(height), out) != 0:
+        raise ValueError((lib.hmr_gpu_last_error() or b"hmr_gpu_cut_score").decode(errors="replace"))
+    return tuple(out)
+
+
+def _au_is_intra(au):
+    """an access unit holds an intra picture: one of its NAL units is an IRAP slice (types 16 .. 23; the encoder writes every I slice as an IDR picture)"""
+    at = au.find(b"\x00\x00\x01")
+    while 0 <= at < len(au) - 3:
+        if 16 <= (au[at + 3] >> 1) & 0x3f <= 23:
+            return True
+        at = au.find(b"\x00\x00\x01", at + 3)
+    return False
+
+
+class SceneCut:
+    """The policy that turns scene-cut statistics into intra pictures, for Encoder.encode(..., scene_cut=policy) and BatchEncoder.step(..., scene_cut=policy).  Pure
+    Python on the statistics' rows: needs neither torch nor a GPU.  One object serves one encoder for its whole life (it counts that encoder's frames).
+    A sequence CUTS in a step when all three hold: it has a pair (it was given a picture in the immediately preceding step too); cut_score's share of blocks that the
+    previous frame does not explain, NINTRA / blocks, is at least `share`; and at least `min_gap` frames have passed since the last intra picture the object saw for
+    it - one it forced, one the caller asked for, or one the encoder returned as slice type I (a pipelined BatchEncoder returns a frame's access unit one step late,
+    so an intra picture the encoder chose by itself is seen one frame late).  20 is the reference's own distance (hmr_motion_inter.c:3791).
+    groups: lists of sequence indices, each one ladder: the group's first member that has a picture in the step decides for all its members that have one, so the
+    rungs get their intra pictures on the same frame.  Sequences in no group decide alone."""
+
+    def __init__(self, share=0.5, min_gap=20, groups=None):
+        self.share, self.min_gap = float(share), int(min_gap)
+        self.groups = [[int(i) for i in g] for g in (groups or [])]
+        members = [i for g in self.groups for i in g]
+        if len(set(members)) != len(members) or min(members, default=0) < 0:
+            raise ValueError(f"SceneCut: a sequence belongs to one group at most, indices start at 0: {self.groups}")
+        self.frames = {}           # sequence -> the pictures it has been given
+        self.last_intra = {}       # sequence -> the number of its last intra picture (absent: none seen)
+
+    def wants(self, i, row, size):
+        """sequence i alone: its row (eight values; None or all -1: no pair) of a picture of `size` says cut, and its last intra picture is far enough back"""
+        if row is None or all(int(v) == -1 for v in row):
+            return False
+        if i in self.last_intra and self.frames.get(i, 0) - self.last_intra[i] < self.min_gap:
+            return False
+        return cut_score(row, size[0], size[1])[2] >= self.share
+
+    def decide(self, live, rows, sizes, image_types=None):
+        """One step.  live: the sequences that have a picture in it; rows[i], sizes[i], image_types[i]: the statistics (None or all -1: no pair), the (width, height)
+        and the image type the caller asked for, per SEQUENCE.  Returns one bool per sequence: the policy's decision.  The step's pictures are counted, and the intra
+        pictures that follow - decided here or asked for by the caller - are remembered."""
+        cuts = [False] * len(rows)
+        grouped = set()
+        for g in self.groups:
+            members = [i for i in g if i in live]
+            grouped.update(g)
+            if members and self.wants(members[0], rows[members[0]], sizes[members[0]]):
+                for i in members:
+                    cuts[i] = True
+        for i in live:
+            if i not in grouped:
+                cuts[i] = self.wants(i, rows[i], sizes[i])
+        for i in live:
+            if cuts[i] or (image_types is not None and int(image_types[i]) == IMAGE_I):
+                self.last_intra[i] = self.frames.get(i, 0)
+            self.frames[i] = self.frames.get(i, 0) + 1
+        return cuts
+
+    def observe(self, i, intra, back=0):
+        """what the encoder returned for sequence i's picture `back` pictures before its last: an intra picture is remembered"""
+        if intra:
+            self.last_intra[i] = max(self.last_intra.get(i, -1), self.frames.get(i, 0) - 1 - back)
+
+
 def load_library():
     """libhomer_gpu.so with the argument types of the calls this module makes.  torch brings up its HIP runtime first where it finds a GPU."""
     global _lib
@@ -383,6 +469,7 @@ def load_library():
         lib.hmr_gpu_enc_encode_source.argtypes = [P, I, I, C.c_char_p, L, C.POINTER(L), C.c_char_p]
         lib.hmr_gpu_enc_export_pictures_device.argtypes = [C.POINTER(P), I, C.POINTER(Picture), C.POINTER(I), P, P]
         lib.hmr_gpu_enc_ssim_device.argtypes = [C.POINTER(P), I, C.POINTER(I), P, P]
+        lib.hmr_gpu_enc_cut_stats.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), P, P]
         lib.hmr_gpu_enc_export_pictures_rgb_device.argtypes = [C.POINTER(P), I, C.POINTER(I), C.POINTER(RgbPicture), C.POINTER(RgbPicture), P, P]
         batch = [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_char_p), C.POINTER(L), C.POINTER(L)]
         lib.hmr_gpu_enc_encode_batch.argtypes = batch
@@ -485,6 +572,25 @@ def _ssim(lib, device, encs, slot):
     if lib.hmr_gpu_enc_ssim_device((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([slot] * n)), C.c_void_p(sums.data_ptr()), _stream_of(device)) != 0:
         _fail(lib, "hmr_gpu_enc_ssim_device")
     return sums
+
+
+def _cut_stats(lib, device, encs, slot):
+    """ONE hmr_gpu_enc_cut_stats for the encoders `encs`, slot `slot` against the other slot: an int64 tensor [len(encs), 8]"""
+    import torch
+    n = len(encs)
+    stats = torch.empty((n, CUT_VALUES), dtype=torch.int64, device=f"cuda:{device}")
+    if lib.hmr_gpu_enc_cut_stats((C.c_void_p * n)(*encs), n, (C.c_int * n)(*([slot] * n)), (C.c_int * n)(*([slot ^ 1] * n)), C.c_void_p(stats.data_ptr()), _stream_of(device)) != 0:
+        _fail(lib, "hmr_gpu_enc_cut_stats")
+    return stats
+
+
+def _cut_table(lib, device, encs, sequences, pairs, slot):
+    """the statistics of the sequences `pairs` (indices into encs; slot `slot` against the other slot) as an int64 tensor [sequences, 8]; every other row is -1"""
+    import torch
+    table = torch.full((sequences, CUT_VALUES), -1, dtype=torch.int64, device=f"cuda:{device}")
+    if pairs:
+        table[torch.tensor(pairs, device=table.device)] = _cut_stats(lib, device, [encs[i] for i in pairs], slot)
+    return table
 
 
 # What a frame class is loaded by: (ctypes struct, C call, the function that describes frame k of a step).  Consulted in this order; anything else is what
@@ -602,20 +708,42 @@ class Encoder:
         self.buf = C.create_string_buffer(_au_capacity(cfg))
         self.slot = 0
         self.slot_used = None            # the slot of the last encoded frame (export)
+        self.has_pair = False            # the other slot holds the frame before it (cut_stats)
+        self.last_cuts = None            # the SceneCut policy's decision of the last encode() that had one: [bool]
 
-    def encode(self, frame, image_type=IMAGE_AUTO):
+    def encode(self, frame, image_type=IMAGE_AUTO, scene_cut=None):
         """frame: what picture_of takes, an RGBFrame, a YUVFrame, a ScaledFrame, a ScaledRGBFrame or a ScaledYUVFrame.  image_type 0: the encoder decides (intra_period, scene changes), 3: an intra picture.  Returns (bytes, 1 for P /
-        2 for I)."""
+        2 for I).
+        scene_cut: a SceneCut policy (the encoder is its sequence 0).  Behind the load, one launch of k_cut compares the frame with the one before, the eight values are
+        copied to the host - the one host wait the policy adds - and where the policy cuts, the frame is encoded as an intra picture; an image_type the caller set to
+        intra stays.  The decision is readable as last_cuts.  Without a policy the calls are exactly those of before."""
         lib = self.lib
         keep = _load(lib, self.device, [self.enc], [self.cfg], self.slot, [frame])
+        pair = self.slot_used is not None
+        if scene_cut is not None:
+            row = _cut_stats(lib, self.device, [self.enc], self.slot)[0].tolist() if pair else None
+            self.last_cuts = scene_cut.decide([0], [row], [(int(self.cfg.width), int(self.cfg.height))], [image_type])
+            if self.last_cuts[0]:
+                image_type = IMAGE_I
         n = C.c_long()
         slice_type = lib.hmr_gpu_enc_encode_source(self.enc, self.slot, int(image_type), self.buf, len(self.buf), C.byref(n), None)
         del keep
         if slice_type < 0:
             _fail(lib, "hmr_gpu_enc_encode_source")
-        self.slot_used = self.slot
+        self.slot_used, self.has_pair = self.slot, pair
         self.slot ^= 1
+        if scene_cut is not None:
+            scene_cut.observe(0, slice_type == SLICE_I)
         return self.buf.raw[:n.value], slice_type
+
+    def cut_stats(self):
+        """The eight exact scene-cut statistics (SAD_Y, SAD_U, SAD_V, HIST, INTRA, INTER, NINTRA, LUMA: include/homer_gpu.h section 12m) of the frame the last encode()
+        encoded against the frame the encode() before it encoded, as they lie in the two picture slots, as an int64 CUDA tensor [8]; all -1 after the first frame, which
+        has no predecessor.  cut_score(stats.tolist(), W, H) gives the scores.  One launch of k_cut, ordered on torch's current stream: what is queued there afterwards
+        sees the values, nothing waits on the host."""
+        if self.slot_used is None:
+            raise RuntimeError("Encoder.cut_stats: nothing has been encoded yet")
+        return _cut_table(self.lib, self.device, [self.enc], 1, [0] if self.has_pair else [], self.slot_used)[0]
 
     def export(self, picture=True, ssd=False, out=None, nv12=False):
         """The reconstructed picture of the frame the last encode() encoded (the final picture: after deblocking and SAO, what a decoder makes of the access unit) and / or
@@ -711,6 +839,8 @@ class BatchEncoder:
         self.slot = 0
         self.outstanding = None          # pipelined: the sequences of the step whose access units have not been delivered
         self.last_live, self.slot_used = [], None      # the sequences of the last step that had a picture, and the slot they were encoded from (export)
+        self.before, self.pairs = [], []               # the sequences that had a picture in the step before this one, and those of last_live whose other slot holds it
+        self.last_cuts = None                          # the SceneCut policy's decision of the last step() that had one: a bool per sequence
 
     def _call(self, live, slots, image_types):
         n = len(live)
@@ -723,7 +853,10 @@ class BatchEncoder:
             _fail(self.lib, "hmr_gpu_enc_encode_batch_pipelined" if self.pipelined else "hmr_gpu_enc_encode_batch")
         return {i: C.string_at(self.bufs[i], got[k]) for k, i in enumerate(live)}
 
-    def step(self, frames, image_types=None):
+    def step(self, frames, image_types=None, scene_cut=None):
+        """scene_cut: a SceneCut policy.  Behind the load, ONE launch of k_cut compares every sequence's picture with the one it was given in the step before, the
+        8 x n values are copied to the host - the one host wait the policy adds - and the sequences the policy cuts are encoded as intra pictures; an image type the
+        caller set to intra stays.  The decision is readable as last_cuts.  Without a policy the calls are exactly those of before."""
         if len(frames) != len(self.encs):
             raise ValueError(f"BatchEncoder.step: {len(self.encs)} sequences, {len(frames)} frames")
         live = [i for i, f in enumerate(frames) if f is not None]
@@ -733,13 +866,22 @@ class BatchEncoder:
         if live:
             slots = [self.slot] * len(live)
             keep = _load(self.lib, self.device, [self.encs[i] for i in live], [self.cfgs[i] for i in live], self.slot, [frames[i] for i in live])
+            pairs = [i for i in live if i in self.before]
+            if scene_cut is not None:
+                rows = _cut_table(self.lib, self.device, self.encs, len(self.encs), pairs, self.slot).tolist()
+                self.last_cuts = scene_cut.decide(live, rows, [(int(c.width), int(c.height)) for c in self.cfgs], image_types)
+                image_types = [IMAGE_I if cut else (int(image_types[i]) if image_types is not None else IMAGE_AUTO) for i, cut in enumerate(self.last_cuts)]
             for i, au in self._call(live, slots, [int(image_types[i]) for i in live] if image_types is not None else None).items():
                 out[i] = out.get(i, b"") + au      # (behind a flush the call itself delivers nothing)
             del keep
-            self.last_live, self.slot_used = live, self.slot
+            self.last_live, self.slot_used, self.pairs = live, self.slot, pairs
             self.slot ^= 1
             if self.pipelined:
                 self.outstanding = live
+            if scene_cut is not None:
+                for i, au in out.items():      # (pipelined: the access unit of the picture before the one just given)
+                    scene_cut.observe(i, _au_is_intra(au), 1 if self.pipelined and i in live else 0)
+        self.before = live
         return [out.get(i, b"") for i in range(len(self.encs))]
 
     def export(self, picture=True, ssd=False, out=None, nv12=False):
@@ -775,6 +917,13 @@ class BatchEncoder:
         table = torch.full((len(self.encs), 3), -(1 << 63), dtype=torch.int64, device=sums.device)
         table[torch.tensor(live, device=sums.device)] = sums
         return table
+
+    def cut_stats(self):
+        """As Encoder.cut_stats, for every sequence that was given a picture in the last step() AND in the step before it, with ONE launch: an int64 CUDA tensor
+        [sequences, 8]; the row of a sequence that has no such pair - idle in either step, or the first step - is all -1 (no statistic is negative)."""
+        if not self.last_live:
+            raise RuntimeError("BatchEncoder.cut_stats: the last step encoded nothing")
+        return _cut_table(self.lib, self.device, self.encs, len(self.encs), self.pairs, self.slot_used)
 
     def export_rgb(self, out=None, order=None, dtype=None, matrix="bt709", full_range=False, reference=None, source=False):
         """As Encoder.export_rgb, for every sequence that was given a picture in the last step(), with ONE launch - also with access units outstanding.  `out` and

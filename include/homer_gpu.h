@@ -1111,6 +1111,60 @@ int hmr_gpu_enc_load_source_scaled_yuv(hmr_gpu_enc *enc, int slot, const hmr_gpu
 int hmr_gpu_scale_yuv_host(const hmr_gpu_scaled_yuv_picture *pic, int dst_w, int dst_h, uint8_t *y, uint8_t *u, uint8_t *v);
 
 /* ------------------------------------------------------------------------------------------------
+ * 12m. Scene-cut statistics of a frame against its predecessor, left in device memory: batched motion-compensated cost sums
+ *     Every encode call takes an image_type; nothing in the library said when to pass an intra picture.  The reference's own detector (hmr_motion_inter.c:3791) fires
+ *     in the middle of a P frame, after a tenth of the partitions, adjusts costs and the GOP, and leaves the cut frame a P picture; it runs per encoder, so the rungs
+ *     of a ladder decide independently.  hmr_gpu_enc_cut_stats leaves, for n encoders (1 .. 512, sizes mixed), eight exact statistics of the picture in slot
+ *     slots[i] of encs[i] (cur) against the picture in slot prev_slots[i] of the same encoder (prev) with ONE call: a launch of k_cut (picture_io.hip) over the int16
+ *     planes of the two slots and a small finishing kernel behind it, no host synchronisation.  It needs no encoded picture: it works before the first encode, on
+ *     whatever the two slots hold when the launch runs - whatever form the frames arrived in (12d, 12f, 12g, 12j, 12k, 12l).
+ *     The arithmetic is defined in integers, so that a caller can reproduce every value (homerhevc_amd/csrc/cut_stats.h holds it once, for the kernel and the host).
+ *     cur and prev are 8-bit 4:2:0 samples of a W x H picture.  Every size the frame encoder accepts is a multiple of 8, so luma is an exact grid of 8 x 8 BLOCKS.
+ *     The call leaves HMR_GPU_CUT_VALUES = 8 signed 64-bit values per picture, each exact in any order of addition:
+ *       0, 1, 2  SAD_Y, SAD_U, SAD_V   the sum of abs(cur - prev) over the plane
+ *       3        HIST                  the sum over v = 0 .. 255 of abs(hc[v] - hp[v]), hc and hp being the luma histograms of cur and prev; it lies in 0 .. 2 W H
+ *       4        INTRA                 the sum of act(b) over the blocks
+ *       5        INTER                 the sum of min(64 msad(b), act(b)) over the blocks
+ *       6        NINTRA                the number of blocks with act(b) < 64 msad(b) (strict)
+ *       7        LUMA                  the sum of cur's luma samples (for fades: the caller keeps the previous value)
+ *     The per-block terms, for the luma block b at (bx, by):
+ *       act(b)   the sum over the block's 64 samples x of abs(64 x - S), S the block's sample sum: the mean-removed deviation, scaled by 64 so that nothing is
+ *                rounded.  At most 522 240 (32 samples of 255 and 32 of 0).
+ *       msad(b)  the minimum, over the valid integer vectors, of the sum over the 64 samples of abs(cur(bx + i, by + j) - prev(bx + dx + i, by + dy + j)).
+ *       valid    (dx, dy) in [-R, R]^2, R = HMR_GPU_CUT_RANGE = 8, for which the displaced block lies wholly inside the picture: 0 <= bx + dx, bx + dx + 8 <= W,
+ *                and likewise in y.  (0, 0) is always valid, and an 8 x 8 picture has only that vector.
+ *     The two entries on encoders take device memory like their siblings; their names deliberately do not end in _device, as 12l's.
+ *     Only the minimum VALUE enters a sum, so no tie-break exists to get wrong.  No sample outside W x H is read: the slots' margins are never looked at.
+ *     dev_stats (device memory, n x 8 values): dev_stats[8 * i + k] = value k of encs[i].  The same encoder may appear more than once.
+ *     consumer_stream: as in 12h, word for word.  The launch runs on the first encoder's stream behind an event recorded on consumer_stream (the consumer may still be
+ *     using dev_stats) and behind whatever the encoders' streams hold (a load into a slot); dev_stats and the library's histogram bins (2 x 256 32-bit counts per
+ *     picture, owned by the first encoder) are zeroed on that stream in front of the launch.  Behind the launch the library records an event that consumer_stream and
+ *     the streams of all the call's encoders wait for: what the caller queues on consumer_stream after the call sees the values, a later load into either slot runs
+ *     after the kernel has read the pictures.  The host waits for nothing in either direction (but for the bins, allocated at the first call an encoder leads).
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is queued, every encoder left working: n outside 1 .. 512, NULL encs, slots,
+ *     prev_slots or dev_stats, a NULL encoder, encoders on different devices, a slot or a previous slot that does not exist, slots[i] == prev_slots[i], dev_stats that
+ *     hipPointerGetAttributes does not report as device memory of the encoders' device.
+ *     hmr_gpu_cut_stats_host: the same arithmetic in plain nested loops over two 8-bit pictures in HOST memory - the descriptors' planes are host pointers here; I420
+ *     or NV12 (the two may differ), any pitch - into stats[8].  No device, no context.  It refuses what hmr_gpu_picture_check refuses for either picture, a width or
+ *     height that is not a positive multiple of 8, and NULL stats.
+ *     hmr_gpu_cut_score: four correctly rounded double quotients of exact integers (every operand is exact below 2^53).  Pure host code.
+ *       score[0] = SAD_Y / (W H)          the mean absolute luma difference, 0 .. 255
+ *       score[1] = HIST / (2 W H)         0 .. 1
+ *       score[2] = NINTRA / blocks        the share of blocks that motion compensation from prev does not explain, 0 .. 1; blocks = W H / 64
+ *       score[3] = INTER / INTRA          0 .. 1, or 1.0 when INTRA is 0
+ *     It refuses NULL arguments, a width or height that is not a positive multiple of 8, a value outside its range (below 0; SAD_Y, LUMA above 255 W H; SAD_U, SAD_V
+ *     above 255 W H / 4; HIST above 2 W H; INTRA, INTER above 522 240 blocks; NINTRA above blocks) and INTER above INTRA.
+ *     Out of scope: sub-sample motion, vectors or per-block maps as outputs, ranges other than 8, chroma in the search, lookahead over more than one frame, fade
+ *     handling beyond exposing LUMA.  The reference's own detector is unchanged.
+ * ------------------------------------------------------------------------------------------------ */
+#define HMR_GPU_CUT_VALUES 8
+#define HMR_GPU_CUT_RANGE 8
+int hmr_gpu_enc_cut_stats(hmr_gpu_enc **encs, int n, const int *slots, const int *prev_slots, int64_t *dev_stats, void *consumer_stream);
+int hmr_gpu_enc_cut_stats_one(hmr_gpu_enc *enc, int slot, int prev_slot, int64_t *dev_stats, void *consumer_stream);
+int hmr_gpu_cut_stats_host(const hmr_gpu_picture *cur, const hmr_gpu_picture *prev, int width, int height, int64_t stats[8]);
+int hmr_gpu_cut_score(const int64_t stats[8], int width, int height, double score[4]);
+
+/* ------------------------------------------------------------------------------------------------
  * 13. Phase planes of a reference picture
  *     Replaces the per-block interpolation calls of the motion search and of motion compensation - the sixteen planes of
  *     hmr_half_pixel_estimation_luma_hm / hmr_quarter_pixel_estimation_luma_hm (hmr_motion_inter.c:395,442) and
