@@ -172,7 +172,10 @@ template <int V> struct RgbForm {
 	static constexpr int PX = V == RGB_F32 ? 8 : 16;      // pixels read at a time (binary32: half a span, 96 bytes a row)
 	static constexpr int PLANE = V == RGB_PLANAR8 ? PX / 4 : V == RGB_F16 ? PX / 2 : PX;      // dwords per channel (planar)
 	static constexpr int WORDS = V == RGB_PACKED3 ? 3 * PX / 4 : V == RGB_PACKED4 ? PX : 3 * PLANE;
+	static constexpr int FMT = V == RGB_PLANAR8 ? HMR_GPU_RGB_PLANAR8 : V == RGB_F16 ? HMR_GPU_RGB_PLANAR_F16 : V == RGB_F32 ? HMR_GPU_RGB_PLANAR_F32 : HMR_GPU_RGB_PACKED8;      // (for rgb_sample)
 };
+// a compile-time tag: what rgb_dispatch / yuv_dispatch hand a generic callable
+template <int N> struct Int { static constexpr int value = N; };
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // which of the forms RGB_PACKED3 .. RGB_F32 a descriptor's format and pixel bytes are
 __host__ __device__ __forceinline__ int rgb_form(int format, int pixel_bytes)
@@ -234,6 +237,49 @@ __device__ __forceinline__ void rgb_pixel(const uint32_t *raw, int i, const int 
 	}
 }
 
+// the sample-by-sample R, G, B of pixel (px, py) of a job's picture of format FMT: rgb_yuv.h's rgb_sample - the one the host twin runs - on global pointers (the rows' tails)
+template <int FMT, class Job>
+__device__ __forceinline__ void rgb_sample3(const Job &j, int px, int py, int c3[3])
+{
+	constexpr bool packed = FMT == HMR_GPU_RGB_PACKED8;
+#pragma unroll
+	for (int c = 0; c < 3; c++)
+		c3[c] = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[packed ? 0 : c], j.pitch[packed ? 0 : c], FMT, j.pixel_bytes, j.offset[c], px, py);
+}
+
+// the 2 x 2 block of pixels i, i + 1 of two adjacent rows a, b: its four pixels (a's two, then b's) and their R, G, B sums - what one chroma sample is made of
+template <int V>
+__device__ __forceinline__ void rgb_quad(const uint32_t *a, const uint32_t *b, int i, const int sh[3], int px[4][3], int s[3])
+{
+#pragma unroll
+	for (int k = 0; k < 4; k++) rgb_pixel<V>(k < 2 ? a : b, i + (k & 1), sh, px[k][0], px[k][1], px[k][2]);
+#pragma unroll
+	for (int c = 0; c < 3; c++) s[c] = px[0][c] + px[1][c] + px[2][c] + px[3][c];
+}
+
+// 16 pixels at (x, y) of rows y and y + 1 in pieces of F::PX pixels (binary32: two halves, the other forms one load a row): half(h, a, b, i0) for h = 0, 1 - the
+// eight pixels of half h are pixels i0 .. i0 + 7 of the raw rows a and b
+template <int V, class Job, class Half>
+__device__ __forceinline__ void rgb_two_rows(const Job &j, int x, int y, Half half)
+{
+	typedef RgbForm<V> F;
+	if (F::PX == 8) {
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			uint32_t a[F::WORDS], b[F::WORDS];
+			rgb_load_row<V>(j, x + 8 * h, y, a);
+			rgb_load_row<V>(j, x + 8 * h, y + 1, b);
+			half(h, a, b, 0);
+		}
+	} else {
+		uint32_t a[F::WORDS], b[F::WORDS];
+		rgb_load_row<V>(j, x, y, a);
+		rgb_load_row<V>(j, x, y + 1, b);
+#pragma unroll
+		for (int h = 0; h < 2; h++) half(h, a, b, 8 * h);
+	}
+}
+
 // pixels i0 .. i0 + 7 of two adjacent rows a, b: eight luma samples of each row and four U and four V samples, as int16 pairs
 template <int V>
 __device__ __forceinline__ void rgb_convert8(const uint32_t *a, const uint32_t *b, int i0, const RgbMatrix &m, const int sh[3], u32x4 &ya, u32x4 &yb, uint32_t *u, uint32_t *v)
@@ -241,16 +287,12 @@ __device__ __forceinline__ void rgb_convert8(const uint32_t *a, const uint32_t *
 	uint32_t la[4], lb[4], cu[4], cv[4];
 #pragma unroll
 	for (int p = 0; p < 4; p++) {
-		int r0, g0, b0, r1, g1, b1, r2, g2, b2, r3, g3, b3;
-		rgb_pixel<V>(a, i0 + 2 * p, sh, r0, g0, b0);
-		rgb_pixel<V>(a, i0 + 2 * p + 1, sh, r1, g1, b1);
-		rgb_pixel<V>(b, i0 + 2 * p, sh, r2, g2, b2);
-		rgb_pixel<V>(b, i0 + 2 * p + 1, sh, r3, g3, b3);
-		la[p] = (uint32_t)hmr_rgb_luma(m, r0, g0, b0) | (uint32_t)hmr_rgb_luma(m, r1, g1, b1) << 16;
-		lb[p] = (uint32_t)hmr_rgb_luma(m, r2, g2, b2) | (uint32_t)hmr_rgb_luma(m, r3, g3, b3) << 16;
-		const int sr = r0 + r1 + r2 + r3, sg = g0 + g1 + g2 + g3, sb = b0 + b1 + b2 + b3;
-		cu[p] = (uint32_t)hmr_rgb_chroma(m.u, sr, sg, sb);
-		cv[p] = (uint32_t)hmr_rgb_chroma(m.v, sr, sg, sb);
+		int px[4][3], s[3];
+		rgb_quad<V>(a, b, i0 + 2 * p, sh, px, s);
+		la[p] = (uint32_t)hmr_rgb_luma(m, px[0][0], px[0][1], px[0][2]) | (uint32_t)hmr_rgb_luma(m, px[1][0], px[1][1], px[1][2]) << 16;
+		lb[p] = (uint32_t)hmr_rgb_luma(m, px[2][0], px[2][1], px[2][2]) | (uint32_t)hmr_rgb_luma(m, px[3][0], px[3][1], px[3][2]) << 16;
+		cu[p] = (uint32_t)hmr_rgb_chroma(m.u, s[0], s[1], s[2]);
+		cv[p] = (uint32_t)hmr_rgb_chroma(m.v, s[0], s[1], s[2]);
 	}
 	ya = u32x4{la[0], la[1], la[2], la[3]};
 	yb = u32x4{lb[0], lb[1], lb[2], lb[3]};
@@ -262,24 +304,9 @@ __device__ __forceinline__ void rgb_convert8(const uint32_t *a, const uint32_t *
 template <int V>
 __device__ __forceinline__ void rgb_span(const RgbIngestJob &j, int x, int y, const int sh[3])
 {
-	typedef RgbForm<V> F;
 	u32x4 ya[2], yb[2];
 	uint32_t u[4], v[4];
-	if (F::PX == 8) {
-#pragma unroll
-		for (int h = 0; h < 2; h++) {
-			uint32_t a[F::WORDS], b[F::WORDS];
-			rgb_load_row<V>(j, x + 8 * h, y, a);
-			rgb_load_row<V>(j, x + 8 * h, y + 1, b);
-			rgb_convert8<V>(a, b, 0, j.m, sh, ya[h], yb[h], u + 2 * h, v + 2 * h);
-		}
-	} else {
-		uint32_t a[F::WORDS], b[F::WORDS];
-		rgb_load_row<V>(j, x, y, a);
-		rgb_load_row<V>(j, x, y + 1, b);
-#pragma unroll
-		for (int h = 0; h < 2; h++) rgb_convert8<V>(a, b, 8 * h, j.m, sh, ya[h], yb[h], u + 2 * h, v + 2 * h);
-	}
+	rgb_two_rows<V>(j, x, y, [&](int h, const uint32_t *a, const uint32_t *b, int i0) { rgb_convert8<V>(a, b, i0, j.m, sh, ya[h], yb[h], u + 2 * h, v + 2 * h); });
 	GLOBAL_AS u32x4 *oa = (GLOBAL_AS u32x4 *)((samples_out)j.dst[0] + (size_t)y * j.stride_y + x), *ob = (GLOBAL_AS u32x4 *)((samples_out)j.dst[0] + (size_t)(y + 1) * j.stride_y + x);
 	oa[0] = ya[0]; oa[1] = ya[1];
 	ob[0] = yb[0]; ob[1] = yb[1];
@@ -293,17 +320,14 @@ template <int FMT>
 __device__ __forceinline__ void rgb_block(const RgbIngestJob &j, int bx, int y)
 {
 	const samples_out dy = (samples_out)j.dst[0];
-	constexpr bool packed = FMT == HMR_GPU_RGB_PACKED8;
 	int s[3] = {0, 0, 0};
 #pragma unroll
 	for (int k = 0; k < 4; k++) {
 		const int px = bx + (k & 1), py = y + (k >> 1);
 		int c3[3];
+		rgb_sample3<FMT>(j, px, py, c3);
 #pragma unroll
-		for (int c = 0; c < 3; c++) {
-			c3[c] = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[packed ? 0 : c], j.pitch[packed ? 0 : c], FMT, j.pixel_bytes, j.offset[c], px, py);
-			s[c] += c3[c];
-		}
+		for (int c = 0; c < 3; c++) s[c] += c3[c];
 		dy[(size_t)py * j.stride_y + px] = (int16_t)hmr_rgb_luma(j.m, c3[0], c3[1], c3[2]);
 	}
 	const size_t oc = (size_t)(y >> 1) * j.stride_c + (bx >> 1);
@@ -311,41 +335,49 @@ __device__ __forceinline__ void rgb_block(const RgbIngestJob &j, int bx, int y)
 	((samples_out)j.dst[2])[oc] = (int16_t)hmr_rgb_chroma(j.m.v, s[0], s[1], s[2]);
 }
 
-// the rows y0 .. of a picture read in form V (format FMT): whole spans, then the row's tail of fewer than 16 pixels, a lane per 2 x 2 block
-template <int V, int FMT>
-__device__ __forceinline__ void rgb_chunk(const RgbIngestJob &j, int y0)
+// The chunk walk of k_ingest_rgb and k_ingest_yuv: block b of a picture takes the CHUNK_ROWS luma rows from b * CHUNK_ROWS on, two at a time - span(x, y) for every whole
+// span of 16 pixels of rows y and y + 1, then block(bx, y) for the 2 x 2 blocks of the row's tail of fewer than 16 pixels, a lane per block.
+__host__ __device__ __forceinline__ int pair_chunks(int height) { return (height + CHUNK_ROWS - 1) / CHUNK_ROWS; }
+template <class Job, class Span, class Block>
+__device__ __forceinline__ void pair_chunk(const Job &j, int y0, Span span, Block block)
 {
 	const int left = j.height - y0, pairs = (left < CHUNK_ROWS ? left : CHUNK_ROWS) >> 1, per_row = j.width >> 4;      // (whole spans)
-	const int sh[3] = {8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]};
 	for (int i = (int)threadIdx.x; i < pairs * per_row; i += HMR_BLOCK) {
 		const int r = i / per_row, x = (i - r * per_row) << 4, y = y0 + 2 * r;
-		rgb_span<V>(j, x, y, sh);
+		span(x, y);
 	}
 	const int tail = (j.width & 15) >> 1;
 	for (int i = (int)threadIdx.x; i < pairs * tail; i += HMR_BLOCK) {
 		const int r = i / tail;
-		rgb_block<FMT>(j, (j.width & ~15) + 2 * (i - r * tail), y0 + 2 * r);
+		block((j.width & ~15) + 2 * (i - r * tail), y0 + 2 * r);
 	}
 }
 
-__host__ __device__ __forceinline__ int rgb_chunks(int height) { return (height + CHUNK_ROWS - 1) / CHUNK_ROWS; }
+// The forms of the RGB family, once: with(Int<V>) for the form V of a job's picture (k_ingest_rgb, k_rgb_ladder; a launch mixes forms, one per picture)
+template <class Job, class With>
+__device__ __forceinline__ void rgb_dispatch(const Job &j, With with)
+{
+	switch (rgb_form(j.format, j.pixel_bytes)) {
+	case RGB_PACKED3: with(Int<RGB_PACKED3>{}); break;
+	case RGB_PACKED4: with(Int<RGB_PACKED4>{}); break;
+	case RGB_PLANAR8: with(Int<RGB_PLANAR8>{}); break;
+	case RGB_F16: with(Int<RGB_F16>{}); break;
+	default: with(Int<RGB_F32>{}); break;
+	}
+}
 
 __global__ __launch_bounds__(HMR_BLOCK) void k_ingest_rgb(const RgbIngestJob *jobs)
 {
 	const RgbIngestJob j = jobs[blockIdx.y];
 	const int y0 = (int)blockIdx.x * CHUNK_ROWS;
 	if (y0 >= j.height) return;
-	switch (j.format) {
-	case HMR_GPU_RGB_PACKED8:
-		if (j.pixel_bytes == 3) rgb_chunk<RGB_PACKED3, HMR_GPU_RGB_PACKED8>(j, y0);
-		else rgb_chunk<RGB_PACKED4, HMR_GPU_RGB_PACKED8>(j, y0);
-		break;
-	case HMR_GPU_RGB_PLANAR8: rgb_chunk<RGB_PLANAR8, HMR_GPU_RGB_PLANAR8>(j, y0); break;
-	case HMR_GPU_RGB_PLANAR_F16: rgb_chunk<RGB_F16, HMR_GPU_RGB_PLANAR_F16>(j, y0); break;
-	default: rgb_chunk<RGB_F32, HMR_GPU_RGB_PLANAR_F32>(j, y0); break;
-	}
+	const int sh[3] = {8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]};
+	rgb_dispatch(j, [&](auto form) {
+		constexpr int V = decltype(form)::value;
+		pair_chunk(j, y0, [&](int x, int y) { rgb_span<V>(j, x, y, sh); }, [&](int bx, int y) { rgb_block<RgbForm<V>::FMT>(j, bx, y); });
+	});
 }
-template <> struct PictureKernel<RgbIngestJob> { static constexpr auto kernel = k_ingest_rgb; static int chunks(const RgbIngestJob &j) { return rgb_chunks(j.height); } };
+template <> struct PictureKernel<RgbIngestJob> { static constexpr auto kernel = k_ingest_rgb; static int chunks(const RgbIngestJob &j) { return pair_chunks(j.height); } };
 
 // ---- deep / 4:2:2 / 4:4:4 ingest (section 12k) ----
 // k_ingest_yuv: Y'CbCr pictures of 8 .. 16 bits - 4:2:0, 4:2:2 or 4:4:4; planar, semi-planar in either order, or packed 4:2:2 in any of its four orders - into the int16
@@ -402,13 +434,53 @@ template <int L, int SB, int K> struct YuvSpan {
 	static constexpr int TAPS = K == 2 ? 2 : 1;                                      // per row
 };
 
+// The chroma tap sums of eight columns of the converted 4:2:0 chroma planes, added into su (U) and sv (V); the caller rounds a sum with f.s + K.  (8 bits: s = 0,
+// maxv = 255, rs = 0 - hmr_yuv_value is the identity and is left out.)  Two forms, both for k_ingest_yuv's spans and k_yuv_ladder's chroma tiles:
+// a packed row that is already in registers - group c of its 8 groups (16 pixels) holds chroma column c; the two rows under a chroma row make K = 1
+template <int SB>
+__device__ __forceinline__ void yuv_taps_packed(const YuvForm &f, const uint32_t *g, uint32_t *su, uint32_t *sv)
+{
+	const int bits1 = 8 * SB * f.offset[1], bits2 = 8 * SB * f.offset[2];
+#pragma unroll
+	for (int c = 0; c < 8; c++) {
+		const uint32_t u = yuv_pick<SB, 4>(g, c, bits1), v = yuv_pick<SB, 4>(g, c, bits2);
+		su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
+		sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
+	}
+}
+// the planar and semi-planar layouts: loads the F::ROWS x 8 F::TAPS containers of U and of V under columns cx .. cx + 7 of converted chroma row cy (Job: YuvIngestJob, YuvScaleJob)
+template <int L, int SB, int K, class Job>
+__device__ __forceinline__ void yuv_taps_planes(const Job &j, int cx, int cy, uint32_t *su, uint32_t *sv)
+{
+	typedef YuvSpan<L, SB, K> F;
+	const YuvForm &f = j.f;
+	const int bits1 = 8 * SB * f.offset[1], bits2 = 8 * SB * f.offset[2];
+	const int row0 = K == 0 ? cy : 2 * cy, col0 = K == 2 ? 2 * cx : cx;
+#pragma unroll
+	for (int r = 0; r < F::ROWS; r++) {
+		uint32_t cu[F::CHROMA_BYTES / 4], cv[F::CHROMA_BYTES / 4];
+		yuv_load<F::CHROMA_BYTES>((bytes_in)j.src[1] + (int64_t)(row0 + r) * j.pitch[1] + (int64_t)col0 * SB * (L == YUV_SEMI ? 2 : 1), cu);
+		if (L == YUV_PLANAR) yuv_load<F::CHROMA_BYTES>((bytes_in)j.src[2] + (int64_t)(row0 + r) * j.pitch[2] + (int64_t)col0 * SB, cv);
+#pragma unroll
+		for (int c = 0; c < 8; c++)
+#pragma unroll
+			for (int t = 0; t < F::TAPS; t++) {
+				const int i = c * F::TAPS + t;
+				const uint32_t u = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, i, bits1) : yuv_pick<SB, 1>(cu, i, 0);
+				const uint32_t v = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, i, bits2) : yuv_pick<SB, 1>(cv, i, 0);
+				su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
+				sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
+			}
+	}
+}
+
 // 16 pixels at (x, y) of rows y and y + 1 (x a multiple of 16, y even): 32 luma samples, 8 U and 8 V samples
 template <int L, int SB, int K>
 __device__ __forceinline__ void yuv_span(const YuvIngestJob &j, int x, int y)
 {
 	typedef YuvSpan<L, SB, K> F;
 	const YuvForm &f = j.f;
-	const int bits0 = 8 * SB * f.offset[0], bits1 = 8 * SB * f.offset[1], bits2 = 8 * SB * f.offset[2];
+	const int bits0 = 8 * SB * f.offset[0];
 	uint32_t la[2][F::LUMA_BYTES / 4];
 #pragma unroll
 	for (int r = 0; r < 2; r++) yuv_load<F::LUMA_BYTES>((bytes_in)j.src[0] + (int64_t)(y + r) * j.pitch[0] + (int64_t)x * (L == YUV_PACKED ? 2 : 1) * SB, la[r]);
@@ -429,38 +501,12 @@ __device__ __forceinline__ void yuv_span(const YuvIngestJob &j, int x, int y)
 		d[0] = u32x4{o[0], o[1], o[2], o[3]};
 		d[1] = u32x4{o[4], o[5], o[6], o[7]};
 	}
-	uint32_t su[8], sv[8];
+	uint32_t su[8] = {}, sv[8] = {};
+	if (L == YUV_PACKED) {      // the rows are here already
 #pragma unroll
-	for (int c = 0; c < 8; c++) su[c] = sv[c] = 0;
-	if (L == YUV_PACKED) {      // the rows are here already: group c holds chroma column c
-#pragma unroll
-		for (int r = 0; r < 2; r++)
-#pragma unroll
-			for (int c = 0; c < 8; c++) {
-				const uint32_t u = yuv_pick<SB, 4>(la[r], c, bits1), v = yuv_pick<SB, 4>(la[r], c, bits2);
-				su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
-				sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
-			}
-	} else {
-		const int row0 = K == 0 ? y >> 1 : y, col0 = K == 2 ? x : x >> 1;
-#pragma unroll
-		for (int r = 0; r < F::ROWS; r++) {
-			uint32_t cu[F::CHROMA_BYTES / 4], cv[F::CHROMA_BYTES / 4];
-			yuv_load<F::CHROMA_BYTES>((bytes_in)j.src[1] + (int64_t)(row0 + r) * j.pitch[1] + (int64_t)col0 * SB * (L == YUV_SEMI ? 2 : 1), cu);
-			if (L == YUV_PLANAR) yuv_load<F::CHROMA_BYTES>((bytes_in)j.src[2] + (int64_t)(row0 + r) * j.pitch[2] + (int64_t)col0 * SB, cv);
-#pragma unroll
-			for (int c = 0; c < 8; c++)
-#pragma unroll
-				for (int t = 0; t < F::TAPS; t++) {
-					const int i = c * F::TAPS + t;
-					const uint32_t u = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, i, bits1) : yuv_pick<SB, 1>(cu, i, 0);
-					const uint32_t v = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, i, bits2) : yuv_pick<SB, 1>(cv, i, 0);
-					su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
-					sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
-				}
-		}
-	}
-	const int t = f.s + K;      // (8 bits: s = 0, maxv = 255, rs = 0 - hmr_yuv_value is the identity and was left out above)
+		for (int r = 0; r < 2; r++) yuv_taps_packed<SB>(f, la[r], su, sv);
+	} else yuv_taps_planes<L, SB, K>(j, x >> 1, y >> 1, su, sv);
+	const int t = f.s + K;
 	uint32_t ou[4], ov[4];
 #pragma unroll
 	for (int q = 0; q < 4; q++) {
@@ -486,27 +532,33 @@ __device__ __forceinline__ void yuv_block(const YuvIngestJob &j, int bx, int y)
 	((samples_out)j.dst[2])[oc] = (int16_t)hmr_yuv_chroma<bytes_in>(j.src, j.pitch, j.f, 2, bx >> 1, y >> 1);
 }
 
-// the rows y0 .. of a picture in layout L with containers of SB bytes and 2^K chroma taps: whole spans, then the row's tail of fewer than 16 pixels
-template <int L, int SB, int K>
-__device__ __forceinline__ void yuv_chunk(const YuvIngestJob &j, int y0)
+// The forms of the Y'CbCr family, once (k_ingest_yuv, k_yuv_ladder; a launch mixes forms, one per picture): yuv_dispatch gives with(Int<L>, Int<SB>) for the layout and
+// the container of a form, yuv_dispatch_taps then with(Int<K>) for its tap count - apart, because a ladder's luma tiles do not depend on K, and a packed picture is K = 1 only.
+template <class With>
+__device__ __forceinline__ void yuv_dispatch(const YuvForm &f, With with)
 {
-	const int left = j.height - y0, pairs = (left < CHUNK_ROWS ? left : CHUNK_ROWS) >> 1, per_row = j.width >> 4;      // (whole spans)
-	for (int i = (int)threadIdx.x; i < pairs * per_row; i += HMR_BLOCK) {
-		const int r = i / per_row, x = (i - r * per_row) << 4, y = y0 + 2 * r;
-		yuv_span<L, SB, K>(j, x, y);
-	}
-	const int tail = (j.width & 15) >> 1;
-	for (int i = (int)threadIdx.x; i < pairs * tail; i += HMR_BLOCK) {
-		const int r = i / tail;
-		yuv_block(j, (j.width & ~15) + 2 * (i - r * tail), y0 + 2 * r);
+	const bool wide = f.sb == 2;
+	switch (f.format) {
+	case HMR_YUV_PLANAR:
+		if (wide) with(Int<YUV_PLANAR>{}, Int<2>{});
+		else with(Int<YUV_PLANAR>{}, Int<1>{});
+		break;
+	case HMR_YUV_SEMIPLANAR:
+		if (wide) with(Int<YUV_SEMI>{}, Int<2>{});
+		else with(Int<YUV_SEMI>{}, Int<1>{});
+		break;
+	default:
+		if (wide) with(Int<YUV_PACKED>{}, Int<2>{});
+		else with(Int<YUV_PACKED>{}, Int<1>{});
+		break;
 	}
 }
-template <int L, int SB>
-__device__ __forceinline__ void yuv_chunk_k(const YuvIngestJob &j, int y0)
+template <int L, class With>
+__device__ __forceinline__ void yuv_dispatch_taps(const YuvForm &f, With with)
 {
-	if (j.f.k == 0) yuv_chunk<L, SB, 0>(j, y0);
-	else if (j.f.k == 1) yuv_chunk<L, SB, 1>(j, y0);
-	else yuv_chunk<L, SB, 2>(j, y0);
+	if (L == YUV_PACKED || f.k == 1) with(Int<1>{});
+	else if (f.k == 0) with(Int<0>{});
+	else with(Int<2>{});
 }
 
 __global__ __launch_bounds__(HMR_BLOCK) void k_ingest_yuv(const YuvIngestJob *jobs)
@@ -514,29 +566,20 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_ingest_yuv(const YuvIngestJob *jo
 	const YuvIngestJob j = jobs[blockIdx.y];
 	const int y0 = (int)blockIdx.x * CHUNK_ROWS;
 	if (y0 >= j.height) return;
-	const bool wide = j.f.sb == 2;
-	switch (j.f.format) {
-	case HMR_YUV_PLANAR:
-		if (wide) yuv_chunk_k<YUV_PLANAR, 2>(j, y0);
-		else yuv_chunk_k<YUV_PLANAR, 1>(j, y0);
-		break;
-	case HMR_YUV_SEMIPLANAR:
-		if (wide) yuv_chunk_k<YUV_SEMI, 2>(j, y0);
-		else yuv_chunk_k<YUV_SEMI, 1>(j, y0);
-		break;
-	default:
-		if (wide) yuv_chunk<YUV_PACKED, 2, 1>(j, y0);
-		else yuv_chunk<YUV_PACKED, 1, 1>(j, y0);
-		break;
-	}
+	yuv_dispatch(j.f, [&](auto layout, auto container) {
+		constexpr int L = decltype(layout)::value, SB = decltype(container)::value;
+		yuv_dispatch_taps<L>(j.f, [&](auto taps) {
+			pair_chunk(j, y0, [&](int x, int y) { yuv_span<L, SB, decltype(taps)::value>(j, x, y); }, [&](int bx, int y) { yuv_block(j, bx, y); });
+		});
+	});
 }
-template <> struct PictureKernel<YuvIngestJob> { static constexpr auto kernel = k_ingest_yuv; static int chunks(const YuvIngestJob &j) { return rgb_chunks(j.height); } };
+template <> struct PictureKernel<YuvIngestJob> { static constexpr auto kernel = k_ingest_yuv; static int chunks(const YuvIngestJob &j) { return pair_chunks(j.height); } };
 
 // ---- downscaling ingest (section 12g) ----
 // k_downscale: 8-bit pictures of one size, area-averaged (scale_area.h) into the int16 planes of a smaller - or equal - size.  1.5 Ws Hs bytes read, 3 Wd Hd written per
 // picture.  blockIdx.y = picture; blockIdx.x = a tile of tile_rows output rows x SCALE_TILE_W output columns of one plane class - the
 // luma tiles first, then the chroma tiles (a chroma tile holds SCALE_TILE_W / 2 columns of U and as many of V, so that NV12's pairs are read once); smaller pictures
-// leave their last blocks empty.  Vertical pass first: a lane takes a span of 16 bytes of the source columns the tile covers and ONE output row, walks that row's source
+// leave their last blocks empty.  Vertical pass first (scale_columns16 with the row policy ScaleBytes): a lane takes a span of 16 bytes of the source columns the tile covers and ONE output row, walks that row's source
 // rows (at most nine) with 16-byte loads at whatever address the pitch gives and keeps the sixteen weighted column sums in 32-bit registers; they go to LDS, a span in
 // SCALE_SPAN_WORDS words (16 and 4 of padding: the eight lanes of a 16-byte LDS store hit eight different quads of banks).  NV12's pairs stay interleaved in LDS - the
 // vertical pass works on bytes - and the horizontal pass picks every second column.  Horizontal pass: a lane per output sample, consecutive lanes consecutive columns,
@@ -630,200 +673,163 @@ __device__ __forceinline__ void scale_finish(const ScaleTile &k, const ScaleAxis
 	}
 }
 
-__global__ __launch_bounds__(HMR_BLOCK) void k_downscale(const ScaleJob *jobs)
+// The vertical pass of a tile (k_downscale, k_rgb_ladder, k_yuv_ladder): every lane of the workgroup comes here, in front of the barrier.  What a source row gives is
+// the kernel's ROW POLICY P: built once a tile from the job, in front of the lane loop, its one function add(j, k, p or cx, sy, w, sums) adds w times the 8-bit samples
+// of source row sy under the lane's columns to the lane's sums - by 16-byte loads where the columns lie inside the row, sample by sample, every sample checked against
+// the width, where they reach past its end.  (The policy multiplies and adds itself: handed back to be weighted here, the samples make a different program.  What a
+// policy copies from a job that is read where it lies - the Y'CbCr form - it copies in its constructor: read in add, the compiler has to read it again in the row's tail,
+// no longer knows the container width the dispatch tested, and k_yuv_ladder grows by 14 KB.)
+// scale_columns16: a lane takes ONE output row and span p of the tile's `streams` x `spans` spans of 16 source columns, walks the row's source rows (at most nine) and
+// keeps the sixteen weighted column sums in 32-bit registers; they go to LDS, a span in SCALE_SPAN_WORDS words.  k_downscale's tiles and the ladders' luma tiles.
+template <class P, class Job>
+__device__ __forceinline__ void scale_columns16(const Job &j, const ScaleTile &k, u32x4 *sums4, int row_words)
 {
-	__shared__ u32x4 sums4[SCALE_LDS_WORDS / 4];
-	__shared__ u32x4 outs4[SCALE_MAX_ROWS * SCALE_TILE_W / 8];
-	uint32_t *sums = (uint32_t *)sums4;
-	const ScaleJob j = jobs[blockIdx.y];
-	const ScaleTile k = scale_tile(j, (int)blockIdx.x, j.format == HMR_GPU_PIC_NV12);
-	if (k.empty) return;
-	const int t = (int)threadIdx.x, total = k.total(), row_words = total * SCALE_SPAN_WORDS;
-	const ScaleAxis ax = j.ax, ay = j.ay;
-
-	// vertical: (output row, span) per lane
-	for (int i = t; i < total * k.ny; i += HMR_BLOCK) {
+	const ScaleAxis ay = j.ay;
+	const P row(j);
+	const int total = k.total();
+	for (int i = (int)threadIdx.x; i < total * k.ny; i += HMR_BLOCK) {
 		const int r = i / total, p = i - r * total;
-		const bool second = p >= k.spans;      // (I420 chroma: the V plane's spans behind the U plane's)
-		const int b = k.b0 + ((second ? p - k.spans : p) << 4);
-		const bytes_in plane = (bytes_in)(k.luma ? j.src[0] : second ? j.src[2] : j.src[1]);
-		const int64_t pitch = k.luma ? j.pitch[0] : second ? j.pitch[2] : j.pitch[1];
 		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
-		uint32_t acc[16];
-#pragma unroll
-		for (int m = 0; m < 16; m++) acc[m] = 0;
-		const bool whole = b + 16 <= k.row_bytes;
-		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
-			const uint32_t w = hmr_scale_weight(ay, y, sy);
-			const bytes_in row = plane + (int64_t)sy * pitch + b;
-			if (whole) {
-				const u32x4 v = load16(row);
-				const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-				for (int m = 0; m < 16; m++) acc[m] += w * ((d[m >> 2] >> (8 * (m & 3))) & 255u);
-			} else {
-#pragma unroll
-				for (int m = 0; m < 16; m++) acc[m] += b + m < k.row_bytes ? w * row[m] : 0u;      // (the row's last bytes: sample by sample)
-			}
-		}
+		uint32_t acc[16] = {};
+		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) row.add(j, k, p, sy, hmr_scale_weight(ay, y, sy), acc);
 		u32x4 *o = &sums4[(r * row_words + p * SCALE_SPAN_WORDS) >> 2];
 #pragma unroll
 		for (int m = 0; m < 4; m++) o[m] = u32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
 	}
-	__syncthreads();
+}
+// scale_columns8x2, the ladders' chroma tiles: a lane takes ONE chroma output row and a span of EIGHT columns of the converted 4:2:0 chroma planes (k.row_bytes wide) and accumulates U and V apart; its
+// sixteen sums are half a span of the U stream and half a span of the V stream (two 16-byte LDS stores each: eight lanes of such a store hit six different quads of
+// banks, two of them twice).  Sixteen chroma columns a lane would hold 32 sums beside the source rows under them: eight keeps every form free of spills.
+template <class P, class Job>
+__device__ __forceinline__ void scale_columns8x2(const Job &j, const ScaleTile &k, u32x4 *sums4, int row_words)
+{
+	const ScaleAxis ay = j.ay;
+	const P row(j);
+	const int halves = 2 * k.spans;
+	for (int i = (int)threadIdx.x; i < halves * k.ny; i += HMR_BLOCK) {
+		const int r = i / halves, q = i - r * halves, cx = k.c0 + (q << 3);
+		if (cx >= k.row_bytes) continue;      // (the second half of the last span may lie beyond the plane: no tap reads its sums)
+		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
+		uint32_t au[8] = {}, av[8] = {};
+		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) row.add(j, k, cx, sy, hmr_scale_weight(ay, y, sy), au, av);
+		u32x4 *o = &sums4[(r * row_words + scale_word(q << 3)) >> 2];
+		o[0] = u32x4{au[0], au[1], au[2], au[3]}; o[1] = u32x4{au[4], au[5], au[6], au[7]};
+		o += (k.spans * SCALE_SPAN_WORDS) >> 2;      // (the V stream lies behind the U stream)
+		o[0] = u32x4{av[0], av[1], av[2], av[3]}; o[1] = u32x4{av[4], av[5], av[6], av[7]};
+	}
+}
 
-	scale_finish(k, ax, j.den, j.mden, sums, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
+// k_downscale's source row (scale_columns16): the sixteen bytes of span p of the tile's window themselves; I420 chroma: the V plane's spans behind the U plane's
+struct ScaleBytes {
+	__device__ __forceinline__ ScaleBytes(const ScaleJob &) {}
+	__device__ __forceinline__ void add(const ScaleJob &j, const ScaleTile &k, int p, uint32_t sy, uint32_t w, uint32_t *acc) const
+	{
+		const bool second = p >= k.spans;
+		const int b = k.b0 + ((second ? p - k.spans : p) << 4);
+		const bytes_in row = (bytes_in)(k.luma ? j.src[0] : second ? j.src[2] : j.src[1]) + (int64_t)sy * (k.luma ? j.pitch[0] : second ? j.pitch[2] : j.pitch[1]) + b;
+		if (b + 16 <= k.row_bytes) {
+			const u32x4 v4 = load16(row);
+			const uint32_t d[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+			for (int m = 0; m < 16; m++) acc[m] += w * ((d[m >> 2] >> (8 * (m & 3))) & 255u);
+		} else {
+#pragma unroll
+			for (int m = 0; m < 16; m++) acc[m] += b + m < k.row_bytes ? w * row[m] : 0u;      // (the row's last bytes: sample by sample)
+		}
+	}
+};
+
+__global__ __launch_bounds__(HMR_BLOCK) void k_downscale(const ScaleJob *jobs)
+{
+	__shared__ u32x4 sums4[SCALE_LDS_WORDS / 4];
+	__shared__ u32x4 outs4[SCALE_MAX_ROWS * SCALE_TILE_W / 8];
+	// (read where it lies, as the ladders': of a copy, ScaleBytes' choice of a plane by the lane's stream goes through private memory)
+	const ScaleJob &j = jobs[blockIdx.y];
+	const ScaleTile k = scale_tile(j, (int)blockIdx.x, j.format == HMR_GPU_PIC_NV12);
+	if (k.empty) return;
+	const int row_words = k.total() * SCALE_SPAN_WORDS;
+	scale_columns16<ScaleBytes>(j, k, sums4, row_words);
+	__syncthreads();
+	scale_finish(k, j.ax, j.den, j.mden, (const uint32_t *)sums4, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
 }
 template <> struct PictureKernel<ScaleJob> { static constexpr auto kernel = k_downscale; static int chunks(const ScaleJob &j) { return scale_tiles(j); } };
 
 // ---- downscaling RGB ingest (section 12j) ----
 // k_rgb_ladder: RGB pictures of one size, in any of k_ingest_rgb's forms, into the int16 planes of a smaller - or equal - size: every slot sample is section 12g's
 // area average of the 8-bit 4:2:0 picture section 12f makes of the source, and that picture never exists in memory.  12f's luma is a function of one pixel and its
-// chroma of one 2 x 2 block, so a lane converts what it has loaded in registers (rgb_load_row, rgb_pixel, hmr_rgb_luma, hmr_rgb_chroma) and accumulates the weighted
-// 8-bit results: the column sums are k_downscale's, bit for bit, and so are the tiles, the LDS layout, the horizontal pass and the stores (scale_tile, scale_finish).
-// Luma tile: a lane takes ONE output row and a span of 16 source pixels, and walks the row's source rows (at most nine); per source row the loads of k_ingest_rgb's
-// form (binary32: two halves of eight pixels), sixteen luma samples, sixteen multiply-adds.  Chroma tile: a lane takes ONE chroma output row and a span of EIGHT
-// source chroma columns - sixteen pixels, so a source chroma row costs the loads of a luma lane twice (the two pixel rows under it) - forms the eight 2 x 2 sums and
-// accumulates U and V apart; its sixteen sums are half a span of the U stream and half a span of the V stream (two 16-byte LDS stores each: eight lanes of such a
-// store hit six different quads of banks, two of them twice).  Sixteen chroma columns a lane would hold 32 sums beside two rows of 32 pixels: eight keeps every form
-// free of spills.  A span that reaches past the end of a row goes sample by sample (rgb_sample), every sample checked against the width.
+// chroma of one 2 x 2 block, so a lane converts what it has loaded in registers with k_ingest_rgb's own pieces (rgb_load_row, rgb_pixel, rgb_two_rows, rgb_quad; the
+// rows' tails by rgb_sample3) and accumulates the weighted 8-bit results: the column sums are k_downscale's, bit for bit, and so are the tiles, the vertical pass, the
+// LDS layout, the horizontal pass and the stores (scale_tile, scale_columns16 / scale_columns8x2, scale_finish).  What the kernel adds are the two row policies below.
+// Per source row a luma lane issues the loads of k_ingest_rgb's form (binary32: two halves of eight pixels) and sixteen multiply-adds; a chroma lane's eight columns are
+// sixteen pixels of two pixel rows: the loads of a luma lane twice.
 // Luma and chroma tiles each read the RGB source: 2 x (3, 4, 3, 6 or 12) Ws Hs bytes read, 3 Wd Hd written per picture.  No lane
 // reads a byte outside [plane + y * pitch, plane + y * pitch + row bytes) or writes outside dst_w x dst_h.  The weighted sums fit 32 bits as section 12g's do: the
 // converted samples are 8-bit.  LDS: k_downscale's.
-template <int FMT>
-__device__ __forceinline__ void ladder_sample(const RgbScaleJob &j, int px, int py, int &r, int &g, int &b)
-{
-	constexpr bool packed = FMT == HMR_GPU_RGB_PACKED8;
-	r = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[0], j.pitch[0], FMT, j.pixel_bytes, j.offset[0], px, py);
-	g = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[packed ? 0 : 1], j.pitch[packed ? 0 : 1], FMT, j.pixel_bytes, j.offset[1], px, py);
-	b = rgb_sample<bytes_in, GLOBAL_AS const _Float16 *, GLOBAL_AS const float *>((bytes_in)j.src[packed ? 0 : 2], j.pitch[packed ? 0 : 2], FMT, j.pixel_bytes, j.offset[2], px, py);
-}
-
-// the weighted column sums of a luma tile: (output row, span of 16 source pixels) per lane
-template <int V, int FMT>
-__device__ __forceinline__ void ladder_luma(const RgbScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
-{
-	typedef RgbForm<V> F;
-	const int sh[3] = {8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]};
-	const ScaleAxis ay = j.ay;
-	for (int i = (int)threadIdx.x; i < k.spans * k.ny; i += HMR_BLOCK) {
-		const int r = i / k.spans, p = i - r * k.spans, x = k.c0 + (p << 4);
-		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
-		uint32_t acc[16];
+// a luma tile's source row (scale_columns16): the luma of the 16 pixels at (x, sy)
+template <int V> struct RgbLadderLuma {
+	const int sh[3];
+	__device__ __forceinline__ RgbLadderLuma(const RgbScaleJob &j) : sh{8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]} {}
+	__device__ __forceinline__ void add(const RgbScaleJob &j, const ScaleTile &k, int p, uint32_t sy, uint32_t w, uint32_t *acc) const
+	{
+		const int x = k.c0 + (p << 4);
+		typedef RgbForm<V> F;
+		if (x + 16 <= j.src_w) {
 #pragma unroll
-		for (int m = 0; m < 16; m++) acc[m] = 0;
-		const bool whole = x + 16 <= j.src_w;
-		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
-			const uint32_t w = hmr_scale_weight(ay, y, sy);
-			if (whole) {
+			for (int h = 0; h < 16 / F::PX; h++) {
+				uint32_t raw[F::WORDS];
+				rgb_load_row<V>(j, x + F::PX * h, (int)sy, raw);
 #pragma unroll
-				for (int h = 0; h < 16 / F::PX; h++) {
-					uint32_t raw[F::WORDS];
-					rgb_load_row<V>(j, x + F::PX * h, (int)sy, raw);
-#pragma unroll
-					for (int m = 0; m < F::PX; m++) {
-						int cr, cg, cb;
-						rgb_pixel<V>(raw, m, sh, cr, cg, cb);
-						acc[F::PX * h + m] += w * (uint32_t)hmr_rgb_luma(j.m, cr, cg, cb);
-					}
-				}
-			} else {
-#pragma unroll
-				for (int m = 0; m < 16; m++) {      // (the row's last pixels: sample by sample)
-					if (x + m >= j.src_w) continue;
+				for (int m = 0; m < F::PX; m++) {
 					int cr, cg, cb;
-					ladder_sample<FMT>(j, x + m, (int)sy, cr, cg, cb);
-					acc[m] += w * (uint32_t)hmr_rgb_luma(j.m, cr, cg, cb);
+					rgb_pixel<V>(raw, m, sh, cr, cg, cb);
+					acc[F::PX * h + m] += w * (uint32_t)hmr_rgb_luma(j.m, cr, cg, cb);
 				}
 			}
+			return;
 		}
-		u32x4 *o = &sums4[(r * row_words + p * SCALE_SPAN_WORDS) >> 2];
 #pragma unroll
-		for (int m = 0; m < 4; m++) o[m] = u32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
+		for (int m = 0; m < 16; m++) {      // (the row's last pixels)
+			if (x + m >= j.src_w) continue;
+			int c3[3];
+			rgb_sample3<F::FMT>(j, x + m, (int)sy, c3);
+			acc[m] += w * (uint32_t)hmr_rgb_luma(j.m, c3[0], c3[1], c3[2]);
+		}
 	}
-}
-
-// four chroma columns from pixels i0 .. i0 + 7 of the two pixel rows a, b, weighted into au, av
-template <int V>
-__device__ __forceinline__ void ladder_chroma4(const uint32_t *a, const uint32_t *b, int i0, const RgbMatrix &m, const int sh[3], uint32_t w, uint32_t *au, uint32_t *av)
-{
+};
+// a chroma tile's source row (scale_columns8x2): U and V of the eight 2 x 2 blocks at chroma (cx, sy) - sixteen pixels of two pixel rows, the loads of a luma lane twice
+template <int V> struct RgbLadderChroma {
+	const int sh[3];
+	__device__ __forceinline__ RgbLadderChroma(const RgbScaleJob &j) : sh{8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]} {}
+	__device__ __forceinline__ void add(const RgbScaleJob &j, const ScaleTile &k, int cx, uint32_t sy, uint32_t w, uint32_t *au, uint32_t *av) const
+	{
+		const int py = 2 * (int)sy, cw = k.row_bytes;      // (the source's chroma width)
+		if (cx + 8 <= cw) {
+			rgb_two_rows<V>(j, 2 * cx, py, [&](int h, const uint32_t *a, const uint32_t *b, int i0) {
 #pragma unroll
-	for (int p = 0; p < 4; p++) {
-		int r0, g0, b0, r1, g1, b1, r2, g2, b2, r3, g3, b3;
-		rgb_pixel<V>(a, i0 + 2 * p, sh, r0, g0, b0);
-		rgb_pixel<V>(a, i0 + 2 * p + 1, sh, r1, g1, b1);
-		rgb_pixel<V>(b, i0 + 2 * p, sh, r2, g2, b2);
-		rgb_pixel<V>(b, i0 + 2 * p + 1, sh, r3, g3, b3);
-		const int sr = r0 + r1 + r2 + r3, sg = g0 + g1 + g2 + g3, sb = b0 + b1 + b2 + b3;
-		au[p] += w * (uint32_t)hmr_rgb_chroma(m.u, sr, sg, sb);
-		av[p] += w * (uint32_t)hmr_rgb_chroma(m.v, sr, sg, sb);
-	}
-}
-
-// the weighted column sums of a chroma tile: (chroma output row, span of 8 source chroma columns) per lane; the U sums to the first stream, the V sums to the second
-template <int V, int FMT>
-__device__ __forceinline__ void ladder_chroma(const RgbScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
-{
-	typedef RgbForm<V> F;
-	const int sh[3] = {8 * j.offset[0], 8 * j.offset[1], 8 * j.offset[2]};
-	const ScaleAxis ay = j.ay;
-	const int halves = 2 * k.spans, cw = k.row_bytes;      // (the source's chroma width)
-	for (int i = (int)threadIdx.x; i < halves * k.ny; i += HMR_BLOCK) {
-		const int r = i / halves, q = i - r * halves, cx = k.c0 + (q << 3);
-		if (cx >= cw) continue;      // (the second half of the last span may lie beyond the plane: no tap reads its sums)
-		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
-		uint32_t au[8], av[8];
-#pragma unroll
-		for (int m = 0; m < 8; m++) au[m] = av[m] = 0;
-		const bool whole = cx + 8 <= cw;
-		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
-			const uint32_t w = hmr_scale_weight(ay, y, sy);
-			const int py = 2 * (int)sy;
-			if (whole) {
-				if (F::PX == 8) {
-#pragma unroll
-					for (int h = 0; h < 2; h++) {
-						uint32_t a[F::WORDS], b[F::WORDS];
-						rgb_load_row<V>(j, 2 * cx + 8 * h, py, a);
-						rgb_load_row<V>(j, 2 * cx + 8 * h, py + 1, b);
-						ladder_chroma4<V>(a, b, 0, j.m, sh, w, au + 4 * h, av + 4 * h);
-					}
-				} else {
-					uint32_t a[F::WORDS], b[F::WORDS];
-					rgb_load_row<V>(j, 2 * cx, py, a);
-					rgb_load_row<V>(j, 2 * cx, py + 1, b);
-#pragma unroll
-					for (int h = 0; h < 2; h++) ladder_chroma4<V>(a, b, 8 * h, j.m, sh, w, au + 4 * h, av + 4 * h);
+				for (int p = 0; p < 4; p++) {
+					int px[4][3], s[3];
+					rgb_quad<V>(a, b, i0 + 2 * p, sh, px, s);
+					au[4 * h + p] += w * (uint32_t)hmr_rgb_chroma(j.m.u, s[0], s[1], s[2]);
+					av[4 * h + p] += w * (uint32_t)hmr_rgb_chroma(j.m.v, s[0], s[1], s[2]);
 				}
-			} else {
+			});
+			return;
+		}
 #pragma unroll
-				for (int m = 0; m < 8; m++) {      // (the row's last blocks: sample by sample)
-					if (cx + m >= cw) continue;
-					int sr = 0, sg = 0, sb = 0;
+		for (int m = 0; m < 8; m++) {      // (the row's last blocks)
+			if (cx + m >= cw) continue;
+			int s[3] = {0, 0, 0};
 #pragma unroll
-					for (int c = 0; c < 4; c++) {
-						int cr, cg, cb;
-						ladder_sample<FMT>(j, 2 * (cx + m) + (c & 1), py + (c >> 1), cr, cg, cb);
-						sr += cr; sg += cg; sb += cb;
-					}
-					au[m] += w * (uint32_t)hmr_rgb_chroma(j.m.u, sr, sg, sb);
-					av[m] += w * (uint32_t)hmr_rgb_chroma(j.m.v, sr, sg, sb);
-				}
+			for (int c = 0; c < 4; c++) {
+				int c3[3];
+				rgb_sample3<RgbForm<V>::FMT>(j, 2 * (cx + m) + (c & 1), py + (c >> 1), c3);
+				s[0] += c3[0]; s[1] += c3[1]; s[2] += c3[2];
 			}
+			au[m] += w * (uint32_t)hmr_rgb_chroma(j.m.u, s[0], s[1], s[2]);
+			av[m] += w * (uint32_t)hmr_rgb_chroma(j.m.v, s[0], s[1], s[2]);
 		}
-		u32x4 *o = &sums4[(r * row_words + scale_word(q << 3)) >> 2];
-		o[0] = u32x4{au[0], au[1], au[2], au[3]}; o[1] = u32x4{au[4], au[5], au[6], au[7]};
-		o += (k.spans * SCALE_SPAN_WORDS) >> 2;
-		o[0] = u32x4{av[0], av[1], av[2], av[3]}; o[1] = u32x4{av[4], av[5], av[6], av[7]};
 	}
-}
-
-template <int V, int FMT>
-__device__ __forceinline__ void ladder_vertical(const RgbScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
-{
-	if (k.luma) ladder_luma<V, FMT>(j, k, sums4, row_words);
-	else ladder_chroma<V, FMT>(j, k, sums4, row_words);
-}
+};
 
 __global__ __launch_bounds__(HMR_BLOCK) void k_rgb_ladder(const RgbScaleJob *jobs)
 {
@@ -833,13 +839,11 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_rgb_ladder(const RgbScaleJob *job
 	const ScaleTile k = scale_tile(j, (int)blockIdx.x, false);
 	if (k.empty) return;
 	const int row_words = k.total() * SCALE_SPAN_WORDS;
-	switch (rgb_form(j.format, j.pixel_bytes)) {
-	case RGB_PACKED3: ladder_vertical<RGB_PACKED3, HMR_GPU_RGB_PACKED8>(j, k, sums4, row_words); break;
-	case RGB_PACKED4: ladder_vertical<RGB_PACKED4, HMR_GPU_RGB_PACKED8>(j, k, sums4, row_words); break;
-	case RGB_PLANAR8: ladder_vertical<RGB_PLANAR8, HMR_GPU_RGB_PLANAR8>(j, k, sums4, row_words); break;
-	case RGB_F16: ladder_vertical<RGB_F16, HMR_GPU_RGB_PLANAR_F16>(j, k, sums4, row_words); break;
-	default: ladder_vertical<RGB_F32, HMR_GPU_RGB_PLANAR_F32>(j, k, sums4, row_words); break;
-	}
+	rgb_dispatch(j, [&](auto form) {
+		constexpr int V = decltype(form)::value;
+		if (k.luma) scale_columns16<RgbLadderLuma<V>>(j, k, sums4, row_words);
+		else scale_columns8x2<RgbLadderChroma<V>>(j, k, sums4, row_words);
+	});
 	__syncthreads();
 	scale_finish(k, j.ax, j.den, j.mden, (const uint32_t *)sums4, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
 }
@@ -848,145 +852,75 @@ template <> struct PictureKernel<RgbScaleJob> { static constexpr auto kernel = k
 // ---- downscaling deep / 4:2:2 / 4:4:4 ingest (section 12l) ----
 // k_yuv_ladder: Y'CbCr pictures of one size, in any of k_ingest_yuv's forms, into the int16 planes of a smaller - or equal - size: every slot sample is section 12g's
 // area average of the 8-bit 4:2:0 picture section 12k makes of the source, and that picture never exists in memory.  12k's luma is a function of one container and its
-// chroma of 1, 2 or 4 containers of one plane, so a lane rounds what it has loaded in registers (yuv_load, yuv_pick, hmr_yuv_value, hmr_yuv_round) and accumulates the
-// weighted 8-bit results: the column sums are k_downscale's, bit for bit, and so are the tiles, the LDS layout, the horizontal pass and the stores (scale_tile with a
-// chroma tile's columns those of the converted 4:2:0 chroma planes, scale_finish).
-// Luma tile: a lane takes ONE output row and a span of 16 source pixels, and walks the row's source rows (at most nine); per source row the loads k_ingest_yuv issues
-// for the layout and the container (16 bytes for 8-bit planes, 32 for 16-bit planes or 8-bit packed, 64 for 16-bit packed), sixteen 8-bit samples (8-bit planes: the
-// bytes themselves), sixteen multiply-adds.  Chroma tile: a lane takes ONE chroma output row and a span of EIGHT converted chroma columns (ladder_chroma's choice:
-// sixteen would hold 32 sums); per converted chroma row it reads one (4:2:0) or two source chroma rows, 8 (4:2:0, 4:2:2) or 16 (4:4:4) columns of U and of V, forms
-// the eight tap sums, rounds them with s + K exactly as yuv_span does and accumulates U and V apart into the two streams of the tile row (two 16-byte LDS stores each).
-// A span that reaches past the end of a row goes sample by sample through yuv_depth.h's own hmr_yuv_luma / hmr_yuv_chroma - the ones the host twin runs - every sample
-// checked against the width.  The vertical pass is specialised as k_ingest_yuv is, on the layout, the container's width and the tap count (14 classes, picked per
-// job: a launch mixes forms; luma does not depend on the taps).
+// chroma of 1, 2 or 4 containers of one plane, so a lane rounds what it has loaded in registers (yuv_load, yuv_pick, hmr_yuv_value, hmr_yuv_round; the chroma taps by
+// k_ingest_yuv's own yuv_taps_packed / yuv_taps_planes) and accumulates the weighted 8-bit results: the column sums are k_downscale's, bit for bit, and so are the tiles,
+// the vertical pass, the LDS layout, the horizontal pass and the stores (scale_tile with a chroma tile's columns those of the converted 4:2:0 chroma planes,
+// scale_columns16 / scale_columns8x2, scale_finish).  What the kernel adds are the two row policies below.
+// Per source row a luma lane issues the loads k_ingest_yuv issues for the layout and the container (16 bytes for 8-bit planes, 32 for 16-bit planes or 8-bit packed, 64
+// for 16-bit packed) and sixteen multiply-adds; a chroma lane reads, per converted chroma row, one (4:2:0) or two source chroma rows, 8 (4:2:0, 4:2:2) or 16 (4:4:4)
+// columns of U and of V.  The rows' tails go through yuv_depth.h's own hmr_yuv_luma / hmr_yuv_chroma - the ones the host twin runs.  The policies are specialised as
+// k_ingest_yuv is, through the same yuv_dispatch (14 classes, picked per job: a launch mixes forms; luma does not depend on the taps).
 // Planar and semi-planar sources are read once - luma tiles read the luma plane, chroma tiles the chroma planes: sb (Ws Hs + 2 Wc Hc) bytes read, 3 Wd Hd written per
 // picture; a packed source's single plane is read by both tile classes: 2 x 2 sb Ws Hs read.  No lane reads a byte outside [plane + y * pitch, plane + y * pitch +
 // row bytes) or writes outside dst_w x dst_h.  The weighted sums fit 32 bits as section 12g's do: the converted samples are 8-bit.  No atomics.  LDS: k_downscale's.
-
-// the weighted column sums of a luma tile: (output row, span of 16 source pixels) per lane
-template <int L, int SB>
-__device__ __forceinline__ void yuv_ladder_luma(const YuvScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
-{
-	typedef YuvSpan<L, SB, 0> F;
-	const YuvForm f = j.f;
-	const int bits0 = 8 * SB * f.offset[0], src_w = j.src_w;
-	const ScaleAxis ay = j.ay;
-	const bytes_in plane = (bytes_in)j.src[0];
-	const int64_t pitch = j.pitch[0];
-	for (int i = (int)threadIdx.x; i < k.spans * k.ny; i += HMR_BLOCK) {
-		const int r = i / k.spans, p = i - r * k.spans, x = k.c0 + (p << 4);
-		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
-		uint32_t acc[16];
+// a luma tile's source row (scale_columns16): the 16 rounded samples at (x, sy); as 32-bit values for the multiply-adds, where yuv_span packs int16 pairs for its stores
+template <int L, int SB> struct YuvLadderLuma {
+	const YuvForm f;
+	__device__ __forceinline__ YuvLadderLuma(const YuvScaleJob &j) : f(j.f) {}
+	__device__ __forceinline__ void add(const YuvScaleJob &j, const ScaleTile &k, int p, uint32_t sy, uint32_t w, uint32_t *acc) const
+	{
+		const int x = k.c0 + (p << 4);
+		typedef YuvSpan<L, SB, 0> F;
+		const int bits0 = 8 * SB * f.offset[0];
+		if (x + 16 <= j.src_w) {
+			uint32_t la[F::LUMA_BYTES / 4];
+			yuv_load<F::LUMA_BYTES>((bytes_in)j.src[0] + (int64_t)sy * j.pitch[0] + (int64_t)x * (L == YUV_PACKED ? 2 : 1) * SB, la);
 #pragma unroll
-		for (int m = 0; m < 16; m++) acc[m] = 0;
-		const bool whole = x + 16 <= src_w;
-		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
-			const uint32_t w = hmr_scale_weight(ay, y, sy);
-			if (whole) {
-				uint32_t la[F::LUMA_BYTES / 4];
-				yuv_load<F::LUMA_BYTES>(plane + (int64_t)sy * pitch + (int64_t)x * (L == YUV_PACKED ? 2 : 1) * SB, la);
+			for (int m = 0; m < 16; m++) {
+				const uint32_t raw = L == YUV_PACKED ? yuv_pick<SB, 2>(la, m, bits0) : yuv_pick<SB, 1>(la, m, 0);
+				acc[m] += w * (SB == 1 ? raw : hmr_yuv_round(hmr_yuv_value(f, raw), f.s));      // (8 bits: the sample itself)
+			}
+			return;
+		}
 #pragma unroll
-				for (int m = 0; m < 16; m++) {
-					const uint32_t raw = L == YUV_PACKED ? yuv_pick<SB, 2>(la, m, bits0) : yuv_pick<SB, 1>(la, m, 0);
-					acc[m] += w * (SB == 1 ? raw : hmr_yuv_round(hmr_yuv_value(f, raw), f.s));      // (8 bits: the sample itself)
+		for (int m = 0; m < 16; m++)      // (the row's last pixels: yuv_depth.h's own function - the one the host twin runs)
+			if (x + m < j.src_w) acc[m] += w * hmr_yuv_luma<bytes_in>(j.src, j.pitch, f, x + m, (int)sy);
+	}
+};
+// a chroma tile's source row (scale_columns8x2): U and V of the eight converted chroma columns at (cx, sy), the tap sums rounded with s + K exactly as yuv_span rounds them
+template <int L, int SB, int K> struct YuvLadderChroma {
+	const YuvForm f;
+	__device__ __forceinline__ YuvLadderChroma(const YuvScaleJob &j) : f(j.f) {}
+	__device__ __forceinline__ void add(const YuvScaleJob &j, const ScaleTile &k, int cx, uint32_t sy, uint32_t w, uint32_t *au, uint32_t *av) const
+	{
+		typedef YuvSpan<L, SB, K> F;
+		const int cw = k.row_bytes;      // (the converted chroma width: src_w / 2)
+		if (cx + 8 <= cw) {
+			uint32_t su[8] = {}, sv[8] = {};
+			if (L == YUV_PACKED) {
+#pragma unroll
+				for (int r = 0; r < 2; r++) {
+					uint32_t g[F::LUMA_BYTES / 4];
+					yuv_load<F::LUMA_BYTES>((bytes_in)j.src[0] + (int64_t)(2 * (int)sy + r) * j.pitch[0] + (int64_t)cx * 4 * SB, g);
+					yuv_taps_packed<SB>(f, g, su, sv);
 				}
-			} else {
+			} else yuv_taps_planes<L, SB, K>(j, cx, (int)sy, su, sv);
+			const int t = f.s + K;
 #pragma unroll
-				for (int m = 0; m < 16; m++)      // (the row's last pixels: sample by sample)
-					if (x + m < src_w) acc[m] += w * hmr_yuv_luma<bytes_in>(j.src, j.pitch, f, x + m, (int)sy);
+			for (int c = 0; c < 8; c++) {
+				au[c] += w * hmr_yuv_round(su[c], t);
+				av[c] += w * hmr_yuv_round(sv[c], t);
+			}
+		} else {
+#pragma unroll
+			for (int m = 0; m < 8; m++) {      // (the row's last columns: yuv_depth.h's own function)
+				if (cx + m >= cw) continue;
+				au[m] += w * hmr_yuv_chroma<bytes_in>(j.src, j.pitch, f, 1, cx + m, (int)sy);
+				av[m] += w * hmr_yuv_chroma<bytes_in>(j.src, j.pitch, f, 2, cx + m, (int)sy);
 			}
 		}
-		u32x4 *o = &sums4[(r * row_words + p * SCALE_SPAN_WORDS) >> 2];
-#pragma unroll
-		for (int m = 0; m < 4; m++) o[m] = u32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
 	}
-}
-
-// the weighted column sums of a chroma tile: (chroma output row, span of 8 converted chroma columns) per lane; the U sums to the first stream, the V sums to the second
-template <int L, int SB, int K>
-__device__ __forceinline__ void yuv_ladder_chroma(const YuvScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
-{
-	typedef YuvSpan<L, SB, K> F;
-	const YuvForm f = j.f;
-	const int bits1 = 8 * SB * f.offset[1], bits2 = 8 * SB * f.offset[2], t = f.s + K;
-	const ScaleAxis ay = j.ay;
-	const bytes_in first = (bytes_in)j.src[L == YUV_PACKED ? 0 : 1], second = (bytes_in)j.src[L == YUV_PLANAR ? 2 : L == YUV_SEMI ? 1 : 0];
-	const int64_t pitch1 = j.pitch[L == YUV_PACKED ? 0 : 1], pitch2 = j.pitch[L == YUV_PLANAR ? 2 : L == YUV_SEMI ? 1 : 0];
-	const int halves = 2 * k.spans, cw = k.row_bytes;      // (the converted chroma width: src_w / 2)
-	for (int i = (int)threadIdx.x; i < halves * k.ny; i += HMR_BLOCK) {
-		const int r = i / halves, q = i - r * halves, cx = k.c0 + (q << 3);
-		if (cx >= cw) continue;      // (the second half of the last span may lie beyond the plane: no tap reads its sums)
-		const uint32_t y = (uint32_t)(k.y0 + r), hi = (y + 1) * ay.s;
-		uint32_t au[8], av[8];
-#pragma unroll
-		for (int m = 0; m < 8; m++) au[m] = av[m] = 0;
-		const bool whole = cx + 8 <= cw;
-		for (uint32_t sy = hmr_scale_first(ay, y); sy * ay.d < hi; sy++) {
-			const uint32_t w = hmr_scale_weight(ay, y, sy);
-			if (whole) {
-				uint32_t su[8], sv[8];
-#pragma unroll
-				for (int c = 0; c < 8; c++) su[c] = sv[c] = 0;
-				if (L == YUV_PACKED) {      // group c of a row holds chroma column c: 8 groups are 16 pixels
-#pragma unroll
-					for (int rr = 0; rr < 2; rr++) {
-						uint32_t g[F::LUMA_BYTES / 4];
-						yuv_load<F::LUMA_BYTES>(first + (int64_t)(2 * (int)sy + rr) * pitch1 + (int64_t)cx * 4 * SB, g);
-#pragma unroll
-						for (int c = 0; c < 8; c++) {
-							const uint32_t u = yuv_pick<SB, 4>(g, c, bits1), v = yuv_pick<SB, 4>(g, c, bits2);
-							su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
-							sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
-						}
-					}
-				} else {
-					const int row0 = K == 0 ? (int)sy : 2 * (int)sy, col0 = K == 2 ? 2 * cx : cx;
-#pragma unroll
-					for (int rr = 0; rr < F::ROWS; rr++) {
-						uint32_t cu[F::CHROMA_BYTES / 4], cv[F::CHROMA_BYTES / 4];
-						yuv_load<F::CHROMA_BYTES>(first + (int64_t)(row0 + rr) * pitch1 + (int64_t)col0 * SB * (L == YUV_SEMI ? 2 : 1), cu);
-						if (L == YUV_PLANAR) yuv_load<F::CHROMA_BYTES>(second + (int64_t)(row0 + rr) * pitch2 + (int64_t)col0 * SB, cv);
-#pragma unroll
-						for (int c = 0; c < 8; c++)
-#pragma unroll
-							for (int tap = 0; tap < F::TAPS; tap++) {
-								const int n = c * F::TAPS + tap;
-								const uint32_t u = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, n, bits1) : yuv_pick<SB, 1>(cu, n, 0);
-								const uint32_t v = L == YUV_SEMI ? yuv_pick<SB, 2>(cu, n, bits2) : yuv_pick<SB, 1>(cv, n, 0);
-								su[c] += SB == 1 ? u : hmr_yuv_value(f, u);
-								sv[c] += SB == 1 ? v : hmr_yuv_value(f, v);
-							}
-					}
-				}
-#pragma unroll
-				for (int c = 0; c < 8; c++) {      // (8 bits: s = 0, maxv = 255, rs = 0 - hmr_yuv_value is the identity and was left out above)
-					au[c] += w * hmr_yuv_round(su[c], t);
-					av[c] += w * hmr_yuv_round(sv[c], t);
-				}
-			} else {
-#pragma unroll
-				for (int m = 0; m < 8; m++) {      // (the row's last columns: sample by sample)
-					if (cx + m >= cw) continue;
-					au[m] += w * hmr_yuv_chroma<bytes_in>(j.src, j.pitch, f, 1, cx + m, (int)sy);
-					av[m] += w * hmr_yuv_chroma<bytes_in>(j.src, j.pitch, f, 2, cx + m, (int)sy);
-				}
-			}
-		}
-		u32x4 *o = &sums4[(r * row_words + scale_word(q << 3)) >> 2];
-		o[0] = u32x4{au[0], au[1], au[2], au[3]}; o[1] = u32x4{au[4], au[5], au[6], au[7]};
-		o += (k.spans * SCALE_SPAN_WORDS) >> 2;
-		o[0] = u32x4{av[0], av[1], av[2], av[3]}; o[1] = u32x4{av[4], av[5], av[6], av[7]};
-	}
-}
-
-template <int L, int SB>
-__device__ __forceinline__ void yuv_ladder_vertical(const YuvScaleJob &j, const ScaleTile &k, u32x4 *sums4, int row_words)
-{
-	if (k.luma) yuv_ladder_luma<L, SB>(j, k, sums4, row_words);
-	else if (L == YUV_PACKED || j.f.k == 1) yuv_ladder_chroma<L, SB, 1>(j, k, sums4, row_words);
-	else if (j.f.k == 0) yuv_ladder_chroma<L, SB, 0>(j, k, sums4, row_words);
-	else yuv_ladder_chroma<L, SB, 2>(j, k, sums4, row_words);
-}
+};
 
 __global__ __launch_bounds__(HMR_BLOCK) void k_yuv_ladder(const YuvScaleJob *jobs)
 {
@@ -996,21 +930,11 @@ __global__ __launch_bounds__(HMR_BLOCK) void k_yuv_ladder(const YuvScaleJob *job
 	const ScaleTile k = scale_tile(j, (int)blockIdx.x, false);
 	if (k.empty) return;
 	const int row_words = k.total() * SCALE_SPAN_WORDS;
-	const bool wide = j.f.sb == 2;
-	switch (j.f.format) {
-	case HMR_YUV_PLANAR:
-		if (wide) yuv_ladder_vertical<YUV_PLANAR, 2>(j, k, sums4, row_words);
-		else yuv_ladder_vertical<YUV_PLANAR, 1>(j, k, sums4, row_words);
-		break;
-	case HMR_YUV_SEMIPLANAR:
-		if (wide) yuv_ladder_vertical<YUV_SEMI, 2>(j, k, sums4, row_words);
-		else yuv_ladder_vertical<YUV_SEMI, 1>(j, k, sums4, row_words);
-		break;
-	default:
-		if (wide) yuv_ladder_vertical<YUV_PACKED, 2>(j, k, sums4, row_words);
-		else yuv_ladder_vertical<YUV_PACKED, 1>(j, k, sums4, row_words);
-		break;
-	}
+	yuv_dispatch(j.f, [&](auto layout, auto container) {
+		constexpr int L = decltype(layout)::value, SB = decltype(container)::value;
+		if (k.luma) scale_columns16<YuvLadderLuma<L, SB>>(j, k, sums4, row_words);
+		else yuv_dispatch_taps<L>(j.f, [&](auto taps) { scale_columns8x2<YuvLadderChroma<L, SB, decltype(taps)::value>>(j, k, sums4, row_words); });
+	});
 	__syncthreads();
 	scale_finish(k, j.ax, j.den, j.mden, (const uint32_t *)sums4, outs4, row_words, j.dst[0], j.dst[1], j.dst[2], j.stride_y, j.stride_c);
 }

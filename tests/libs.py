@@ -1,7 +1,8 @@
-"""Locate / build / load the three shared libraries the tests talk to (ctypes)."""
+"""Locate / build / load the three shared libraries the tests talk to (ctypes), and the one device-only compile the as-compiled tests of the picture kernels share."""
 import ctypes
 import os
 import subprocess
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -33,6 +34,21 @@ def load_ref():
                 lib = None
         _cache["ref"] = lib
     return _cache["ref"]
+
+
+def picture_io_as_compiled():
+    """(the compiler's resource remarks, the assembly) of ONE device-only compile of picture_io.hip for gfx950 with build.py's flags: every as-compiled test of a picture
+    kernel reads these two texts, and the first to ask pays for the compile.  A compile that fails fails each of them."""
+    if "picture_io" not in _cache:
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "picture_io.s")
+            r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-device-only",
+                                "-Rpass-analysis=kernel-resource-usage", "-S", "-o", out, os.path.join(ROOT, "homerhevc_amd", "csrc", "picture_io.hip")],
+                               capture_output=True, text=True, timeout=900)
+            assert r.returncode == 0, r.stderr[-2000:]
+            with open(out) as f:
+                _cache["picture_io"] = (r.stderr, f.read())
+    return _cache["picture_io"]
 
 
 def load_gpu():

@@ -5,7 +5,6 @@ import ctypes as C
 import json
 import os
 import re
-import subprocess
 from fractions import Fraction
 
 import pytest
@@ -226,17 +225,13 @@ def test_the_default_clip_is_cut_where_its_cut_is(lib, size):
 
 # ---- the kernel as compiled ----
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_cut_kernel_as_compiled(tmp_path):
+def test_cut_kernel_as_compiled():
     """k_cut for gfx950: no private memory, no spills, LDS that lets at least four workgroups share a CU (160 KB), global_ (not flat_) loads, the search on the
     unmasked quad SAD, and no store to memory but the 32- and 64-bit atomic adds; k_cut_finish: one plain store, the only writer of HIST"""
-    out = tmp_path / "picture_io.s"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-S", "-o", str(out), os.path.join(libs.ROOT, "homerhevc_amd", "csrc", "picture_io.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
+    remarks, asm = libs.picture_io_as_compiled()
     seen = {}
-    for blk in r.stderr.split("Function Name: ")[1:]:
+    for blk in remarks.split("Function Name: ")[1:]:
         seen[blk.split()[0]] = {k: int(v) for k, v in re.findall(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", blk)}
-    asm = out.read_text()
 
     def ops_of(name):
         body = asm[asm.index(name + ":"):]

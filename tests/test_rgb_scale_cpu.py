@@ -202,14 +202,11 @@ def test_package_import_needs_neither_torch_nor_a_gpu():
 
 # ---- the kernel as compiled ----
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_rgb_ladder_kernel_as_compiled(tmp_path):
+def test_rgb_ladder_kernel_as_compiled():
     """k_rgb_ladder for gfx950: no private memory, no spills, a group segment of at most half a CU's LDS, global_ (not flat_) accesses, 16-byte loads and stores"""
-    out = tmp_path / "picture_io.s"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-S", "-o", str(out), os.path.join(libs.ROOT, "homerhevc_amd", "csrc", "picture_io.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
+    remarks, asm = libs.picture_io_as_compiled()
     seen = {}
-    for blk in r.stderr.split("Function Name: ")[1:]:
+    for blk in remarks.split("Function Name: ")[1:]:
         seen[blk.split()[0]] = {k: int(v) for k, v in re.findall(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", blk)}
     names = [n for n in seen if "k_rgb_ladder" in n]
     assert len(names) == 1, sorted(seen)
@@ -219,7 +216,6 @@ def test_rgb_ladder_kernel_as_compiled(tmp_path):
     print(f)
     assert f["ScratchSize [bytes/lane]"] == 0 and f["VGPRs Spill"] == 0 and f["SGPRs Spill"] == 0, f
     assert 0 < f["LDS Size [bytes/block]"] <= LDS_OF_A_CU // 2, f
-    asm = out.read_text()
     meta = asm[asm.index("amdhsa.kernels"):]
     entries = [e for e in re.split(r"\n  - ", meta) if re.search(r"\.name:\s+" + names[0] + r"\n", e)]      # the kernel's own record of the metadata
     assert len(entries) == 1

@@ -6,7 +6,6 @@ import ctypes as C
 import json
 import os
 import re
-import subprocess
 from fractions import Fraction
 
 import pytest
@@ -170,15 +169,12 @@ def test_the_header_declares_the_calls():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_ssim_kernel_as_compiled(tmp_path):
+def test_ssim_kernel_as_compiled():
     """k_ssim for gfx950: no private memory, no spills, eight waves per SIMD, a few KB of LDS, global_ (not flat_) 16-byte loads, the products by v_dot2, and no store to
     memory but ONE 64-bit atomic add"""
-    out = tmp_path / "picture_io.s"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-S", "-o", str(out), os.path.join(libs.ROOT, "homerhevc_amd", "csrc", "picture_io.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
+    remarks, asm = libs.picture_io_as_compiled()
     seen = {}
-    for blk in r.stderr.split("Function Name: ")[1:]:
+    for blk in remarks.split("Function Name: ")[1:]:
         seen[blk.split()[0]] = {k: int(v) for k, v in re.findall(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", blk)}
     names = [n for n in seen if "k_ssim" in n]
     assert len(names) == 1, sorted(seen)
@@ -186,7 +182,6 @@ def test_ssim_kernel_as_compiled(tmp_path):
     print(f)
     assert f["ScratchSize [bytes/lane]"] == 0 and f["VGPRs Spill"] == 0 and f["SGPRs Spill"] == 0 and f["Occupancy [waves/SIMD]"] == 8, f
     assert 0 < f["LDS Size [bytes/block]"] <= 4096, f
-    asm = out.read_text()
     body = asm[asm.index(names[0] + ":"):]
     body = body[:body.index(".Lfunc_end")]
     code = [l.split(";")[0].split() for l in body.splitlines()]

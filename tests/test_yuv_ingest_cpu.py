@@ -322,14 +322,11 @@ def test_the_header_declares_the_calls():
 
 # ---- the kernel as compiled ----
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_yuv_ingest_kernel_as_compiled(tmp_path):
+def test_yuv_ingest_kernel_as_compiled():
     """k_ingest_yuv for gfx950, from the compiler's resource remarks alone: no private memory, no spills, and as many waves a SIMD as k_ingest_rgb in the same compile"""
-    out = tmp_path / "picture_io.s"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-S", "-o", str(out), os.path.join(libs.ROOT, "homerhevc_amd", "csrc", "picture_io.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
+    remarks, asm = libs.picture_io_as_compiled()
     seen = {}
-    for blk in r.stderr.split("Function Name: ")[1:]:
+    for blk in remarks.split("Function Name: ")[1:]:
         seen[blk.split()[0]] = {k: int(v) for k, v in re.findall(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|Occupancy \[waves/SIMD\]): (\d+)", blk)}
     yuv, rgb = [n for n in seen if "k_ingest_yuv" in n], [n for n in seen if "k_ingest_rgb" in n]
     assert len(yuv) == 1 and len(rgb) == 1, sorted(seen)

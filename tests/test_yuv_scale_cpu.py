@@ -7,7 +7,6 @@ import os
 import re
 import subprocess
 import sys
-import time
 
 import numpy as np
 import pytest
@@ -209,17 +208,12 @@ def test_package_import_needs_neither_torch_nor_a_gpu():
 
 # ---- the kernel as compiled ----
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_yuv_ladder_kernel_as_compiled(tmp_path):
+def test_yuv_ladder_kernel_as_compiled():
     """k_yuv_ladder for gfx950, from ONE device-only compile of picture_io.hip: exactly one kernel of that name and still one per sibling's substring, no private memory, no
     spills of either kind, k_downscale's group segment, global_ (not flat_, not scratch_) accesses, 16-byte loads and stores"""
-    out = tmp_path / "picture_io.s"
-    t0 = time.time()
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-S", "-o", str(out), os.path.join(libs.ROOT, "homerhevc_amd", "csrc", "picture_io.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    print(f"picture_io.hip compiled for the device in {time.time() - t0:.0f} s (the siblings' tests allow 900)")
+    remarks, asm = libs.picture_io_as_compiled()
     seen = {}
-    for blk in r.stderr.split("Function Name: ")[1:]:
+    for blk in remarks.split("Function Name: ")[1:]:
         seen[blk.split()[0]] = {k: int(v) for k, v in re.findall(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", blk)}
     names = [n for n in seen if "k_yuv_ladder" in n]
     assert len(names) == 1, sorted(seen)
@@ -230,7 +224,6 @@ def test_yuv_ladder_kernel_as_compiled(tmp_path):
     assert f["ScratchSize [bytes/lane]"] == 0 and f["VGPRs Spill"] == 0 and f["SGPRs Spill"] == 0, f
     downscale = seen[[n for n in seen if "k_downscale" in n][0]]
     assert 0 < f["LDS Size [bytes/block]"] == downscale["LDS Size [bytes/block]"], (f, downscale)
-    asm = out.read_text()
     meta = asm[asm.index("amdhsa.kernels"):]
     entries = [e for e in re.split(r"\n  - ", meta) if re.search(r"\.name:\s+" + names[0] + r"\n", e)]      # the kernel's own record of the metadata
     assert len(entries) == 1
