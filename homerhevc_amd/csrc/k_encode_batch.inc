@@ -83,20 +83,43 @@ int batch_check(hmr_gpu_enc **encs, int n, const int *slots, uint8_t **streams, 
 	return HMR_GPU_OK;
 }
 
+// The n pictures staged in lead->h_devs / h_frames (launch_buffers) as ONE pool launch on the lead's stream, their gather records and the records' download behind
+// it.  rows_total, needs_rd: launch_pool's.
+int submit_staged(hmr_gpu_enc *lead, int n, int rows_total, bool needs_rd)
+{
+	hipStream_t bst = lead->ctx->stream;
+	hipLaunchKernelGGL(k_batch_stage, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->h_devs, (const FrameCtx *)lead->h_frames, (EncDev *)lead->d_batch, lead->d_frames);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(lead->ev_batch0, bst));
+	const int rc = launch_pool(lead, lead->h_devs, n, rows_total, needs_rd, bst);
+	if (rc) return rc;
+	(void)hipEventRecord(lead->ev_batch1, bst);
+	return queue_gather(lead, n);
+}
+// the lead's stream waited for: the launch is over (CTU decisions, filters and entropy coding of every picture) and its records are on the host; ms: the pool's time
+int wait_for_launch(hmr_gpu_enc *lead, float *ms)
+{
+	const hipError_t waited = hipStreamSynchronize(lead->ctx->stream);
+	if (waited != hipSuccess) {
+		hmr_set_error("k_encode_pool: %s", hipGetErrorString(waited));
+		return HMR_GPU_ERR_HIP;
+	}
+	HIP_TRY(hipEventElapsedTime(ms, lead->ev_batch0, lead->ev_batch1));
+	return HMR_GPU_OK;
+}
+
 // LAUNCH: the frames' CTU stages as one pool launch on the lead encoder's stream, their counters and distortions gathered behind it
-int batch_launch(hmr_gpu_enc **encs, int n, const int *slots, const int *image_types, int *pitch_out)
+int batch_launch(hmr_gpu_enc **encs, int n, const int *slots, const int *image_types)
 {
 	hmr_gpu_enc *lead = encs[0];
 	hipStream_t bst = lead->ctx->stream;
 	int rc, rows_total = 0, max_ctus = 0;
 	bool needs_rd = false;
+	for (int i = 0; i < n; i++)
+		if (encs[i]->seq.nctu > max_ctus) max_ctus = encs[i]->seq.nctu;
+	if ((rc = launch_buffers(lead, n, max_ctus, BATCH_MAX))) return rc;
 	// frame set-up on the host; nothing is queued on the sequences' streams: the launch's stream waits for what each of them still has in flight (the filter
 	// chain and packing of its previous frame) and takes the rest - the frames' parameters in one upload, the phase planes, the per-frame state in one kernel
-	if (!lead->d_frames) {
-		HIP_TRY(hipMalloc((void **)&lead->d_frames, BATCH_MAX * sizeof(FrameCtx)));
-		HIP_TRY(hipHostMalloc((void **)&lead->h_frames, BATCH_MAX * sizeof(FrameCtx), hipHostMallocDefault));
-		HIP_TRY(hipHostMalloc((void **)&lead->h_devs, BATCH_MAX * sizeof(EncDev), hipHostMallocDefault));
-	}
 	for (int i = 0; i < n; i++) {
 		hmr_gpu_enc *e = encs[i];
 		if ((rc = set_frame(e, slots[i], image_types ? image_types[i] : 0, -1.0, false))) return rc;
@@ -108,7 +131,6 @@ int batch_launch(hmr_gpu_enc **encs, int n, const int *slots, const int *image_t
 		lead->h_devs[i].frame = lead->d_frames + i;
 		rows_total += pool_inflight(e->seq, e->raster);
 		needs_rd = needs_rd || e->seq.rd_mode == RDM_FULL;
-		if (e->seq.nctu > max_ctus) max_ctus = e->seq.nctu;
 	}
 	// The phase planes of all the reference pictures one after the other on the launch's stream: a picture's three kernels fill the GPU (2500 workgroups, 1.9 TB/s);
 	// run side by side on the sequences' streams, sixteen at a time, they reached a quarter of that between them (rocprofv3 trace: 52 ms for 180 pictures).
@@ -135,92 +157,41 @@ int batch_launch(hmr_gpu_enc **encs, int n, const int *slots, const int *image_t
 		HIP_TRY(hipEventRecord(lead->ev_plane[k], lead->plane_stream[k]));
 		HIP_TRY(hipStreamWaitEvent(bst, lead->ev_plane[k], 0));
 	}
-	if (!lead->d_batch) {
-		HIP_TRY(hipMalloc((void **)&lead->d_batch, BATCH_MAX * sizeof(EncDev)));
-		HIP_TRY(hipDeviceGetAttribute(&lead->n_cus, hipDeviceAttributeMultiprocessorCount, lead->ctx->device));
-	}
-	const int pitch = GATHER_HEAD + max_ctus + POST_MAX_ROWS;
-	if ((size_t)pitch * n > lead->gather_words) {
-		if (lead->d_gather) (void)hipFree(lead->d_gather);
-		if (lead->h_gather) (void)hipHostFree(lead->h_gather);
-		lead->d_gather = lead->h_gather = nullptr;
-		lead->gather_words = 0;
-		HIP_TRY(hipMalloc((void **)&lead->d_gather, (size_t)pitch * BATCH_MAX * 4));
-		HIP_TRY(hipHostMalloc((void **)&lead->h_gather, (size_t)pitch * BATCH_MAX * 4, hipHostMallocDefault));
-		lead->gather_words = (size_t)pitch * BATCH_MAX;
-	}
-	hipLaunchKernelGGL(k_batch_stage, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->h_devs, (const FrameCtx *)lead->h_frames, (EncDev *)lead->d_batch, lead->d_frames);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(lead->ev_batch0, bst));
-	if ((rc = launch_pool(lead, lead->h_devs, n, rows_total, needs_rd, bst))) return rc;
-	(void)hipEventRecord(lead->ev_batch1, bst);
-	hipLaunchKernelGGL(k_gather_results, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->d_batch, lead->d_gather, pitch, (const int *)(lead->d_pool_state + BATCH_MAX * POOL_STRIDE));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(lead->h_gather, lead->d_gather, (size_t)pitch * n * 4, hipMemcpyDeviceToHost, bst));
-	*pitch_out = pitch;
-	return HMR_GPU_OK;
+	return submit_staged(lead, n, rows_total, needs_rd);
 }
 
-// FINISH: wait for the launch (CTU decisions, filters and entropy coding of every picture are done when it ends); frame bookkeeping from the gathered counters,
-// distortions and sub-stream sizes; the sub-streams of all pictures packed into one staging buffer by one kernel and their download queued on the copy stream
-int batch_finish(hmr_gpu_enc **encs, int n, const int *slots, int pitch, BatchTimes &bt)
+// FINISH: wait for the launch; frame bookkeeping from the gathered counters, distortions and sub-stream sizes; the sub-streams of all pictures packed into one
+// staging buffer by one kernel and their download queued on the copy stream
+int batch_finish(hmr_gpu_enc **encs, int n, BatchTimes &bt)
 {
-	(void)slots;
 	hmr_gpu_enc *lead = encs[0];
 	hipStream_t bst = lead->ctx->stream;
-	const hipError_t waited = hipStreamSynchronize(bst);
-	if (waited != hipSuccess) {
-		hmr_set_error("k_encode_pool: %s", hipGetErrorString(waited));
-		return HMR_GPU_ERR_HIP;
-	}
-	bt.t[2] = std::chrono::steady_clock::now();
+	int rc;
 	float ms = 0;
-	HIP_TRY(hipEventElapsedTime(&ms, lead->ev_batch0, lead->ev_batch1));
+	if ((rc = wait_for_launch(lead, &ms))) return rc;
+	bt.t[2] = std::chrono::steady_clock::now();
 	if (!lead->h_offs) HIP_TRY(hipHostMalloc((void **)&lead->h_offs, BATCH_MAX * sizeof(size_t), hipHostMallocDefault));
 	lead->pend_off.resize(n);
 	lead->pend_rows.assign(n, std::vector<uint32_t>());
 	size_t total = 0;
 	for (int i = 0; i < n; i++) {
 		hmr_gpu_enc *e = encs[i];
-		const uint32_t *g = lead->h_gather + (size_t)i * pitch;
-		if (g[3] & 2) {
-			hmr_set_error("k_encode_pool: the launch was abandoned by its watchdog (a worker found nothing to do for too long: HENC_WATCHDOG_S)");
-			return HMR_GPU_ERR_HIP;
-		}
-		if (g[3] & 1) {
-			hmr_set_error("hmr_gpu_enc_encode_batch: sequence %d: a CTU row's sub-stream outgrew its buffer (%d bytes)", i, e->row_cap);
-			return HMR_GPU_ERR_HIP;
-		}
-		e->note_stale_predictions(g[3] >> 8);
+		PictureResults res;
+		if ((rc = read_record(lead, i, e, "hmr_gpu_enc_encode_batch: sequence", &res))) return rc;
 		const int rows = e->seq.wpp ? e->seq.hctu : 1;
 		lead->pend_off[i] = total;
 		lead->h_offs[i] = total;
-		lead->pend_rows[i].assign(g + pitch - POST_MAX_ROWS, g + pitch - POST_MAX_ROWS + rows);
+		lead->pend_rows[i].assign(res.row_bytes, res.row_bytes + rows);
 		for (int r = 0; r < rows; r++) total += lead->pend_rows[i][r];
 		total = (total + 255) & ~(size_t)255;
 		e->last_ms = e->last_total_ms = ms;
-		e->last_encodes = (int)g[1];
-		e->f.scene_cut_ctu = (int)g[2];
-		e->last_passes = 1;
 		release_planes(e);
 		// the frame's statistics (encoder_engine_thread :3217-3238) need the CTUs' distortions only: the sequence can start its next frame
 		e->f_pending = e->f;
 		e->awaiting_delivery = true;
-		FrameRcOut ro;
-		ro.sum_qp = (int)g[4]; ro.consumed_bits = (double)g[5];
-		memcpy(&ro.target_pict_size, &g[6], 8);
-		end_frame(e->seq, e->st, e->f, frame_acc_dist(e->seq, e->cfg.wfpp_num_threads, [&](int c) { return g[GATHER_HEAD + c]; }), &ro);
+		end_frame(e->seq, e->st, e->f, frame_acc_dist(e->seq, e->cfg.wfpp_num_threads, [&](int c) { return res.dist[c]; }), &res.rc);
 	}
-	if (total > lead->stage_bytes) {
-		if (lead->d_stage) (void)hipFree(lead->d_stage);
-		if (lead->h_stage) (void)hipHostFree(lead->h_stage);
-		lead->d_stage = lead->h_stage = nullptr;
-		lead->stage_bytes = 0;
-		const size_t want = total * 2 + (1 << 20);
-		HIP_TRY(hipMalloc((void **)&lead->d_stage, want));
-		HIP_TRY(hipHostMalloc((void **)&lead->h_stage, want, hipHostMallocDefault));
-		lead->stage_bytes = want;
-	}
+	if ((rc = grow_pair(&lead->d_stage, &lead->h_stage, &lead->stage_bytes, total, total * 2 + (1 << 20)))) return rc;
 	if (!lead->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&lead->copy_stream, hipStreamNonBlocking));
 	hipLaunchKernelGGL(k_pack_streams, dim3(n), dim3(256), 0, bst, (const EncDev *)lead->d_batch, lead->d_stage, (const size_t *)lead->h_offs);
 	HIP_TRY(hipGetLastError());
@@ -281,11 +252,10 @@ extern "C" int hmr_gpu_enc_encode_batch(hmr_gpu_enc **encs, int n, const int *sl
 	hmr_gpu_enc *lead = encs[0];
 	HIP_TRY(hipSetDevice(lead->ctx->device));
 	BatchTimes bt;
-	int pitch = 0;
 	bt.t[0] = std::chrono::steady_clock::now();
-	if ((rc = batch_launch(encs, n, slots, image_types, &pitch))) return rc;
+	if ((rc = batch_launch(encs, n, slots, image_types))) return rc;
 	bt.t[1] = std::chrono::steady_clock::now();
-	if ((rc = batch_finish(encs, n, slots, pitch, bt))) return rc;
+	if ((rc = batch_finish(encs, n, bt))) return rc;
 	if ((rc = batch_deliver(lead, streams, caps, stream_bytes, bt))) return rc;
 	batch_report(bt, lead, false);
 	return HMR_GPU_OK;
@@ -313,8 +283,7 @@ extern "C" int hmr_gpu_enc_encode_batch_pipelined(hmr_gpu_enc **encs, int n, con
 	}
 	BatchTimes bt;
 	for (auto &t : bt.t) t = std::chrono::steady_clock::now();
-	int pitch = 0;
-	if (slots && (rc = batch_launch(encs, n, slots, image_types, &pitch))) return rc;
+	if (slots && (rc = batch_launch(encs, n, slots, image_types))) return rc;
 	bt.t[1] = std::chrono::steady_clock::now();
 	if (lead->pending) {
 		if ((rc = batch_deliver(lead, streams, caps, stream_bytes, bt))) return rc;
@@ -322,7 +291,7 @@ extern "C" int hmr_gpu_enc_encode_batch_pipelined(hmr_gpu_enc **encs, int n, con
 		for (int i = 0; i < n; i++) stream_bytes[i] = 0;
 		bt.t[6] = bt.t[1];
 	}
-	if (slots && (rc = batch_finish(encs, n, slots, pitch, bt))) return rc;
+	if (slots && (rc = batch_finish(encs, n, bt))) return rc;
 	if (slots) batch_report(bt, lead, true);
 	return HMR_GPU_OK;
 }
@@ -453,7 +422,10 @@ extern "C" int hmr_gpu_enc_encode_chain(hmr_gpu_enc **encs, int n, hmr_gpu_enc *
 		rows_total += s.hctu;
 		needs_rd = needs_rd || s.rd_mode == RDM_FULL;
 	}
-	const int nctu = lead->seq.nctu, pitch = GATHER_HEAD + nctu + POST_MAX_ROWS;
+	// (This entry still has its own copy of the launch sequence and reads the records by word index - g[1 .. 11] are GatherHead's members in order, k_encode_object.inc:
+	// a rewrite on submit_staged / read_record was taken out again, profiles/launch_collect_refactor.md section 5.  Only the pitch is the shared one: the kernel stores
+	// the head's doubles as doubles, which needs gather_pitch's even record size.)
+	const int pitch = gather_pitch(lead->seq.nctu);
 	if ((size_t)pitch * n > lead->gather_words) {
 		if (lead->d_gather) (void)hipFree(lead->d_gather);
 		if (lead->h_gather) (void)hipHostFree(lead->h_gather);

@@ -117,15 +117,13 @@ struct hmr_gpu_enc {
 	// host side of the entropy stage
 	std::vector<uint8_t, PinnedAlloc<uint8_t>> h_public;
 	std::vector<int16_t, PinnedAlloc<int16_t>> h_coeff;
-	std::vector<int32_t> h_stats, h_params;
-	std::vector<double> h_lambdas;
 	hipEvent_t ev_frame = nullptr, ev_ready = nullptr, ev_batch0 = nullptr, ev_batch1 = nullptr;   // (the batch launch has events of its own: frame_finish re-records the context's)   // start of the frame on the encoder's stream; its CTU stage may be launched
 	int n_cus = 0;
-	uint8_t *d_stage = nullptr, *h_stage = nullptr;      // batch: the side-info records and levels of all sequences, on the device and page-locked on the host
+	uint8_t *d_stage = nullptr, *h_stage = nullptr;      // batch: the packed sub-streams of all sequences (k_pack_streams), on the device and page-locked on the host
 	size_t stage_bytes = 0;
-	void *d_batch = nullptr;                             // hmr_gpu_enc_encode_batch (lead encoder): the sequences' EncDev records and first rows
+	void *d_batch = nullptr;                             // (lead encoder) the EncDev records of a launch's pictures
 	// pipelined batch (lead encoder): the step whose access units are still to be delivered
-	bool pending = false, download_queued = false;
+	bool pending = false;
 	std::vector<hmr_gpu_enc *> pend_encs;
 	std::vector<size_t> pend_off;                        // where each sequence's sub-streams lie in the staging buffer
 	std::vector<std::vector<uint32_t>> pend_rows;        // and the bytes of each of its rows
@@ -134,11 +132,10 @@ struct hmr_gpu_enc {
 	hipStream_t copy_stream = nullptr;
 	uint32_t *d_gather = nullptr, *h_gather = nullptr;   // per picture of a launch: the frame's counters and the CTUs' distortions
 	size_t gather_words = 0;
+	int record_words = 0;                                // (gather_pitch of the last launch)
 	// (every encoder of the batch)
 	bool awaiting_delivery = false;                      // its last frame's access unit has not been coded yet
 	FrameCtx f_pending;                                  // that frame's parameters (e->f moves on with the next set_frame)
-	double acc_pending = 0;
-	hipEvent_t ev_packed = nullptr;                      // its records and levels are in the staging buffer
 	hipEvent_t ev_decided = nullptr;                     // (lead) the batch's SAO decisions are made
 	FrameCtx *d_frames = nullptr, *h_frames = nullptr;   // (lead) the frame parameters of a batch's pictures, on the device and page-locked on the host
 	EncDev *h_devs = nullptr;                            // (lead) their EncDev records, page-locked
@@ -265,24 +262,7 @@ int ctu_stage_prepare(hmr_gpu_enc *e, bool planes_elsewhere = false)
 	HIP_TRY(hipMemsetAsync(e->d_post_err, 0, sizeof(int) * 4, st));
 	return HMR_GPU_OK;
 }
-// row-per-thread schedule, after the launch: what the frame found
-int lockstep_collect(hmr_gpu_enc *e)
-{
-	hipStream_t st = e->ctx->stream;
-	int counters[3], aborted = 0;
-	HIP_TRY(hipMemcpyAsync(counters, e->d.counters, sizeof counters, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&aborted, e->d_pool_state + BATCH_MAX * POOL_STRIDE + 1, sizeof(int), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	e->last_encodes = counters[1];
-	e->f.scene_cut_ctu = counters[2];
-	e->last_passes = 1;
-	release_planes(e);
-	if (aborted) {
-		hmr_set_error("k_encode_pool: the launch was abandoned by its watchdog (a worker found nothing to do for too long: HENC_WATCHDOG_S)");
-		return HMR_GPU_ERR_HIP;
-	}
-	return HMR_GPU_OK;
-}
+int lockstep_run(hmr_gpu_enc *e);      // (behind k_gather_results)
 
 // CTUs of a picture that can be decided at the same time: a wavefront step holds one CTU of every second column, so at most min(rows, (columns + 1) / 2); under rate
 // control a step also waits for the entropy coder's progress (enc_rc.h), which about halves it.  Workers beyond what a launch can keep busy are not merely idle: every
@@ -347,21 +327,12 @@ int launch_pool(hmr_gpu_enc *lead, const EncDev *host, int n, int rows_total, bo
 // the CTU decisions of the frame set up in e->f / e->d_frame: passes until the check finds nothing wrong
 int run_ctu_passes(hmr_gpu_enc *e)
 {
+	if (e->lockstep) return lockstep_run(e);      // wfpp_num_threads > 1: the synchronous wavefront, one launch, nothing to verify - the picture's CTUs as a pool of tasks (k_encode_pool)
 	const Seq &s = e->seq;
 	hipStream_t st = e->ctx->stream;
 	int rc = ctu_stage_prepare(e);
 	if (rc) return rc;
 	HIP_TRY(hipEventRecord(e->ctx->ev0, st));
-	if (e->lockstep) {
-		// wfpp_num_threads > 1: the synchronous wavefront, one launch, nothing to verify - the picture's CTUs as a pool of tasks (k_encode_pool)
-		if (!e->d_batch) HIP_TRY(hipMalloc((void **)&e->d_batch, BATCH_MAX * sizeof(EncDev)));
-		HIP_TRY(hipMemcpyAsync(e->d_batch, &e->d, sizeof(EncDev), hipMemcpyHostToDevice, st));
-		if ((rc = launch_pool(e, &e->d, 1, e->raster ? pool_inflight(s, 1) : s.hctu, s.rd_mode == RDM_FULL, st))) return rc;      // (one picture: a worker per row, each on a CU of its own)
-		HIP_TRY(hipEventRecord(e->ctx->ev1, st));
-		if ((rc = lockstep_collect(e))) return rc;      // (waits for the launch)
-		HIP_TRY(hipEventElapsedTime(&e->last_ms, e->ctx->ev0, e->ctx->ev1));
-		return HMR_GPU_OK;
-	}
 	// wfpp_num_threads = 1: the single thread's order.  Row workers wait for the row above (progress[]), so every workgroup of the launch has to be resident
 	// or the waiting ones spin for ever: a cooperative launch makes the runtime guarantee that - it fails at launch time when the grid does not fit (another
 	// process on the GPU, a partition mode) instead of hanging.
@@ -591,7 +562,6 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 	HIP_TRY(hipEventCreate(&e->ev_ready));
 	HIP_TRY(hipEventCreate(&e->ev_batch0));
 	HIP_TRY(hipEventCreate(&e->ev_batch1));
-	HIP_TRY(hipEventCreateWithFlags(&e->ev_packed, hipEventDisableTiming));
 	HIP_TRY(hipEventCreateWithFlags(&e->ev_decided, hipEventDisableTiming));
 	DEV_ALLOC(e->d.coeff, (size_t)6144 * s.nctu);
 	DEV_ALLOC(e->d.progress, s.hctu);
@@ -667,8 +637,6 @@ static int enc_create(hmr_gpu_ctx *ctx, const hmr_gpu_enc_cfg *cfg, int engine_i
 	DEV_ALLOC(e->d_public, sizeof(CtuPublic) * s.nctu);
 	e->h_public.resize(sizeof(CtuPublic) * s.nctu);
 	e->h_coeff.resize((size_t)6144 * s.nctu);
-	e->h_stats.resize((size_t)s.nctu * 3 * 5 * 2 * 32);
-	e->h_params.resize((size_t)s.nctu * 3 * 34);
 	e->d.seq = e->d_seq;
 	e->d.frame = e->d_frame;
 	e->d.tables = ctx->tables;
@@ -834,7 +802,6 @@ extern "C" void hmr_gpu_enc_destroy(hmr_gpu_enc *e)
 	if (e->ev_ready) (void)hipEventDestroy(e->ev_ready);
 	if (e->ev_batch0) (void)hipEventDestroy(e->ev_batch0);
 	if (e->ev_batch1) (void)hipEventDestroy(e->ev_batch1);
-	if (e->ev_packed) (void)hipEventDestroy(e->ev_packed);
 	if (e->ev_decided) (void)hipEventDestroy(e->ev_decided);
 	if (e->d_frames) (void)hipFree(e->d_frames);
 	if (e->h_frames) (void)hipHostFree(e->h_frames);
@@ -1018,15 +985,36 @@ extern "C" int hmr_gpu_enc_frame_ctus(hmr_gpu_enc *e, const uint8_t *y, const ui
 }
 
 namespace {
-constexpr int GATHER_HEAD = 12;         // words in front of the CTUs' distortions in a picture's gather record
 constexpr int CHAIN_MAX_FRAMES = 32;    // frames of one hmr_gpu_enc_encode_chain call
+// A picture's gather record - what the host's bookkeeping needs of a picture of a pool launch, in one small download: a GatherHead, the CTUs' distortions (a word
+// each: gather_dist), a gap, and in its last POST_MAX_ROWS words the bytes of the rows' sub-streams (gather_row_bytes).  Record i of a launch starts at word
+// i * gather_pitch(the largest CTU count among the launch's pictures).  The buffers are declared as words - the distortions and byte counts are words - and a
+// record's head is read and written through a GatherHead reference: the device and the host agree on the layout (one struct, one translation unit), the buffers come
+// from hipMalloc / hipHostMalloc and nothing else aliases them.
+constexpr int GATHER_HEAD = 12;         // words in front of the CTUs' distortions
+struct GatherHead {
+	int32_t failed_checks, encodes, scene_cut_ctu;      // EncDev::counters - the single-thread order's failed checks (the pool leaves 0), CTU encodes, the CTU that found a scene cut (-1: none)
+	uint32_t flags;                                      // GATHER_*
+	uint32_t sum_qp, bits;                               // rate control: the sum of the CTUs' QPs (the root nodes': acc_qp, hmr_encoder_lib.c:2938), the bits of all CTUs,
+	double target_pict_size;                             // the picture target as the frame left it
+	double launch_dist, avg_dist;                        // chains: the distortion total as the launch computed it, the average distortion the picture started from (the launch sets it for an engine's later pictures)
+};
+static_assert(sizeof(GatherHead) == GATHER_HEAD * 4, "the record's head is GATHER_HEAD words");
+// flags: a row's sub-stream outgrew its buffer; the launch was abandoned by its watchdog; from bit 8 the picture's evaluations on a stale prediction window (Q12), saturating
+constexpr uint32_t GATHER_ROW_OVERFLOW = 1u << 0, GATHER_ABANDONED = 1u << 1, GATHER_STALE_MAX = 0xffffffu;
+constexpr int GATHER_STALE_SHIFT = 8;
+// An EVEN number of words: the buffers start on 256 bytes, so every record - and with it the doubles of its head - starts on 8 bytes and the members are stored and
+// read as they are (an odd pitch would need byte-wise access: a double stored through a misaligned pointer faults on the device).  The buffers are the encoder's own.
+__host__ __device__ constexpr int gather_pitch(int max_nctu) { return (GATHER_HEAD + max_nctu + POST_MAX_ROWS + 1) & ~1; }
+template <class W> __host__ __device__ W *gather_dist(W *rec) { return rec + GATHER_HEAD; }
+template <class W> __host__ __device__ W *gather_row_bytes(W *rec, int pitch) { return rec + pitch - POST_MAX_ROWS; }
+
 __global__ void k_gather_results(const EncDev *devs, uint32_t *out, int pitch, const int *pool_flags)
 {
 	const EncDev &d = devs[blockIdx.x];
 	uint32_t *o = out + (size_t)blockIdx.x * pitch;
+	GatherHead &h = *(GatherHead *)o;
 	const int nctu = d.seq->nctu;
-	if (threadIdx.x < 3) o[threadIdx.x] = (uint32_t)d.counters[threadIdx.x];
-	// rate control: the sum of the CTUs' QPs (the root nodes': acc_qp, hmr_encoder_lib.c:2938), the bits of all CTUs, the picture target as the frame left it
 	__shared__ uint32_t s_qp, s_bits, s_stale;
 	if (threadIdx.x == 0) { s_qp = 0; s_bits = 0; s_stale = 0; }
 	__syncthreads();
@@ -1037,21 +1025,130 @@ __global__ void k_gather_results(const EncDev *devs, uint32_t *out, int pitch, c
 	atomicAdd(&s_bits, b);
 	atomicAdd(&s_stale, stale);
 	__syncthreads();
-	// word 3: bit 0 a row's sub-stream outgrew its buffer, bit 1 the launch was abandoned, bits 8 ...: the picture's evaluations on a stale prediction window (Q12)
-	if (threadIdx.x == 0) o[3] = (uint32_t)(d.post.errors[0] != 0) | ((uint32_t)(pool_flags && pool_flags[1] != 0) << 1) | ((s_stale > 0xffffffu ? 0xffffffu : s_stale) << 8);
 	if (threadIdx.x == 0) {
-		o[4] = s_qp;
-		o[5] = s_bits;
-		const double tp = d.counters[2] >= 0 ? d.rc_dyn->target_pict_size : d.frame->rc.target_pict_size;
-		memcpy(&o[6], &tp, 8);
-		// chains: the distortion total as the launch computed it, and the average distortion the picture started from (the launch sets it for an engine's later pictures)
-		const double fin = d.fin[0], avg = d.frame->avg_dist;
-		memcpy(&o[8], &fin, 8);
-		memcpy(&o[10], &avg, 8);
+		h.failed_checks = d.counters[0]; h.encodes = d.counters[1]; h.scene_cut_ctu = d.counters[2];
+		h.flags = (d.post.errors[0] != 0 ? GATHER_ROW_OVERFLOW : 0) | (pool_flags && pool_flags[1] != 0 ? GATHER_ABANDONED : 0) | ((s_stale > GATHER_STALE_MAX ? GATHER_STALE_MAX : s_stale) << GATHER_STALE_SHIFT);
+		h.sum_qp = s_qp;
+		h.bits = s_bits;
+		h.target_pict_size = d.counters[2] >= 0 ? d.rc_dyn->target_pict_size : d.frame->rc.target_pict_size;
+		h.launch_dist = d.fin[0];
+		h.avg_dist = d.frame->avg_dist;
 	}
-	for (int c = threadIdx.x; c < nctu; c += blockDim.x) o[GATHER_HEAD + c] = d.ctus[c].distortion;
-	// bytes of the rows' sub-streams, behind the distortions
-	for (int r = threadIdx.x; r < d.seq->hctu; r += blockDim.x) o[pitch - POST_MAX_ROWS + r] = (uint32_t)d.post.ent[r].bytecnt;
+	for (int c = threadIdx.x; c < nctu; c += blockDim.x) gather_dist(o)[c] = d.ctus[c].distortion;
+	for (int r = threadIdx.x; r < d.seq->hctu; r += blockDim.x) gather_row_bytes(o, pitch)[r] = (uint32_t)d.post.ent[r].bytecnt;
+}
+
+// a device buffer and its page-locked twin on the host, grown to `want` elements when they hold fewer than `need`
+template <class T>
+int grow_pair(T **dev, T **host, size_t *have, size_t need, size_t want)
+{
+	if (need <= *have) return HMR_GPU_OK;
+	if (*dev) (void)hipFree(*dev);
+	if (*host) (void)hipHostFree(*host);
+	*dev = *host = nullptr;
+	*have = 0;
+	HIP_TRY(hipMalloc((void **)dev, want * sizeof(T)));
+	HIP_TRY(hipHostMalloc((void **)host, want * sizeof(T), hipHostMallocDefault));
+	*have = want;
+	return HMR_GPU_OK;
+}
+// What the lead of a pool launch of n pictures of up to max_nctu CTUs owns: the device copies of their EncDev records, room for `records` gather records and - where
+// the pictures are staged through k_batch_stage (records = BATCH_MAX; one picture on its own uploads its record and parameters itself) - the staging arrays.
+int launch_buffers(hmr_gpu_enc *lead, int n, int max_nctu, int records)
+{
+	const int pitch = lead->record_words = gather_pitch(max_nctu);
+	if (records > 1 && !lead->d_frames) {
+		HIP_TRY(hipMalloc((void **)&lead->d_frames, BATCH_MAX * sizeof(FrameCtx)));
+		HIP_TRY(hipHostMalloc((void **)&lead->h_frames, BATCH_MAX * sizeof(FrameCtx), hipHostMallocDefault));
+		HIP_TRY(hipHostMalloc((void **)&lead->h_devs, BATCH_MAX * sizeof(EncDev), hipHostMallocDefault));
+	}
+	if (!lead->d_batch) HIP_TRY(hipMalloc((void **)&lead->d_batch, BATCH_MAX * sizeof(EncDev)));
+	return grow_pair(&lead->d_gather, &lead->h_gather, &lead->gather_words, (size_t)pitch * n, (size_t)pitch * records);
+}
+// behind a pool launch of n pictures on the lead's stream: their gather records, and the records' download
+int queue_gather(hmr_gpu_enc *lead, int n)
+{
+	hipStream_t st = lead->ctx->stream;
+	const int pitch = lead->record_words;
+	hipLaunchKernelGGL(k_gather_results, dim3(n), dim3(256), 0, st, (const EncDev *)lead->d_batch, lead->d_gather, pitch, (const int *)(lead->d_pool_state + BATCH_MAX * POOL_STRIDE));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(lead->h_gather, lead->d_gather, (size_t)pitch * n * 4, hipMemcpyDeviceToHost, st));
+	return HMR_GPU_OK;
+}
+
+// The downloaded record of picture `index` of lead's launch, e's picture, read for a call of `entry` ("<the entry's name>: <its word for a picture>", for the
+// messages): refuses a launch its watchdog abandoned and a sub-stream that outgrew its buffer, notes the launch's counters in e and hands back what the frame's
+// bookkeeping needs (dist: the CTUs' distortions; row_bytes: the bytes of the rows' sub-streams).
+struct PictureResults { FrameRcOut rc; double launch_dist, avg_dist; const uint32_t *dist, *row_bytes; };
+int read_record(hmr_gpu_enc *lead, int index, hmr_gpu_enc *e, const char *entry, PictureResults *out)
+{
+	const uint32_t *rec = lead->h_gather + (size_t)index * lead->record_words;
+	const GatherHead &h = *(const GatherHead *)rec;
+	if (h.flags & GATHER_ABANDONED) {
+		hmr_set_error("k_encode_pool: the launch was abandoned by its watchdog (a worker found nothing to do for too long: HENC_WATCHDOG_S)");
+		return HMR_GPU_ERR_HIP;
+	}
+	if (h.flags & GATHER_ROW_OVERFLOW) {
+		hmr_set_error("%s %d: a CTU row's sub-stream outgrew its buffer (%d bytes)", entry, index, e->row_cap);
+		return HMR_GPU_ERR_HIP;
+	}
+	e->note_stale_predictions(h.flags >> GATHER_STALE_SHIFT);
+	e->last_encodes = h.encodes;
+	e->f.scene_cut_ctu = h.scene_cut_ctu;
+	e->last_passes = 1;
+	out->rc.sum_qp = (int)h.sum_qp; out->rc.consumed_bits = (double)h.bits; out->rc.target_pict_size = h.target_pict_size;
+	out->launch_dist = h.launch_dist; out->avg_dist = h.avg_dist;
+	out->dist = gather_dist(rec);
+	out->row_bytes = gather_row_bytes(rec, lead->record_words);
+	return HMR_GPU_OK;
+}
+
+// One picture in the row-per-thread schedule (hmr_gpu_enc_encode_source): it is its own lead.  LAUNCH - its EncDev record and parameters go up by copies of their
+// own, not through k_batch_stage: a lone sequence's launches per frame stay what they are ...
+int lockstep_launch(hmr_gpu_enc *e)
+{
+	const Seq &s = e->seq;
+	hipStream_t st = e->ctx->stream;
+	int rc = ctu_stage_prepare(e);
+	if (rc) return rc;
+	HIP_TRY(hipEventRecord(e->ctx->ev0, st));
+	if ((rc = launch_buffers(e, 1, s.nctu, 1))) return rc;
+	HIP_TRY(hipMemcpyAsync(e->d_batch, &e->d, sizeof(EncDev), hipMemcpyHostToDevice, st));
+	if ((rc = launch_pool(e, &e->d, 1, e->raster ? pool_inflight(s, 1) : s.hctu, s.rd_mode == RDM_FULL, st))) return rc;      // (one picture: a worker per row, each on a CU of its own)
+	HIP_TRY(hipEventRecord(e->ctx->ev1, st));
+	return HMR_GPU_OK;
+}
+// ... and COLLECT, once queue_gather's download has been waited for: the CTU stage is over (entry: read_record's)
+int lockstep_collect(hmr_gpu_enc *e, const char *entry, PictureResults *res)
+{
+	release_planes(e);
+	HIP_TRY(hipEventElapsedTime(&e->last_ms, e->ctx->ev0, e->ctx->ev1));
+	return read_record(e, 0, e, entry, res);
+}
+// run_ctu_passes, that is hmr_gpu_enc_frame_ctus on a row-per-thread object: the CTU stage from start to end.  Its collect is the record too (the parent fetched the
+// counters and the abandoned flag by two copies of their own), so this entry also counts the stale predictions and refuses a sub-stream that outgrew its buffer.
+int lockstep_run(hmr_gpu_enc *e)
+{
+	PictureResults res;
+	int rc = lockstep_launch(e);
+	if (rc || (rc = queue_gather(e, 1))) return rc;
+	HIP_TRY(hipStreamSynchronize(e->ctx->stream));
+	return lockstep_collect(e, "hmr_gpu_enc_frame_ctus: picture", &res);
+}
+
+// a picture's sub-streams, as many bytes as each row took, one after the other into e->h_bs: a copy per row queued on `st` (frame_assemble reads them once it has been waited for)
+int queue_substreams(hmr_gpu_enc *e, const uint32_t *row_bytes, hipStream_t st)
+{
+	const int rows = e->seq.wpp ? e->seq.hctu : 1;
+	size_t total = 0;
+	for (int r = 0; r < rows; r++) total += row_bytes[r];
+	if (e->h_bs.size() < total) e->h_bs.resize(total);      // (the host copy holds what the picture took, not the rows' whole buffers)
+	total = 0;
+	for (int r = 0; r < rows; r++) {
+		HIP_TRY(hipMemcpyAsync(e->h_bs.data() + total, e->d_bs + (size_t)r * e->row_cap, row_bytes[r], hipMemcpyDeviceToHost, st));
+		total += row_bytes[r];
+	}
+	return HMR_GPU_OK;
 }
 
 }  // namespace
@@ -1078,32 +1175,19 @@ int frame_assemble(hmr_gpu_enc *e, const FrameCtx &f, const uint8_t *bytes, cons
 	memcpy(stream, out.data(), out.size());
 	return f.slice_type;
 }
-// one sequence, behind its CTU stage (which has been waited for): the sub-streams and the CTUs' distortions to the host, the access unit, the frame bookkeeping
-int frame_finish(hmr_gpu_enc *e, int slot, uint8_t *stream, long cap, long *stream_bytes, uint8_t *recon)
+// one sequence, behind its CTU stage (row-per-thread schedule: launched, and waited for here; single-thread order: over): the sub-streams and the CTUs' distortions
+// to the host, the access unit, the frame bookkeeping
+int frame_finish(hmr_gpu_enc *e, uint8_t *stream, long cap, long *stream_bytes, uint8_t *recon)
 {
-	(void)slot;
 	const Seq &s = e->seq;
 	hipStream_t st = e->ctx->stream;
 	int rc, err[4];
 	HIP_TRY(hipMemcpyAsync(e->h_ent.data(), e->d_ent, sizeof(RowEnt) * s.hctu, hipMemcpyDeviceToHost, st));
-	const int pitch = GATHER_HEAD + s.nctu + POST_MAX_ROWS;
-	if (e->lockstep) {
-		// the frame's counters, distortions and rate-control sums in one small record (the picture's EncDev is at d_batch: run_ctu_passes)
-		if ((size_t)pitch > e->gather_words) {
-			if (e->d_gather) (void)hipFree(e->d_gather);
-			if (e->h_gather) (void)hipHostFree(e->h_gather);
-			e->d_gather = e->h_gather = nullptr;
-			e->gather_words = 0;
-			HIP_TRY(hipMalloc((void **)&e->d_gather, (size_t)pitch * 4));
-			HIP_TRY(hipHostMalloc((void **)&e->h_gather, (size_t)pitch * 4, hipHostMallocDefault));
-			e->gather_words = (size_t)pitch;
-		}
-		hipLaunchKernelGGL(k_gather_results, dim3(1), dim3(256), 0, st, (const EncDev *)e->d_batch, e->d_gather, pitch, (const int *)nullptr);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(e->h_gather, e->d_gather, (size_t)pitch * 4, hipMemcpyDeviceToHost, st));
-	} else if ((rc = download_public(e))) return rc;
+	if ((rc = e->lockstep ? queue_gather(e, 1) : download_public(e))) return rc;
 	HIP_TRY(hipMemcpyAsync(err, e->d_post_err, sizeof err, hipMemcpyDeviceToHost, st));      // (err[3]: download_public's count)
 	HIP_TRY(hipStreamSynchronize(st));
+	PictureResults res;
+	if (e->lockstep && (rc = lockstep_collect(e, "hmr_gpu_enc_encode: picture", &res))) return rc;      // (refuses an abandoned launch and a row overflow itself)
 	if (getenv("HENC_DEBUG_POST")) {
 		std::vector<PostRow> rows(s.hctu);
 		HIP_TRY(hipMemcpy(rows.data(), e->d_rows, sizeof(PostRow) * s.hctu, hipMemcpyDeviceToHost));
@@ -1111,7 +1195,7 @@ int frame_finish(hmr_gpu_enc *e, int slot, uint8_t *stream, long cap, long *stre
 			fprintf(stderr, "post row %d: dec %d D %d/%d P %d/%d F %d/%d\n", r, rows[r].dec, rows[r].d_claim, rows[r].d_done, rows[r].p_claim, rows[r].p_done, rows[r].f_claim, rows[r].f_done);
 		fprintf(stderr, "post errors %d %d %d %d, sao %d\n", err[0], err[1], err[2], err[3], s.sao);
 	}
-	if (err[0]) {
+	if (err[0]) {      // (single-thread order only: on the row-per-thread path read_record has refused it above, and the rows' bytes come from the record, not from h_ent)
 		hmr_set_error("hmr_gpu_enc_encode: a CTU row's sub-stream outgrew its buffer (%d bytes)", e->row_cap);
 		return HMR_GPU_ERR_HIP;
 	}
@@ -1119,33 +1203,23 @@ int frame_finish(hmr_gpu_enc *e, int slot, uint8_t *stream, long cap, long *stre
 		hmr_set_error("hmr_gpu_enc_encode: the post-decision stage was abandoned by its watchdog");
 		return HMR_GPU_ERR_HIP;
 	}
-	const int rows = s.wpp ? s.hctu : 1;
-	std::vector<uint32_t> row_bytes(rows);
-	size_t total = 0;
-	for (int r = 0; r < rows; r++) total += row_bytes[r] = (uint32_t)e->h_ent[r].bytecnt;
-	if (e->h_bs.size() < total) e->h_bs.resize(total);      // (the host copy holds what the picture took, not the rows' whole buffers)
-	total = 0;
-	for (int r = 0; r < rows; r++) {
-		HIP_TRY(hipMemcpyAsync(e->h_bs.data() + total, e->d_bs + (size_t)r * e->row_cap, row_bytes[r], hipMemcpyDeviceToHost, st));
-		total += row_bytes[r];
-	}
+	std::vector<uint32_t> ent_bytes(s.hctu);      // (single-thread order: the rows' bytes from their coders' records)
+	for (int r = 0; r < s.hctu; r++) ent_bytes[r] = (uint32_t)e->h_ent[r].bytecnt;
+	const uint32_t *row_bytes = e->lockstep ? res.row_bytes : ent_bytes.data();
+	if ((rc = queue_substreams(e, row_bytes, st))) return rc;
 	if (recon) {      // (the device path - k_egress into the staging buffer - plus one copy)
 		if ((rc = narrow_packed(e, e->d_bytes))) return rc;
 		HIP_TRY(hipMemcpyAsync(recon, e->d_bytes, (size_t)s.width * s.height * 3 / 2, hipMemcpyDeviceToHost, st));
 	}
 	HIP_TRY(hipStreamSynchronize(st));
-	const uint32_t *gr = e->h_gather;
-	e->note_stale_predictions(e->lockstep ? gr[3] >> 8 : (uint32_t)err[3]);
-	const double acc = e->lockstep ? frame_acc_dist(s, e->cfg.wfpp_num_threads, [&](int n) { return gr[GATHER_HEAD + n]; })
+	FrameRcOut ro = {0, 0.0, 0.0};
+	if (e->lockstep) ro = res.rc;
+	else e->note_stale_predictions((uint32_t)err[3]);
+	const double acc = e->lockstep ? frame_acc_dist(s, e->cfg.wfpp_num_threads, [&](int n) { return res.dist[n]; })
 				       : frame_acc_dist(s, e->cfg.wfpp_num_threads, [&](int n) { return ((const CtuPublic *)(e->h_public.data() + sizeof(CtuPublic) * n))->distortion; });
 	// (a buffer that is too small loses the access unit; the sequence state has not moved on, but the device pictures have: the caller has to start over)
-	rc = frame_assemble(e, e->f, e->h_bs.data(), row_bytes.data(), stream, cap, stream_bytes);
+	rc = frame_assemble(e, e->f, e->h_bs.data(), row_bytes, stream, cap, stream_bytes);
 	if (rc < 0) return rc;
-	FrameRcOut ro = {0, 0.0, 0.0};
-	if (e->lockstep) {
-		ro.sum_qp = (int)gr[4]; ro.consumed_bits = (double)gr[5];
-		memcpy(&ro.target_pict_size, &gr[6], 8);
-	}
 	end_frame(s, e->st, e->f, acc, &ro);
 	HIP_TRY(hipEventRecord(e->ctx->ev1, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -1166,7 +1240,7 @@ extern "C" int hmr_gpu_enc_encode_source(hmr_gpu_enc *e, int slot, int image_typ
 	HIP_TRY(hipEventRecord(e->ev_frame, st));
 	int rc = set_frame(e, slot, image_type, -1.0);
 	if (rc) return rc;
-	rc = run_ctu_passes(e);
+	rc = e->lockstep ? lockstep_launch(e) : run_ctu_passes(e);
 	if (rc) return rc;
-	return frame_finish(e, slot, stream, cap, stream_bytes, recon);
+	return frame_finish(e, stream, cap, stream_bytes, recon);
 }

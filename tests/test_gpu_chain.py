@@ -19,9 +19,10 @@ DUMPS = {}
 GOLD = json.load(open(os.path.join(ec.GOLDEN, "streams.json")))
 
 
-def encode_chained(lib, case, chain=None, sets=1):
+def encode_chained(lib, case, chain=None, sets=1, refused_first=False):
     """the fixture's clip in chains of `chain` frames (default: sets x E); sets > 1: every engine has `sets` objects (twins sharing its persistent state), so a chain
-    holds up to sets x E frames - an engine's next frame starts inside the same launch when its previous one is finished"""
+    holds up to sets x E frames - an engine's next frame starts inside the same launch when its previous one is finished.  refused_first: before the first chain, the
+    same call with the objects of frames 1 and 2 swapped - frame 0 is set up, frame 1 is refused - which has to leave every object as it found it"""
     g = GOLD[case]
     w, h, frames, keys = g["width"], g["height"], g["frames"], dict(g["keys"])
     cut_at = keys.pop("cut_at", None)
@@ -62,6 +63,14 @@ def encode_chained(lib, case, chain=None, sets=1):
         assert lib.hmr_gpu_enc_load_source(encs[obj_of[f]], slot_of[f], *planes) == 0, lib.hmr_gpu_last_error()
     bufs = [C.create_string_buffer(8 << 20) for _ in range(chain)]
     stream = b""
+    if refused_first:
+        fs = [0, 2, 1]
+        e_arr = (C.c_void_p * 3)(*[encs[obj_of[f]] for f in fs])
+        slots = (C.c_int * 3)(*[slot_of[f] for f in fs])
+        ptrs = (C.c_char_p * 3)(*[C.cast(bufs[i], C.c_char_p) for i in range(3)])
+        caps = (C.c_long * 3)(*[len(bufs[i]) for i in range(3)])
+        assert lib.hmr_gpu_enc_encode_chain(e_arr, 3, None, slots, None, ptrs, caps, (C.c_long * 3)()) < 0
+        assert b"belongs to engine" in lib.hmr_gpu_last_error()
     t0 = time.time()
     for si, first in enumerate(starts):
         fs = list(range(first, min(starts[si + 1] if si + 1 < len(starts) else frames, frames)))
@@ -105,5 +114,14 @@ def encode_chained(lib, case, chain=None, sets=1):
 def test_overlapping_frames_reproduce_the_reference_engine_stream(case, chain, sets):
     lib = libs.load_gpu()
     stream, g = encode_chained(lib, case, chain, sets)
+    assert len(stream) == g["stream_bytes"]
+    assert hashlib.md5(stream).hexdigest() == g["stream_md5"]
+
+
+def test_a_refused_chain_leaves_every_object_as_it_found_it():
+    """a chain refused while its frames are being set up (frame 1 given to the wrong engine, after frame 0 has been set up) makes no launch and moves no object on:
+    the clip encoded behind it is the fixture's stream"""
+    lib = libs.load_gpu()
+    stream, g = encode_chained(lib, "416x240_eng3_wpp_rows", refused_first=True)
     assert len(stream) == g["stream_bytes"]
     assert hashlib.md5(stream).hexdigest() == g["stream_md5"]
