@@ -905,3 +905,4 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 #include "k_encode_walktest.inc"
 #include "k_encode_posttest.inc"
 #include "k_encode_helpertest.inc"
+#include "k_encode_mergetest.inc"

@@ -1417,6 +1417,73 @@ typedef struct hmr_gpu_helper_out {
 } hmr_gpu_helper_out;
 int hmr_gpu_walk_helper_forms(const hmr_gpu_helper_case *cases, int ncases, const uint8_t *arena, size_t arena_bytes, hmr_gpu_helper_out *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * 19. Test aid: the merge evaluation of an 8 x 8 or 16 x 16 CU as the device runs it, and the device-only body of motion_compensate_cu
+ *     For these CUs check_rd_cost_merge (homerhevc_amd/csrc/enc/enc_ctu.h) does not run its candidate loop on the device: quad_load_cands -> quad_prepare (every distinct
+ *     candidate side by side: luma on the worker, chroma on the helper through HJOB_QUAD_C) -> quad_merge_loop (the loop replayed on figures in registers) -> quad_commit
+ *     (one deferred write of the windows of two depths, the per-depth buffers, the CTU's record, the prediction window, Enc::inter_ssq and the node), enc/enc_quad.h.
+ *     Section 16 pins the tiles' arithmetic; this entry pins the replay and the commit, and motion_compensate_cu's three-block fetch from the phase planes
+ *     (tests/test_gpu_merge_forms.py).  It follows section 18's rules: workgroups of a worker wavefront and its real helper wavefront, the pool kernel's LDS places and
+ *     register budget, entered through rows_enter and left through release_helpers, group types of the harness's own; no wait loop of its own (it waits inside
+ *     quad_prepare and helper_wait only), no way out of the worker's loop over its cases but its end.  One CtuPublic in HBM per workgroup is Enc::ctu.  Host pointers,
+ *     synchronous, default context: one upload, one launch, one download per call.
+ *     arena: curr, pred (6144 bytes each: the worker's source / prediction windows as in section 16; multiples of 4) and the phase planes behind sub_y / sub_c in the
+ *     addressing of section 16, row pitches stride_y / stride_c.
+ *     Before every step each 32-bit word of the workgroup's WorkSlow and of its CtuPublic holds 0x12341234 (a byte array of the record that starts at an even offset
+ *     holds 0x34 at even entries, 0x12 at odd ones).
+ *     Step MERGE (node: an 8 x 8 or 16 x 16 CU; `units`: its size * size / 16 4 x 4 units from Geo::abs_index on, depth = 3 or 2):
+ *       filled from the case: the windows, Work::merge_cands (mv, ref_idx), inter_modes, Seq (width, height, margin_y = margin, stride_y, stride_c, perf_mode,
+ *       sign_hiding, chroma_qp_offset), FrameCtx (slice_type P, avg_dist, chroma_weight, sub_y, sub_c), the node's qp;
+ *       planted: every other byte of the node 0xEE, then Node::inter_ref_index = old_ref_index; Work::intra_mode_buffs[k][depth][unit u] = 0x40 + 0x20 k + (u & 15);
+ *       Work::cbf_buffs[0..2][depth][units] and Work::tr_idx_buffs[depth][units] = 0x77; CtuPublic::cbf[k][units] = 0xa0 + k; Enc::inter_ssq[] = 0xEEEEEEEE,
+ *       Enc::inter_ssq_valid = -1; the prediction window = pred;
+ *       then HJOB_NEW_CTU, and the three statements of check_rd_cost_merge: quad_load_cands; quad_prepare<8 | 16>; if (slots >= 0) quad_merge_loop<8 | 16>.
+ *       out: slots (quad_prepare's return value: -1, or the slot of candidate k in bits 4 k .. 4 k + 3), ret (quad_merge_loop's), the node's fields, Enc::inter_ssq /
+ *       inter_ssq_valid, the per-depth buffers and the record's arrays over the units (entry u: unit abs_index + u; entries behind the CU's units are 0), lv / dec: the
+ *       level and the decoded windows of [0] depth + 1 and [1] window 0 - the Y block row by row, then U, then V (an 8 x 8 CU: 64 + 16 + 16 entries, the rest 0) -, pred:
+ *       the whole prediction window after the step, pred_rest: the sum of (i + 1) x byte i over the bytes of that window OUTSIDE the CU's three blocks, modulo 2^32.
+ *       quad_prepare returns -1 and nothing runs behind it (performance_mode 0; a candidate whose block leaves the padded picture - quirk Q12): everything above then
+ *       holds what was planted.
+ *     Step MC (node: a CU of 8, 16, 32 or 64): motion_compensate_cu(node, mv[0]) on the prediction window `pred`.  out: pred, pred_rest.
+ *     stray (both steps): after the harness has put 0x12341234 back over the CU's blocks of the four windows and over the record's cbf / tr_idx / intra_mode / mv_ref_idx
+ *     entries of the CU's units, the number of 32-bit words of WorkSlow and CtuPublic that hold anything else.  cand_* / n_stale_pred are not written by this entry
+ *     (the one-lane twin of this step, oracle/enc_cpu.cpp henc_cpu_merge_cases, reports the candidate list it derived there).
+ *     Refused with HMR_GPU_ERR_ARG and a text (hmr_gpu_last_error) before anything is launched: "step"; "step (the library was built with a helper per chroma plane)"
+ *     (HENC_NHELP = 2: every step); "step (the library was built without the merge tiles)" (MERGE); "node"; "node (MERGE: an 8 x 8 or 16 x 16 CU)"; "node (MC: a CU of
+ *     8 to 64)"; "qp"; "perf_mode"; "chroma_qp_offset"; "sign_hiding"; "avg_dist / chroma_weight"; "ctu_x / ctu_y"; "width / height / margin"; "stride"; "reserved";
+ *     "mv"; "ref_idx"; "inter_modes"; "old_ref_index"; "curr"; "pred"; "a luma prediction block outside the arena"; "a chroma prediction block outside the arena".
+ * ------------------------------------------------------------------------------------------------ */
+enum hmr_gpu_merge_step { HMR_GPU_MERGE_MERGE = 1, HMR_GPU_MERGE_MC };
+typedef struct hmr_gpu_merge_case {
+	int32_t step, node, qp, perf_mode;
+	int32_t ctu_x, ctu_y, width, height;
+	int32_t margin, stride_y, stride_c, sign_hiding;
+	int32_t chroma_qp_offset, old_ref_index, reserved[2];      /* reserved: 0 */
+	int32_t mv[2][2], ref_idx[2], inter_modes[2];               /* the candidate list: x, y in quarter samples; MC: mv[0] */
+	double avg_dist, chroma_weight;
+	int64_t sub_y, sub_c[2], curr, pred;
+} hmr_gpu_merge_case;      /* 152 bytes */
+typedef struct hmr_gpu_merge_out {
+	int32_t slots;
+	uint32_t ret;
+	int32_t skipped, inter_mv[2], inter_ref_index;
+	uint32_t cost, distortion;
+	int32_t merge_flag, merge_idx, inter_mode;
+	uint32_t sum;
+	int32_t inter_cbf[3], inter_tr_idx;
+	uint32_t inter_ssq[3];
+	int32_t inter_ssq_valid;
+	uint32_t stray, pred_rest;
+	int32_t cand_mv[2][2], cand_ref[2], cand_modes[2], n_stale_pred;
+	uint32_t reserved;
+	uint8_t cbf_buffs[3][16], tr_idx_buffs[16];
+	uint8_t rec_cbf[3][16], rec_tr_idx[16], rec_intra_mode[2][16];
+	int8_t rec_mv_ref_idx[16];
+	int16_t lv[2][384], dec[2][384];
+	uint8_t pred[6144];
+} hmr_gpu_merge_out;       /* 9520 bytes */
+int hmr_gpu_walk_merge_forms(const hmr_gpu_merge_case *cases, int ncases, const uint8_t *arena, size_t arena_bytes, hmr_gpu_merge_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -943,4 +943,181 @@ long henc_cpu_encode_frame(void *h, const uint8_t *y, const uint8_t *u, const ui
 	return (long)out.size();
 }
 
+// ---- the merge evaluation of one CU on given input: the one-lane twin of hmr_gpu_walk_merge_forms' MERGE step (include/homer_gpu.h section 19) ----
+// The device replays the candidate loop on figures in registers (enc_quad.h); here the checker's own check_rd_cost_merge runs - get_merge_candidates on neighbour
+// units planted in the CTU's own record, then the sequential loop with motion compensation from a reference picture - and the same outputs are copied out.  Only
+// cases whose vectors are multiples of 8 quarter samples: the prediction is then a copy of the reference picture, whose samples are the bytes of phase plane 0.
+// nbr: per case the units left of the CU's bottom-left unit, above its top-right unit, and the top-right unit (pred_mode -1: not planted; 1 = intra: only that).
+struct henc_cpu_merge_nbr {
+	int32_t pred_mode, inter_mode, mv[2], ref_idx;
+};
+int henc_cpu_merge_cases(const HostCfg *cfg, const hmr_gpu_merge_case *cases, const henc_cpu_merge_nbr *nbr, int ncases, const uint8_t *arena, size_t arena_bytes, hmr_gpu_merge_out *out)
+{
+	if (!cfg || !cases || !nbr || ncases < 1 || !arena || !out) return -3;
+	constexpr uint32_t POISON = 0x12341234u;
+	constexpr int REACH = 40, REACH_C = 20;      // the reference picture is built this many samples around the CU
+	Geo geo[NNODES];
+	make_geo(geo);
+	Seq seq0;
+	const char *why;
+	if (!make_seq(*cfg, seq0, &why)) { fprintf(stderr, "henc_cpu_merge_cases: unsupported configuration: %s\n", why); return -3; }
+	Work *w = new_work();
+	std::vector<CtuInfo> ctu_store(1);
+	CtuInfo &ctu = ctu_store[0];
+	FastTables ft;
+	int rc = 0;
+	for (int i = 0; i < ncases && rc == 0; i++) {
+		const hmr_gpu_merge_case &cs = cases[i];
+		hmr_gpu_merge_out &o = out[i];
+		memset((void *)&o, 0, sizeof o);
+		if (cs.step != HMR_GPU_MERGE_MERGE || cs.node < 5 || cs.node >= 85 || cs.qp < 0 || cs.qp > 51) { rc = -3; break; }
+		const Geo &q = geo[cs.node];
+		const int n = q.size, nc = q.size_chroma, depth = q.depth, units = q.num_part;
+		if (cs.curr < 0 || (size_t)cs.curr + 6144 > arena_bytes || cs.pred < 0 || (size_t)cs.pred + 6144 > arena_bytes) { rc = -3; break; }
+		for (int k = 0; k < 3; k++)
+			if (nbr[3 * i + k].pred_mode == PM_INTER && (nbr[3 * i + k].mv[0] % 8 || nbr[3 * i + k].mv[1] % 8 || abs(nbr[3 * i + k].mv[0]) > 4 * (REACH - 8) || abs(nbr[3 * i + k].mv[1]) > 4 * (REACH - 8))) rc = -3;
+		if (rc) break;
+		// the sequence and the frame: the checker's own configuration, with what the case sets
+		Seq seq = seq0;
+		FrameCtx f;
+		memset((void *)&f, 0, sizeof f);
+		const int gx = cs.ctu_x + q.x, gy = cs.ctu_y + q.y, gxc = (cs.ctu_x >> 1) + q.xc, gyc = (cs.ctu_y >> 1) + q.yc;
+		const int bw = n + 2 * REACH, bwc = nc + 2 * REACH_C;
+		seq.width = cs.width; seq.height = cs.height; seq.margin_y = cs.margin; seq.stride_y = bw; seq.stride_c = bwc;
+		seq.perf_mode = cs.perf_mode; seq.sign_hiding = cs.sign_hiding; seq.chroma_qp_offset = cs.chroma_qp_offset;
+		// the reference picture around the CU: sample (X, Y) is the byte of phase plane 0 at row Y, column X (section 13); 0 where the arena has none
+		std::vector<int16_t> ref[3];
+		ref[0].assign((size_t)bw * bw, 0);
+		ref[1].assign((size_t)bwc * bwc, 0);
+		ref[2].assign((size_t)bwc * bwc, 0);
+		for (int y = 0; y < bw; y++)
+			for (int x = 0; x < bw; x++) {
+				const int64_t at = cs.sub_y + (int64_t)(gy - REACH + y) * 16 * cs.stride_y + gx - REACH + x;
+				if (at >= 0 && (uint64_t)at < arena_bytes) ref[0][(size_t)y * bw + x] = arena[at];
+			}
+		for (int p = 0; p < 2; p++)
+			for (int y = 0; y < bwc; y++)
+				for (int x = 0; x < bwc; x++) {
+					const int64_t at = cs.sub_c[p] + (int64_t)(gyc - REACH_C + y) * 64 * cs.stride_c + gxc - REACH_C + x;
+					if (at >= 0 && (uint64_t)at < arena_bytes) ref[1 + p][(size_t)y * bwc + x] = arena[at];
+				}
+		f.slice_type = SLICE_P; f.qp = cs.qp; f.avg_dist = cs.avg_dist; f.chroma_weight = cs.chroma_weight; f.scene_cut_ctu = -1;
+		// (motion compensation addresses ref[] + gy * stride + gx: the pointers stand where sample (0, 0) of the picture would be)
+		f.ref[0] = ref[0].data() + ((ptrdiff_t)REACH * bw + REACH) - ((ptrdiff_t)gy * bw + gx);
+		f.ref[1] = ref[1].data() + ((ptrdiff_t)REACH_C * bwc + REACH_C) - ((ptrdiff_t)gyc * bwc + gxc);
+		f.ref[2] = ref[2].data() + ((ptrdiff_t)REACH_C * bwc + REACH_C) - ((ptrdiff_t)gyc * bwc + gxc);
+		// the worker: windows from poison, the case's source and prediction windows, the planted buffers
+		uint32_t *slow_words = (uint32_t *)w->slow;
+		for (size_t k = 0; k < sizeof(WorkSlow) / 4; k++) slow_words[k] = POISON;
+		src_t *const cw = w->curr_y;
+		pred_t *const pw = w->pred_y;
+		for (int k = 0; k < 6144; k++) { cw[k] = arena[cs.curr + k]; pw[k] = arena[cs.pred + k]; }
+		static_assert(offsetof(Work, curr_c) == offsetof(Work, curr_y) + 4096 * sizeof(src_t) && offsetof(Work, pred_c) == offsetof(Work, pred_y) + 4096 * sizeof(pred_t), "the windows are one block of Work");
+		for (int u = 0; u < units; u++) {
+			for (int k = 0; k < 2; k++) w->intra_mode_buffs[k][depth][q.abs_index + u] = (uint8_t)(0x40 + 0x20 * k + (u & 15));
+			for (int k = 0; k < 3; k++) w->cbf_buffs[k][depth][q.abs_index + u] = 0x77;
+			w->tr_idx_buffs[depth][q.abs_index + u] = 0x77;
+		}
+		memset((void *)&ctu, 0, sizeof ctu);
+		uint32_t *rec_words = (uint32_t *)(CtuPublic *)&ctu;
+		for (size_t k = 0; k < sizeof(CtuPublic) / 4; k++) rec_words[k] = POISON;
+		for (int u = 0; u < units; u++)
+			for (int k = 0; k < 3; k++) ctu.cbf[k][q.abs_index + u] = (uint8_t)(0xa0 + k);
+		// the neighbour units of the candidate derivation
+		const int np = n >> 2, base = cfg_depth_start(CFG_MAX_CU_DEPTH);
+		const Geo &lb = geo[base + raster2abs(q.raster_index + 16 * (np - 1))], &tr = geo[base + raster2abs(q.raster_index + np - 1)];
+		const int nb_at[3] = {lb.abs_left, tr.abs_top, tr.abs_top_right};
+		for (int k = 0; k < 3; k++) {
+			const henc_cpu_merge_nbr &b = nbr[3 * i + k];
+			if (b.pred_mode < 0) continue;
+			if ((k == 0 && q.x == 0) || (k >= 1 && q.y == 0) || (k == 2 && q.x + n >= 64)) { rc = -3; break; }      // (inside this CTU only)
+			ctu.pred_mode[nb_at[k]] = (uint8_t)b.pred_mode;
+			if (b.pred_mode != PM_INTER) continue;
+			ctu.inter_mode[nb_at[k]] = (uint8_t)b.inter_mode;
+			ctu.mv_ref[nb_at[k]].x = b.mv[0]; ctu.mv_ref[nb_at[k]].y = b.mv[1];
+			ctu.mv_ref_idx[nb_at[k]] = (int8_t)b.ref_idx;
+		}
+		if (rc) break;
+		// the context, as henc_cpu_frame_ctus and ctu_begin build it (no neighbour CTUs)
+		Enc e;
+		memset((void *)&e, 0, sizeof e);
+		e.seq = &seq; e.f = &f; e.T = hmr_host_tables();
+		fast_tables_fill(CpuGrp(), ft, e.T, cs.qp % 6, chroma_qp_table(cs.qp + cs.chroma_qp_offset) % 6);
+		e.ft = &ft;
+		e.geo.p = geo;
+		e.ctus = &ctu; e.ctu_g = &ctu; e.ctu = &ctu;
+		e.w = w;
+		e.nodes = (Node *)(((uintptr_t)w->nodes_fast_store + 15) & ~(uintptr_t)15);
+		e.wrd = w->rd_store;
+		e.node_quad = cs.node >= NODES_RESIDENT ? node_quadrant(cs.node) : -1;
+		e.scratch_a = w->pred_aux; e.scratch_b = w->delta_u; e.mc_tmp_c = w->sub_tmp; e.mc_tmp_y = w->sub_tmp; e.mc_tmp_y_stride = 72; e.adi_c = w->adi;
+		e.ctu_x = cs.ctu_x; e.ctu_y = cs.ctu_y; e.nb_ctus = 0; e.amvp_node = -1; e.last_slog = -1; e.ctu_qp = cs.qp;
+		e.inter_ssq[0] = e.inter_ssq[1] = e.inter_ssq[2] = 0xEEEEEEEEu; e.inter_ssq_valid = -1;
+		Node &nd = node_of(e, cs.node);
+		memset((void *)&nd, 0xEE, sizeof nd);
+		nd.qp = (uint8_t)cs.qp;
+		nd.inter_ref_index = (int8_t)cs.old_ref_index;
+		nd.left_bottom_nb = 0;
+		nd.top_right_nb = nbr[3 * i + 2].pred_mode >= 0;
+		const CpuGrp g;
+		// the list on its own first (the derivation only reads; check_rd_cost_merge derives it again), then the evaluation
+		uint8_t modes[5] = {255, 255, 255, 255, 255};
+		MvCandList list;
+		get_merge_candidates(e, cs.node, list, modes);
+		for (int k = 0; k < 2; k++) { o.cand_mv[k][0] = list.mv[k].x; o.cand_mv[k][1] = list.mv[k].y; o.cand_ref[k] = list.ref_idx[k]; o.cand_modes[k] = modes[k]; }
+		o.slots = -1;
+		o.ret = check_rd_cost_merge(g, e, depth, q.list_index - cfg_depth_start(depth));
+		o.n_stale_pred = e.n_stale_pred;
+		// copy out (section 19), the CU's blocks and entries back to poison, then what else changed
+		o.skipped = nd.skipped; o.inter_mv[0] = nd.inter_mv.x; o.inter_mv[1] = nd.inter_mv.y; o.inter_ref_index = nd.inter_ref_index; o.cost = nd.cost; o.distortion = nd.distortion;
+		o.merge_flag = nd.merge_flag; o.merge_idx = nd.merge_idx; o.inter_mode = nd.inter_mode; o.sum = nd.sum;
+		for (int k = 0; k < 3; k++) { o.inter_cbf[k] = nd.inter_cbf[k]; o.inter_ssq[k] = e.inter_ssq[k]; }
+		o.inter_tr_idx = nd.inter_tr_idx; o.inter_ssq_valid = e.inter_ssq_valid;
+		for (int u = 0; u < units; u++) {
+			const int a = q.abs_index + u;
+			const uint8_t pz = (a & 1) ? 0x12 : 0x34;
+			for (int k = 0; k < 3; k++) { o.cbf_buffs[k][u] = w->cbf_buffs[k][depth][a]; o.rec_cbf[k][u] = ctu.cbf[k][a]; ctu.cbf[k][a] = pz; }
+			o.tr_idx_buffs[u] = w->tr_idx_buffs[depth][a];
+			o.rec_tr_idx[u] = ctu.tr_idx[a]; ctu.tr_idx[a] = pz;
+			for (int k = 0; k < 2; k++) { o.rec_intra_mode[k][u] = ctu.intra_mode[k][a]; ctu.intra_mode[k][a] = pz; }
+			o.rec_mv_ref_idx[u] = ctu.mv_ref_idx[a]; ctu.mv_ref_idx[a] = (int8_t)pz;
+		}
+		for (int k = 0; k < 3; k++) {
+			if (nbr[3 * i + k].pred_mode < 0) continue;
+			const int a = nb_at[k];
+			const uint8_t pz = (a & 1) ? 0x12 : 0x34;
+			ctu.pred_mode[a] = pz; ctu.inter_mode[a] = pz; ctu.mv_ref_idx[a] = (int8_t)pz;
+			ctu.mv_ref[a].x = ctu.mv_ref[a].y = (int32_t)POISON;
+		}
+		for (int wi = 0; wi < 2; wi++) {
+			const int wnd = wi == 0 ? depth + 1 : 0;
+			int at = 0;
+			for (int comp = 0; comp < 3; comp++) {
+				const int m = comp ? nc : n, x = comp ? q.xc : q.x, y = comp ? q.yc : q.y, ds = dec_stride(comp);
+				int16_t *lev = tq_ptr(*w, wnd, comp) + (comp ? (q.abs_index << 4) >> 2 : q.abs_index << 4), *dec = dec_ptr(*w, wnd, comp) + y * ds + x;
+				for (int k = 0; k < m * m; k++, at++) {
+					o.lv[wi][at] = lev[k]; lev[k] = 0x1234;
+					o.dec[wi][at] = dec[(k / m) * ds + k % m]; dec[(k / m) * ds + k % m] = 0x1234;
+				}
+			}
+		}
+		uint32_t rest = 0;
+		for (int k = 0; k < 6144; k++) {
+			o.pred[k] = (uint8_t)pw[k];
+			const int comp = k < 4096 ? 0 : 1, kk = comp ? (k - 4096) % 1024 : k, st = comp ? 32 : 64, x = kk % st, y = kk / st;
+			const int bx = comp ? q.xc : q.x, by = comp ? q.yc : q.y, m = comp ? nc : n;
+			if (!(x >= bx && x < bx + m && y >= by && y < by + m)) rest += (uint32_t)(k + 1) * o.pred[k];
+		}
+		o.pred_rest = rest;
+		uint32_t stray = 0;
+		for (size_t k = 0; k < sizeof(WorkSlow) / 4; k++) stray += slow_words[k] != POISON;
+		for (size_t k = 0; k < sizeof(CtuPublic) / 4; k++) stray += rec_words[k] != POISON;
+		o.stray = stray;
+	}
+	free(w->slow);
+	free(w->rd_store);
+	free(w);
+	return rc;
+}
+
 }  // extern "C"
